@@ -16,8 +16,14 @@ configuration the metric is quoted on) -- the same matrix for every N, row-windo
 i.e. strong scaling of the headline: the per-N values the driver derives its curve from are ONE workload (round 6; the
 N > 1 default used to be papers-like, which made N = 1 and N > 1 different graphs).  BASELINE configs[4] -- ``papers_like``,
 111 M rows sharded over the N ranks, every rank generating ITS OWN shard -- is measured BESIDE the timed steps of every
-N > 1 run and reported as ``config.config5_papers_like`` (all-gather, product and dependent step, MAX over ranks;
+``--full`` N > 1 run and reported as ``config.config5_papers_like`` (all-gather, product and dependent step, MAX over ranks;
 ``--no-config5`` skips it); as the timed workload: ``--workload papers_like`` (1 GPU: 62 ms/step).
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs (``--dump-outputs DIR``)
+and print the line; ``roofline`` there is the arithmetic on the timed steps' own HIP events.  Everything measured or checked
+beside it -- the second preprocess that ``preprocess_ms`` reports, the row-sum check, per-kernel durations, the fp32-feature
+step, the reference-format / cold-cache / host-preprocess runs, the hipSPARSE / rocSPARSE / CPU baselines and, at N > 1, the
+all-gather leg, the other step form and the config-5 leg -- runs with ``--full`` (the ``--no-*`` options still trim it).
 """
 import argparse
 import json
@@ -46,6 +52,12 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beside the headline (baselines, the row-sum check, per-kernel "
+                         "durations, other precisions / formats, the N > 1 legs); a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (C; rank 0's shard at N > 1) as DIR/out.npy in "
+                         "float32 -- a fixed, seeded sample of its rows (ids in DIR/out_rows.npy) when C is above 32 MiB")
     ap.add_argument("--workload", default=None, choices=sorted(synth_graphs.CONFIGS),
                     help="default: reddit_like at every N (round 6: the driver derives its scaling curve from the per-N values, so "
                          "they must be ONE workload -- the headline graph, strong scaling; BASELINE configs[4], papers-like sharded over "
@@ -361,6 +373,24 @@ def config5_leg(world, rank, device, scale=1.0, steps=3):
         return {"error": f"{type(exc).__name__}: {str(exc)[:400]}"}
 
 
+DUMP_BYTES = 32 << 20   # --dump-outputs: at most this much of C (fp32) plus its row ids
+
+
+def dump_outputs(directory, out):
+    """--dump-outputs: the output of the last timed step, so that two builds can be compared output for output (the inputs are
+    seeded).  DIR/out.npy = C in float32 when it fits DUMP_BYTES, else the rows of a fixed, seeded sample in increasing order,
+    their ids in DIR/out_rows.npy (float64)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    keep = max(1, DUMP_BYTES // (4 * max(1, out[0].numel())))
+    if out.shape[0] > keep:
+        rows = torch.randperm(out.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        np.save(os.path.join(directory, "out_rows.npy"), rows.numpy().astype(np.float64))
+        out = out.index_select(0, rows.to(out.device))
+    np.save(os.path.join(directory, "out.npy"), out.float().cpu().numpy())
+
+
 def spawn_ranks(args):
     """``python bench.py --gpus N`` (N > 1) outside torch.distributed.run: start the N ranks as FRESH child processes -- one
     ``python -m torch.distributed.run`` with this command line -- before this process has touched the GPU, relay their output
@@ -478,7 +508,7 @@ def main():
             local_indptr, local_indices = _capi.csr_transpose(local_indptr.contiguous(), local_indices.contiguous(), local_rows, num_cols)
         torch.cuda.empty_cache()
     preprocess_ms = None
-    for _ in range(2):   # first call pays library load / allocator warm-up; report the second (host wall clock, sync'd)
+    for _ in range(2 if args.full else 1):   # first call pays library load / allocator warm-up; --full reports the second (host wall clock, sync'd)
         if args.weighted:   # the first handle (62 GB with its value plane at the papers-like size) must not outlive its purpose
             whandle = handle = None
             torch.cuda.empty_cache()
@@ -500,7 +530,7 @@ def main():
         else:
             handle = voltrix.csr_preprocess_device(local_indptr, local_indices, local_rows, num_cols=num_cols)
         torch.cuda.synchronize()
-        preprocess_ms = (time.perf_counter() - t0) * 1e3
+        preprocess_ms = (time.perf_counter() - t0) * 1e3 if args.full else None
     if args.weighted:
         torch.cuda.empty_cache()   # the plane builder's chunk temporaries
     handle[1].hash_tag = f"bench/{workload}/s{args.scale}/r{rank}of{world}" + ("/transposed" if args.backward else "")
@@ -642,51 +672,55 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     out = out_holder[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
-    # ---- outside the timed region: row-sum check of this rank's result against torch ops on the same gathered B -------
+    # ---- --full, outside the timed region: row-sum check of this rank's result against torch ops on the same gathered B ----
     # (validates shard -> column remap -> all-gather -> SpMM end to end on every rank; fp32 index_add reference, chunked)
-    if not distributed:
-        b_used = gathered
-    elif slab_pipeline:
-        b_used = op.gather_into(bufs[0], feat_local)
-    else:
-        b_used = bufs[(step_no[0] - 1) % len(bufs)] if overlap_timed else bufs[0]
-    col_sums = torch.empty(b_used.shape[0], dtype=torch.float32, device=device)
-    col_abs = torch.empty(b_used.shape[0], dtype=torch.float32, device=device)
-    for q in range(0, b_used.shape[0], 1 << 22):      # by row chunks: a float copy of B is 53 GB at the papers-like size
-        x = b_used[q:q + (1 << 22)].float()
-        col_sums[q:q + (1 << 22)] = x.sum(dim=1)
-        col_abs[q:q + (1 << 22)] = x.abs().sum(dim=1)
-        del x
-    want = torch.zeros(local_rows, dtype=torch.float32, device=device)
-    scale = torch.zeros(local_rows, dtype=torch.float32, device=device)
-    row_of_edge_chunk = 1 << 27
-    ip64 = local_indptr.long()
-    # the shard's column ids are global; the gathered B is laid out in padded shards (voltrix.dist.remap_columns)
-    if world > 1 and gather_mode == "rows":   # the compact buffer: positions the operator computed at setup
-        check_indices = op.compact_ids(local_indices)
-    else:
-        check_indices = vdist.remap_columns(local_indices, parts, rows_padded) if world > 1 else local_indices
-    for e0 in range(0, local_nnz, row_of_edge_chunk):
-        e1 = min(local_nnz, e0 + row_of_edge_chunk)
-        cols = check_indices[e0:e1].long()
-        rows = torch.searchsorted(ip64, torch.arange(e0, e1, device=device), right=True) - 1
-        w_e = edge_values[e0:e1] if edge_values is not None else 1.0
-        want.index_add_(0, rows, col_sums[cols] * w_e)
-        scale.index_add_(0, rows, col_abs[cols] * w_e)
-        del cols, rows
-    got = torch.zeros(local_rows, dtype=torch.float32, device=device)
-    for q in range(0, local_rows, 1 << 22):
-        got[q:q + (1 << 22)] = out[q:q + (1 << 22)].sum(dim=1)
-    check_err = float(((got - want).abs() / (scale + 1e-6)).max()) if local_rows else 0.0
-    if distributed:
-        t = torch.tensor([check_err], device=device, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        check_err = float(t)
-    # edge values enter the MFMA as fp16: each term carries their rounding (2^-11 relative to |w b|), so the weighted
-    # bound is that unit roundoff on top of the unweighted bound
-    check_tol = 1e-4 + (0.0 if edge_values is None else 2.0 ** -11)
-    assert check_err < check_tol, f"row-sum check failed: {check_err} (tolerance {check_tol})"
+    check_err = None
+    if args.full:
+        if not distributed:
+            b_used = gathered
+        elif slab_pipeline:
+            b_used = op.gather_into(bufs[0], feat_local)
+        else:
+            b_used = bufs[(step_no[0] - 1) % len(bufs)] if overlap_timed else bufs[0]
+        col_sums = torch.empty(b_used.shape[0], dtype=torch.float32, device=device)
+        col_abs = torch.empty(b_used.shape[0], dtype=torch.float32, device=device)
+        for q in range(0, b_used.shape[0], 1 << 22):      # by row chunks: a float copy of B is 53 GB at the papers-like size
+            x = b_used[q:q + (1 << 22)].float()
+            col_sums[q:q + (1 << 22)] = x.sum(dim=1)
+            col_abs[q:q + (1 << 22)] = x.abs().sum(dim=1)
+            del x
+        want = torch.zeros(local_rows, dtype=torch.float32, device=device)
+        scale = torch.zeros(local_rows, dtype=torch.float32, device=device)
+        row_of_edge_chunk = 1 << 27
+        ip64 = local_indptr.long()
+        # the shard's column ids are global; the gathered B is laid out in padded shards (voltrix.dist.remap_columns)
+        if world > 1 and gather_mode == "rows":   # the compact buffer: positions the operator computed at setup
+            check_indices = op.compact_ids(local_indices)
+        else:
+            check_indices = vdist.remap_columns(local_indices, parts, rows_padded) if world > 1 else local_indices
+        for e0 in range(0, local_nnz, row_of_edge_chunk):
+            e1 = min(local_nnz, e0 + row_of_edge_chunk)
+            cols = check_indices[e0:e1].long()
+            rows = torch.searchsorted(ip64, torch.arange(e0, e1, device=device), right=True) - 1
+            w_e = edge_values[e0:e1] if edge_values is not None else 1.0
+            want.index_add_(0, rows, col_sums[cols] * w_e)
+            scale.index_add_(0, rows, col_abs[cols] * w_e)
+            del cols, rows
+        got = torch.zeros(local_rows, dtype=torch.float32, device=device)
+        for q in range(0, local_rows, 1 << 22):
+            got[q:q + (1 << 22)] = out[q:q + (1 << 22)].sum(dim=1)
+        check_err = float(((got - want).abs() / (scale + 1e-6)).max()) if local_rows else 0.0
+        if distributed:
+            t = torch.tensor([check_err], device=device, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            check_err = float(t)
+        # edge values enter the MFMA as fp16: each term carries their rounding (2^-11 relative to |w b|), so the weighted
+        # bound is that unit roundoff on top of the unweighted bound
+        check_tol = 1e-4 + (0.0 if edge_values is None else 2.0 ** -11)
+        assert check_err < check_tol, f"row-sum check failed: {check_err} (tolerance {check_tol})"
 
     kernel_ms = sum(s.elapsed_time(e) for s, e in kernel_events) / len(kernel_events)
     if distributed:
@@ -694,19 +728,22 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         kernel_ms = float(t)
 
-    # ---- per-kernel durations of a step (outside the timed region): every launch of the operator bracketed by its own
+    # ---- --full: per-kernel durations of a step (outside the timed region): every launch of the operator bracketed by its own
     # ---- HIP event pair on its own stream (voltrix.utils.KernelTimer); the panel kernel runs beside the window kernel
-    from voltrix.utils import KernelTimer
+    kernels_ms = None
+    if args.full:
+        from voltrix.utils import KernelTimer
 
-    with KernelTimer() as timer:
-        for _ in range(10):
-            step()
-    kernels_ms = {k: round(v[1], 4) for k, v in timer.summary().items()}
+        with KernelTimer() as timer:
+            for _ in range(10):
+                step()
+        kernels_ms = {k: round(v[1], 4) for k, v in timer.summary().items()}
 
-    # ---- the like-for-like step for the fp32 baselines: the same operator call on fp32 features, outside
-    # ---- the timed region (the reference feeds fp32; here they become scaled fp16 or exact fp32 tiles: `config.fp32_in_runs_as`)
+    # ---- --full: the like-for-like step for the fp32 baselines: the same operator call on fp32 features,
+    # ---- outside the timed region (the reference feeds fp32; here they become scaled fp16 or exact fp32 tiles: `config.fp32_in_runs_as`)
     fp32_in_ms = None
-    if world == 1 and is_f16 and whandle is None and not args.no_cpu_baseline and gathered.numel() * 4 < (8 << 30):
+    if (args.full and world == 1 and is_f16 and whandle is None and not args.no_cpu_baseline
+            and gathered.numel() * 4 < (8 << 30)):
         feat32 = gathered.float()
         call32 = lambda: voltrix.spmm(*handle, num_nodes=local_rows, num_edges=local_nnz, feat=feat32)  # noqa: E731
         for _ in range(3):
@@ -758,29 +795,30 @@ def main():
                     "stores from the loop; windows above the cut length in interleaved units + combine pass")
         return "natural window order" if s == 0 else f"balance schedule, chunk {ORDER_CHUNKS.get(s)}"
 
-    # ---- untimed comparison runs (N = 1): the window format alone, and a cold-cache timing --------------------------------
+    # ---- untimed comparison runs (--full; N = 1): the window format alone, and a cold-cache timing --------------------------
     extras = {"first_call_ms": first_call_ms, "handle_bytes": handle_bytes,
               "tuner": dict(tuner_stats, note="sweeps / candidates timed / choices taken from the persisted exact key / from the "
                                               "persisted graph-statistics bucket, up to and including the first call")}
     if distributed:
-        # the two halves of a step on their own ("report all-gather time and SpMM time separately + combined"):
-        # three all-gathers back to back on the communication stream, MAX over ranks; the local SpMM is roofline.kernel_ms
-        dist.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        with torch.cuda.stream(main_stream):
-            for _ in range(3):
-                op.gather_into(bufs[0], feat_local)
-        torch.cuda.synchronize()
-        t = torch.tensor([(time.perf_counter() - t0) / 3 * 1e3], device=device, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        extras["allgather_ms"] = float(t)
+        if args.full:
+            # the two halves of a step on their own ("report all-gather time and SpMM time separately + combined"):
+            # three all-gathers back to back on the communication stream, MAX over ranks; the local SpMM is roofline.kernel_ms
+            dist.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            with torch.cuda.stream(main_stream):
+                for _ in range(3):
+                    op.gather_into(bufs[0], feat_local)
+            torch.cuda.synchronize()
+            t = torch.tensor([(time.perf_counter() - t0) / 3 * 1e3], device=device, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            extras["allgather_ms"] = float(t)
         extras["allgather_mode"] = gather_mode + (f", {args.slabs} feature slabs pipelined" if slab_pipeline else "")
         if exchange_choice is not None:
             extras["exchange_choice"] = exchange_choice   # what the warm-up measured (MAX over ranks) and what it kept
         extras["allgather_bytes_received_per_rank"] = op.exchange_bytes_received(num_feats, gathered.element_size())
         extras["local_spmm_ms"] = kernel_ms
-        if can_overlap:
+        if args.full and can_overlap:
             # the other form of the step, K steps between barriers like the timed region (MAX over ranks): with the dependent
             # step timed (default) this is what INDEPENDENT products would get from overlapping the exchange of step k + 1
             # with the product of step k; with --overlap-steps it is the dependent chain
@@ -812,7 +850,7 @@ def main():
             ref = [json.loads(ln) for ln in open(ref_path) if ln.startswith("{")][-1]
             extras["single_gpu_same_workload"] = {"ms_per_step": ref["ms_per_step"], "value": ref["value"], "unit": ref["unit"],
                                                   "source": os.path.relpath(ref_path, os.path.dirname(os.path.abspath(__file__)))}
-    if world == 1 and not args.no_reference_formats:
+    if args.full and world == 1 and not args.no_reference_formats:
         def time_ms(fn, iters=10):
             fn()
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -876,7 +914,7 @@ def main():
         extras["cold_cache_ms"] = sorted(cold)[len(cold) // 2]
         del flush
 
-    if world > 1 and not args.no_config5 and workload == "reddit_like":
+    if args.full and world > 1 and not args.no_config5 and workload == "reddit_like":
         extras["config5_papers_like"] = config5_leg(world, rank, device, scale=args.config5_scale)
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -997,7 +1035,7 @@ def main():
             },
         }
         line["config"].update(extras)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             vb = vendor_baseline(local_indptr, local_indices, num_nodes, num_feats, device)
             if "ms" in vb:
                 vb["speedup_of_this_work"] = vb["ms"] / ms_per_step

@@ -1,6 +1,6 @@
 """Round 6: who starts a program from inside bench.py?  Runs a script in-process with a Python audit hook that
 prints the stack of every spawn / exec / fork (subprocess.Popen, os.exec*, os.posix_spawn, os.fork, os.system).
-    python harness/experiments/audit_exec.py bench.py --no-cpu-baseline --no-reference-formats"""
+    python harness/experiments/audit_exec.py bench.py --full --no-cpu-baseline --no-reference-formats"""
 import runpy
 import sys
 import traceback

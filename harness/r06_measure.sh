@@ -32,16 +32,16 @@ lines)
   bash harness/final_measure.sh lines r06/final3
   for ARGS in "--backward" "--weighted --backward" "--weighted --weighted-plane"; do
     NAME=$(echo "$ARGS" | tr -d ' ' | tr -s '-' '_')
-    timeout -k 10 400 python bench.py $ARGS --no-cpu-baseline --no-reference-formats > $O/bench_reddit_like_f128${NAME}_final.json 2> $O/bench_reddit$NAME.err
+    timeout -k 10 400 python bench.py $ARGS --full --no-cpu-baseline --no-reference-formats > $O/bench_reddit_like_f128${NAME}_final.json 2> $O/bench_reddit$NAME.err
   done
-  timeout -k 10 300 python bench.py --gpus 2 --backend gloo --one-device --workload reddit_like --feat 128 --scale 0.25 --config5-scale 0.004 --steps 10 --warmup 3 --no-cpu-baseline --no-reference-formats > $O/bench_gpus2_one_device_dependent_step.json 2> $O/bench_gpus2.err
-  timeout -k 10 300 python bench.py --gpus 1 --force-dist --workload reddit_like --feat 128 --steps 10 --warmup 3 --no-cpu-baseline --no-reference-formats > $O/bench_force_dist_1rank_rccl.json 2> $O/bench_force_dist.err
+  timeout -k 10 300 python bench.py --gpus 2 --backend gloo --one-device --workload reddit_like --feat 128 --scale 0.25 --config5-scale 0.004 --steps 10 --warmup 3 --full --no-cpu-baseline --no-reference-formats > $O/bench_gpus2_one_device_dependent_step.json 2> $O/bench_gpus2.err
+  timeout -k 10 300 python bench.py --gpus 1 --force-dist --workload reddit_like --feat 128 --steps 10 --warmup 3 --full --no-cpu-baseline --no-reference-formats > $O/bench_force_dist_1rank_rccl.json 2> $O/bench_force_dist.err
   ;;
 widths)
   # SURVEY 8(d) "feat_dim sweep F in {32, 128, 512} on configs 2-4": the widths the `lines` part does not carry
   for WF in products_like:32 powerlaw_4m:32 powerlaw_4m:128 powerlaw_4m:512; do
     W=${WF%%:*}; F=${WF##*:}
-    timeout -k 10 500 python bench.py --workload $W --feat $F --steps 5 --warmup 2 --no-cpu-baseline --no-reference-formats > $O/bench_${W}_f${F}_final.json 2> $O/bench_${W}_f$F.err || tail -3 $O/bench_${W}_f$F.err
+    timeout -k 10 500 python bench.py --workload $W --feat $F --steps 5 --warmup 2 --full --no-cpu-baseline --no-reference-formats > $O/bench_${W}_f${F}_final.json 2> $O/bench_${W}_f$F.err || tail -3 $O/bench_${W}_f$F.err
     python -c "import json; d=json.loads(open('$O/bench_${W}_f${F}_final.json').read().strip().splitlines()[-1]); print('$W', $F, round(d['ms_per_step'], 3), round(d['roofline']['frac'], 4), d['config'].get('tile'))"
   done
   ;;

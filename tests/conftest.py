@@ -26,6 +26,24 @@ def load_csr_fixture(name):
     return {k: g[k] for k in g.files}
 
 
+def load_sprandom_bits(n, density, seed):
+    """Row bitmaps of the adjacency of the reference's seeded ``sp.random(n, n, density)`` input: uint8 [n, ceil(n / 8)].
+    Small inputs are one file (``sprandom_N<n>_d<density>_seed<seed>.npz``); larger ones are stored in row blocks
+    (``....part<k>.npz``, each under 1 MiB) and joined here."""
+    stem = os.path.join(GOLDEN, f"sprandom_N{n}_d{density}_seed{seed}")
+    if os.path.exists(stem + ".npz"):
+        return np.load(stem + ".npz")["bits"]
+    parts, k = [], 0
+    while os.path.exists(path := f"{stem}.part{k}.npz"):
+        g = np.load(path)
+        assert int(g["row0"]) == sum(p.shape[0] for p in parts), path
+        parts.append(g["bits"])
+        k += 1
+    bits = np.concatenate(parts)
+    assert bits.shape[0] == n
+    return bits
+
+
 @pytest.fixture(params=CSR_FIXTURES)
 def csr_fixture(request):
     return load_csr_fixture(request.param)

@@ -43,3 +43,38 @@ def test_multi_gpu_defaults_are_one_workload_and_the_collective(monkeypatch):
     src = open(bench.__file__).read()
     assert 'workload = args.workload or "reddit_like"' in src          # N = 1 and N > 1 alike
     assert 'extras["config5_papers_like"] = config5_leg(' in src
+
+
+def test_plain_run_is_the_default_and_dumps_are_opt_in(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` is the lean run: --full (every measurement beside the headline) and
+    --dump-outputs are opt-in, and --steps is the number of timed steps."""
+    import sys
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse_args()
+    assert args.full is False and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse_args()
+    assert args.full is True and args.dump_outputs == "d"
+
+
+def test_dump_outputs_samples_large_outputs_with_a_fixed_seed(tmp_path, monkeypatch):
+    """C above the budget: a fixed, seeded sample of its rows in increasing order, the row ids beside it; the same rows on
+    every call.  C within the budget: all of it."""
+    import numpy as np
+    import torch
+
+    c = torch.arange(100 * 8, dtype=torch.float32).reshape(100, 8)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 * 8 * 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), c)
+    rows = np.load(tmp_path / "a" / "out_rows.npy")
+    got = np.load(tmp_path / "a" / "out.npy")
+    assert rows.dtype == np.float64 and got.dtype == np.float32 and got.shape == (10, 8)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(got, c.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "out_rows.npy"))
+    assert np.array_equal(got, np.load(tmp_path / "b" / "out.npy"))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * 8 * 4)
+    bench.dump_outputs(str(tmp_path / "all"), c.half())
+    assert sorted(os.listdir(tmp_path / "all")) == ["out.npy"]
+    assert np.array_equal(np.load(tmp_path / "all" / "out.npy"), c.numpy())

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 def test_bench_line_carries_the_contract(tmp_path):
     env = dict(os.environ, VOLTRIX_TUNE_SPACE="none")
     run = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-                          "--scale", "0.05", "--tune", "none"], capture_output=True, text=True, env=env, timeout=900)
+                          "--scale", "0.05", "--tune", "none", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                       # ONE line
@@ -50,7 +50,7 @@ def test_bench_gpus_2_starts_its_own_ranks(tmp_path):
     env["VOLTRIX_TUNE_SPACE"] = "none"
     run = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo", "--one-device",
                           "--scale", "0.01", "--workload", "reddit_like", "--steps", "3", "--warmup", "1", "--tune", "none",
-                          "--gather", "collective", "--config5-scale", "0.002"], capture_output=True, text=True, env=env, timeout=900)
+                          "--gather", "collective", "--config5-scale", "0.002", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -69,3 +69,42 @@ def test_bench_gpus_2_starts_its_own_ranks(tmp_path):
     assert cfg["allgather_ms"] > 0 and cfg["local_spmm_ms"] > 0 and cfg["step_independent_ms"] > 0
     # the dependent step cannot be shorter than its two halves one after the other allow
     assert line["ms_per_step"] >= 0.5 * max(cfg["allgather_ms"], cfg["local_spmm_ms"])
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_output(tmp_path):
+    """Without --full the run only sets up, warms up, times the K steps, writes the last step's C (--dump-outputs) and prints
+    the line: no baselines, no check, no per-kernel or comparison runs.  The dumped C is the product of the seeded inputs."""
+    import numpy as np
+    import torch
+
+    import synth_graphs
+    from oracle import torch_ref
+
+    env = dict(os.environ, VOLTRIX_TUNE_SPACE="none")
+    dump = tmp_path / "outputs"
+    run = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--scale", "0.05", "--tune", "none", "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, env=env, timeout=900)
+    assert run.returncode == 0, run.stderr[-3000:]
+    lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"] == "spmm_gflops" and line["unit"] == "GFLOP/s" and line["higher_is_better"] is True
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f16" and line["ms_per_step"] > 0
+    cfg = line["config"]
+    assert abs(line["value"] - 2 * cfg["nnz"] * cfg["feat"] / (line["ms_per_step"] * 1e-3) / 1e9) < 1e-6 * line["value"]
+    assert "cpu_baseline" not in line and "vendor_gpu_baseline" not in line
+    for key in ("window_format_ms", "cold_cache_ms", "preprocess_from_host", "one_launch_form_ms"):
+        assert key not in cfg, key
+    assert cfg["rowsum_check_max_rel_err"] is None and cfg["fp32_in_ms_per_step"] is None and cfg["preprocess_ms"] is None
+    assert line["roofline"]["kernels_ms"] is None and line["roofline"]["kernel_ms"] > 0
+    # C of the last timed step, all rows (small enough), against torch.sparse.mm on the same seeded inputs
+    assert sorted(os.listdir(dump)) == ["out.npy"]
+    got = np.load(dump / "out.npy")
+    assert got.dtype == np.float32 and got.shape == (cfg["num_nodes"], cfg["feat"])
+    indptr, indices, _ = synth_graphs.generate("reddit_like", device="cuda", scale=0.05)
+    gen = torch.Generator(device="cuda").manual_seed(1234)
+    feat = torch.randn(cfg["num_nodes"], cfg["feat"], generator=gen, device="cuda", dtype=torch.float32).half()
+    ref = torch_ref.spmm(indptr.cpu(), indices.cpu(), feat.float().cpu(), cfg["num_nodes"])
+    rel = float((torch.from_numpy(got) - ref).norm() / ref.norm())
+    assert rel < 1e-5, rel

@@ -133,7 +133,7 @@ def test_bench_n_gt_1_branch_with_a_one_rank_rccl_group(tmp_path, extra):
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", VOLTRIX_TUNE_SPACE="none")
     run = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--force-dist", "--workload",
                           "papers_like", "--scale", "0.002", "--steps", "3", "--warmup", "1", "--tune", "none",
-                          "--no-cpu-baseline", *extra], capture_output=True, text=True, env=env, timeout=900)
+                          "--no-cpu-baseline", "--full", *extra], capture_output=True, text=True, env=env, timeout=900)
     assert run.returncode == 0, run.stderr[-3000:]
     line = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["steps"] == 3 and line["value"] > 0
@@ -160,7 +160,7 @@ def test_bench_two_ranks_share_one_device_over_gloo(extra):
     run = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2",
                           "--one-device", "--backend", "gloo", "--workload", "reddit_like", "--scale", "0.1", "--steps", "2",
-                          "--warmup", "1", "--tune", "none", "--config5-scale", "0.001", *extra], capture_output=True, text=True,
+                          "--warmup", "1", "--tune", "none", "--config5-scale", "0.001", "--full", *extra], capture_output=True, text=True,
                          env=env, timeout=900)
     assert run.returncode == 0, run.stderr[-3000:]
     line = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1])

@@ -187,7 +187,7 @@ def test_two_level_reddit_like_full_size(cuda_device, monkeypatch):
     plan.parts = None
 
 
-def test_format_policy_is_decided_in_csr_preprocess_at_full_size(cuda_device, monkeypatch):
+def test_format_policy_is_decided_in_csr_preprocess_at_full_size(cuda_device, monkeypatch, tmp_path):
     """The default mode (VOLTRIX_HYBRID=auto) at BASELINE size: ``csr_preprocess_device`` attaches the two-level side-car to the
     reddit-like graph (55 % of the edges in shared columns) and not to its uniform-column variant (29 %: the plan builder stops
     after its count phase -- nothing of the losing form is built); the operator then runs the chosen form without any timing
@@ -223,7 +223,7 @@ def test_format_policy_is_decided_in_csr_preprocess_at_full_size(cuda_device, mo
     assert torch.equal(out, one)
     two.fused = None
     monkeypatch.setenv("VOLTRIX_HYBRID", "tune")
-    monkeypatch.setenv("VOLTRIX_TUNED_STORE", "/tmp/voltrix_policy_test_tuned.json")
+    monkeypatch.setenv("VOLTRIX_TUNED_STORE", str(tmp_path / "tuned.json"))
     out_t = voltrix.spmm(*handle, num_nodes=n, num_edges=e, feat=x)
     assert list(two.format_choice.values())[0] in ("two-level", "window") and torch.equal(out_t, out)
 

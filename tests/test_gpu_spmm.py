@@ -19,7 +19,7 @@ import torch
 
 import synth_graphs
 import voltrix
-from conftest import load_csr_fixture
+from conftest import load_csr_fixture, load_sprandom_bits
 from oracle import oracle_np, torch_ref
 from voltrix import capi
 
@@ -97,13 +97,12 @@ def test_reference_test_inputs_with_autotune(cuda_device, monkeypatch):
 def test_reference_test_spmm_default_case(cuda_device, monkeypatch):
     """The reference's tests/test_spmm.py with ITS OWN defaults (:101-106): seed 20, N = 8192, density 0.1 (6.7 M edges),
     F = 512, fp32 features, hash_tag set by the caller -- on the committed CSR arrays of that input
-    (tests/golden/sprandom_N8192_d0.1_seed20.npz; sp.random streams differ across numpy versions).  The reference prints
+    (tests/golden/sprandom_N8192_d0.1_seed20.part*.npz; sp.random streams differ across numpy versions).  The reference prints
     "difference rate: 0.000%" against cuSPARSE; the same criterion (calc_diff x 100 rounds to 0.000) against the oracle call
     torch.sparse.mm, plus the element-wise bound of the scaled-fp16 operand."""
     monkeypatch.setenv("VOLTRIX_TUNE_SPACE", "default")
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sprandom_N8192_d0.1_seed20.npz"))
     n, f = 8192, 512
-    dense = np.unpackbits(z["bits"], axis=1)[:, :n].astype(bool)      # rows stored as bitmaps, as tests/test_oracle_goldens.py reads them
+    dense = np.unpackbits(load_sprandom_bits(n, 0.1, 20), axis=1)[:, :n].astype(bool)      # rows stored as bitmaps, as tests/test_oracle_goldens.py reads them
     indptr_np = np.concatenate([[0], np.cumsum(dense.sum(1))]).astype(np.int32)
     indices_np = np.nonzero(dense)[1].astype(np.int32)
     assert len(indices_np) == 6710886 and len(indptr_np) == n + 1           # the nnz SURVEY.md section 8c records for this input

@@ -236,3 +236,15 @@ def test_finalists_of_a_sampled_sweep_cover_other_schedules():
     assert [g["SCHED"] for g in got] == [4, 2, 3]
     assert pick_finalists(timed[:2], 3) == [timed[0][1], timed[1][1]]          # one schedule only: the runner-up
     assert pick_finalists([(1.0, {"A": 1})], 3) == [{"A": 1}]
+
+
+def test_parallel_compiles_follow_max_jobs_not_the_host(monkeypatch):
+    """Kernels are compiled $MAX_JOBS at a time (else as many as the CPUs this process may use), never more than the cap and
+    never more than there are kernels: os.cpu_count() of a shared many-core host would start hundreds of hipcc chains."""
+    monkeypatch.setenv("MAX_JOBS", "16")
+    assert vcompiler.parallel_compiles(315) == 16 and vcompiler.parallel_compiles(3) == 3
+    monkeypatch.setenv("MAX_JOBS", "1000")
+    assert vcompiler.parallel_compiles(315) == vcompiler.MAX_PARALLEL_COMPILES
+    monkeypatch.delenv("MAX_JOBS")
+    monkeypatch.setattr(os, "cpu_count", lambda: 512)
+    assert 1 <= vcompiler.parallel_compiles(315) <= min(len(os.sched_getaffinity(0)), vcompiler.MAX_PARALLEL_COMPILES)

@@ -9,15 +9,14 @@ import pytest
 import scipy.sparse as sp
 import torch
 
-from conftest import GOLDEN, load_csr_fixture
+from conftest import GOLDEN, load_csr_fixture, load_sprandom_bits
 from oracle import oracle_c, oracle_np, torch_ref
 
 
 def _load_sprandom_fixture(c):
     """Committed adjacency (row bitmaps) of one of the reference's own seeded test inputs -> CSR with sorted rows, exactly
     what ``np.random.seed(s); sp.random(N, N, density=d, format="csr")`` returns with the numpy / scipy of SURVEY.md 8c."""
-    g = np.load(os.path.join(GOLDEN, f"sprandom_N{c['N']}_d{c['density']}_seed{c['seed']}.npz"))
-    dense = np.unpackbits(g["bits"], axis=1)[:, : c["N"]].astype(bool)
+    dense = np.unpackbits(load_sprandom_bits(c["N"], c["density"], c["seed"]), axis=1)[:, : c["N"]].astype(bool)
     rows, cols = np.nonzero(dense)          # row-major: rows ascending, columns ascending inside a row
     indptr = np.zeros(c["N"] + 1, dtype=np.int32)
     indptr[1:] = np.cumsum(np.bincount(rows, minlength=c["N"]))

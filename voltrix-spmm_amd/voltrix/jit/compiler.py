@@ -158,6 +158,18 @@ def get_tmp_dir() -> str:
     return os.path.join(get_default_user_dir(), "tmp")
 
 
+MAX_PARALLEL_COMPILES = 32
+
+
+def parallel_compiles(count: int) -> int:
+    """How many of ``count`` kernels to compile at once: ``$MAX_JOBS`` when set, else the CPUs this process may run on, at
+    most MAX_PARALLEL_COMPILES.  Never ``os.cpu_count()``: on a shared many-core host that is the whole machine, and every
+    compile is a chain of processes (hipcc, clang, lld)."""
+    env = os.environ.get("MAX_JOBS", "")
+    limit = int(env) if env.isdigit() and int(env) > 0 else len(os.sched_getaffinity(0))
+    return max(1, min(count, limit, MAX_PARALLEL_COMPILES))
+
+
 def get_cache_dir() -> str:
     return os.path.join(get_default_user_dir(), "cache")
 

@@ -11,6 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 import torch
 
 from ..jit import build, cpp_format, generate
+from ..jit.compiler import parallel_compiles
 from . import bmat_swizzle, hmat_gem, preprocess, spmm
 
 
@@ -58,7 +59,7 @@ def prebuild(feature_widths=(32, 64, 128), workers=None, prune=False) -> int:
     """``prune``: afterwards remove every other ``kernel.*`` directory of the cache (entries of older header versions --
     the cache key hashes the include tree -- which would only travel to the GPU box as dead weight)."""
     todo = jobs(feature_widths)
-    workers = workers or max(1, min(len(todo), os.cpu_count() or 1))
+    workers = workers or parallel_compiles(len(todo))
     with ThreadPoolExecutor(max_workers=workers) as pool:
         runtimes = list(pool.map(lambda j: build(*j), todo))
     if prune and runtimes:

@@ -28,7 +28,7 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import Any, Callable, Dict, Optional
 
 from ..jit import build, cpp_format, generate
-from ..jit.compiler import get_default_user_dir, put
+from ..jit.compiler import get_default_user_dir, parallel_compiles, put
 from ..project import DEBUG_FLAG, PRINT_AUTOTUNE_FLAG
 
 
@@ -182,7 +182,7 @@ class JITTuner:
             self.stats["sweeps"] += 1
 
         def build_all(points):
-            workers = max(1, min(len(points), os.cpu_count() or 1))
+            workers = parallel_compiles(len(points))
             with ThreadPoolExecutor(max_workers=workers) as pool:
                 futures = [pool.submit(_build_one, name, arg_defs, render(tk), tk) for tk in points]
                 built = [f.result() for f in futures]
