@@ -128,7 +128,20 @@ def _launch(handle, n, e, feat, is_f16, tile, stream=None, prefill=float("nan"))
 
 @pytest.mark.parametrize("kind", ["f16", "bf16", "f32"])
 def test_every_ahead_of_time_tile_through_the_c_abi(cuda_device, kind):
-    g = load_csr_fixture("skewed_1005")  # N % 16 = 13, empty rows, windows from 1 to >100 TC blocks
+    _every_ahead_of_time_tile(load_csr_fixture("skewed_1005"), kind)  # N % 16 = 13, empty rows, windows from 1 to >100 TC blocks
+
+
+@pytest.mark.parametrize("kind", ["f16", "bf16", "f32"])
+def test_every_ahead_of_time_tile_through_the_c_abi_on_cut_windows(cuda_device, kind):
+    """The same on tests/tile_matrix_cases.py's G1: hub windows beside every XCD range boundary, N % 16 = 13, every column
+    gathered -- the FS 256 and 8-wave tiles of the library on long windows in all XCD ranges."""
+    import tile_matrix_cases
+
+    indptr, indices, n = tile_matrix_cases.graph_cuts()
+    _every_ahead_of_time_tile({"indptr": indptr, "indices": indices, "num_nodes": n}, kind)
+
+
+def _every_ahead_of_time_tile(g, kind):
     n, e = int(g["num_nodes"]), len(g["indices"])
     handle = voltrix.csr_fused_preprocess_kernel(torch.from_numpy(g["indptr"]).cuda(),
                                                  torch.from_numpy(g["indices"]).cuda(), n)[:3]

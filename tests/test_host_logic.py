@@ -143,3 +143,93 @@ def test_every_default_panel_tile_is_instantiated():
             for rb in (2, 4):
                 fs, depth, ksteps = hybrid.default_panel_tile(feat, waves, rb)
                 assert (fs, depth, waves, rb, ksteps) in inst, (feat, waves, rb)
+
+
+# ---- tests/test_gpu_tile_matrix.py: what its GPU cases rely on -------------------------------------------------------------
+def test_shipped_tuned_defaults_lie_in_the_space_of_their_own_keys(monkeypatch):
+    """The store only takes a choice that is in the space ``spmm_kernel`` computes for the call (``stored in list(space)``): a
+    shipped entry outside it is silently ignored.  Windows are short (stream and two-slot points) when the bucket's mean TC
+    blocks per window is at most STREAM_MAX_BLOCKS_PER_WINDOW; the half-octave that straddles the limit may be either."""
+    import ast
+    import math
+
+    import tile_matrix_cases as tm
+
+    monkeypatch.setenv("VOLTRIX_TUNE_SPACE", "default")
+    store = tm.shipped_defaults()
+    assert len(store) >= 100
+    limit_x2 = 2 * math.log2(spmm_mod.STREAM_MAX_BLOCKS_PER_WINDOW)
+    for key, point in store.items():
+        keys = ast.literal_eval(key.split("|", 1)[1])
+        width = 256 if keys["embedding_dim"] == "wide" else keys["embedding_dim"]
+        dtype = keys["dtype"]
+        eb = 4 if dtype == "torch.float32" else 2
+        mean_x2 = ast.literal_eval(keys["graph_bucket"])["log2_mean_blocks_x2"]
+        shorts = [s for s in (True, False) if (mean_x2 - 0.5 <= limit_x2 if s else mean_x2 + 0.5 > limit_x2)]
+        spaces = [spmm_mod.tile_space(width, eb, dtype == "torch.bfloat16",
+                                      spmm_mod.TWO_LEVEL_LDS_BUDGET if keys["two_level"] else None, weighted=keys["weighted"],
+                                      stream_ok=short and not keys.get("row_map") and not keys["two_level"], shallow_ok=short)
+                  for short in shorts]
+        assert any(point in list(space) for space in spaces), (key, point)
+
+
+def test_prebuild_covers_every_point_of_the_tile_matrix():
+    """Every (point, dtype) the GPU tile matrix forces is built ahead of time: the GPU run compiles nothing."""
+    import tile_matrix_cases as tm
+    from voltrix.jit import cpp_format, generate
+    from voltrix.jit_kernels import prebuild
+
+    built = {code for name, _, code in prebuild.jobs() if name == "spmm_kernel"}
+    dtypes = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}
+    missing = []
+    for key in tm.enumerate_points():
+        point = dict(key)
+        code = generate(spmm_mod.includes, spmm_mod.arg_defs_for(dtypes[tm.kind_of(point)]), cpp_format(spmm_mod.template, point))
+        if code not in built:
+            missing.append(tm.case_id(point, 0))
+    assert not missing, missing
+    assert len(tm.enumerate_points()) >= 400
+
+
+def test_tile_matrix_graphs_are_adversarial():
+    """G1 cuts windows under all three cut schedules (unit table, paired unit table, stream table) in at least four of the
+    eight XCD ranges of equal work, starts with an empty window and ends with a partial one; G2 is short-windowed
+    (2-6 TC blocks per window on average), N % 16 = 1 with the single column N - 1 in its last window, three empty windows."""
+    import tile_matrix_cases as tm
+    from oracle import oracle_c
+    from voltrix import schedule
+
+    indptr, indices, n = tm.graph_cuts()
+    assert n == 16 * 640 + 13
+    p1, packed, hind = oracle_c.csr_preprocess(indptr, indices, n)
+    b = torch.from_numpy(p1)
+    nblk = b[1:] - b[:-1]
+    nw = (n + 15) // 16
+    row_deg = np.diff(indptr)
+    win_edges = np.add.reduceat(row_deg, np.arange(0, n, 16))
+    assert win_edges[0] == 0 and win_edges[-1] == 0 and n % 16 != 0
+    assert (win_edges == 0).sum() >= 8
+    assert np.median(nblk.numpy()) <= 3 and (row_deg >= 2000).sum() >= 8 + 16
+    assert set(indices.tolist()) == set(range(n))                     # every row of B is gathered
+    assert ((row_deg.reshape(-1)[: 16 * (n // 16)].reshape(-1, 16) >= 2000).all(1)).sum() == 1   # one window of hubs only
+    nst = (nblk.long() + 3) // 4
+    ranges = schedule.split_equal_work(nst).long()
+    max_stages = schedule.default_max_stages(b, n)
+    tables = {
+        "units": schedule.unit_table_torch(b, n, xcd_ptr=ranges.int()),
+        "pairs": schedule.unit_table_torch(b, n, max(8, int(spmm_mod.PAIR_UNIT_FACTOR * max_stages / 1.5)), xcd_ptr=ranges.int()),
+        "stream": schedule.stream_tables_torch(b, torch.from_numpy(packed.view(np.int32)), torch.from_numpy(hind), n),
+    }
+    for name, table in tables.items():
+        assert table.num_cuts > 0, name
+        xcds = set(torch.searchsorted(ranges[1:8].contiguous(), table.cuts[:, 0].long(), right=True).tolist())
+        assert len(xcds) >= 4, (name, xcds)
+        assert int(table.cuts[:, 2].max()) >= 3, name               # several cuts in one window
+
+    indptr, indices, n = tm.graph_short()
+    assert n % 16 == 1 and indptr[-1] - indptr[-2] == 1 and indices[-1] == n - 1
+    p1, _, _ = oracle_c.csr_preprocess(indptr, indices, n)
+    nblk = np.diff(p1)
+    assert 2 <= nblk.mean() <= 6
+    win_edges = np.add.reduceat(np.diff(indptr), np.arange(0, n, 16))
+    assert np.array_equal(np.nonzero(win_edges == 0)[0], [600, 601, 602])   # one run of three, in the middle

@@ -30,21 +30,11 @@ def jobs(feature_widths=(32, 64, 128), modes=("default", "none", "stream")):
     for dtype, eb in ((torch.float16, 2), (torch.bfloat16, 2), (torch.float32, 4)):
         for width in feature_widths:
             points = []
-            saved = os.environ.get("VOLTRIX_TUNE_SPACE")
             for mode in modes:  # the tuned space and the single default tile (VOLTRIX_TUNE_SPACE=none)
-                os.environ["VOLTRIX_TUNE_SPACE"] = mode
-                points += list(spmm.tile_space(width, eb, dtype == torch.bfloat16))
-            if saved is None:
-                os.environ.pop("VOLTRIX_TUNE_SPACE", None)
-            else:
-                os.environ["VOLTRIX_TUNE_SPACE"] = saved
-            if eb == 2:   # weighted SpMM (voltrix/weighted.py): the default tile of every width; other points build on demand
-                os.environ["VOLTRIX_TUNE_SPACE"] = "none"
-                points += list(spmm.tile_space(width, eb, dtype == torch.bfloat16, weighted=True))
-                if saved is None:
-                    os.environ.pop("VOLTRIX_TUNE_SPACE", None)
-                else:
-                    os.environ["VOLTRIX_TUNE_SPACE"] = saved
+                with spmm.tune_space(mode):
+                    points += list(spmm.tile_space(width, eb, dtype == torch.bfloat16))
+                    if eb == 2:   # weighted SpMM (voltrix/weighted.py): the WEIGHTED tiles of every mode's space, the default one included
+                        points += list(spmm.tile_space(width, eb, dtype == torch.bfloat16, weighted=True))
             for point in points:
                 key = (eb, point["BF16"], point["FS"], point["DEPTH"], point["WAVES"], point["SCHED"], point["WEIGHTED"])
                 if key in seen:

@@ -40,6 +40,7 @@ def _build_one(name, arg_defs, code, tuned_keys):
     try:
         return build(name, arg_defs, code), tuned_keys
     except Exception as exc:  # an illegal point of the space must not kill tuning (reference tuner.py:35-39)
+        jit_tuner.stats["build_failures"] += 1   # ... but it must not go unseen either (tests assert zero)
         if _debug():
             print(f"JIT build of {name} {tuned_keys} failed: {exc}")
         return None, tuned_keys
@@ -50,9 +51,11 @@ class JITTuner:
         self.tuned: Dict[Any, Any] = {}
         self.tuned_keys: Dict[Any, Dict] = {}
         # what this process has done so far (tests / bench.py): sweeps run, candidate kernels timed, choices taken from the
-        # persisted exact key / from the persisted graph-statistics bucket
+        # persisted exact key / from the persisted graph-statistics bucket; points that failed to build and candidates whose
+        # validity launch returned nonzero (both dropped from the sweep: every point of the space should build and run)
         self.stats: Dict[str, Any] = {"sweeps": 0, "timed_candidates": 0, "stored_hits": 0, "bucket_hits": 0,
-                                      "sweep_seconds": 0.0, "sweeps_cut_by_budget": 0, "full_size_checks": 0}
+                                      "sweep_seconds": 0.0, "sweeps_cut_by_budget": 0, "full_size_checks": 0,
+                                      "build_failures": 0, "illegal_candidates": 0}
         # signatures whose Runtime came from a persisted choice and has not run yet (no validation launch is made: the first
         # real launch is the validation -- ``forget`` + a sweep if it fails)
         self.unvalidated = set()
@@ -217,6 +220,7 @@ class JITTuner:
                         self.stats["sweeps_cut_by_budget"] += 1
                         break
                     if run_all(runtime) != 0:  # illegal kernel for these arguments (e.g. LDS budget, alignment)
+                        self.stats["illegal_candidates"] += 1
                         if _debug():
                             print(f"Illegal JIT kernel {name} with keys {keys} and tuned keys {tuned_keys}")
                         continue
