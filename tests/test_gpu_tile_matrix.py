@@ -169,6 +169,12 @@ def _binary_point(run, point, flags, kind, first_graph):
         assert pending is not None, "G1 has cut windows: a combine must be pending"
         pending.run()
         _check(out, ref, None, "defer_combine + PendingCombine.run()")
+        feat_n, ref_n, bound_n = ops["normal"]    # replay of the deferred plan: new operand, new output, new partial tiles
+        out = run.nan_out()
+        pending = run("defer", feat_n, out, defer_combine=True)
+        assert pending is not None, "G1 has cut windows: a combine must be pending (replay)"
+        pending.run()
+        _check(out, ref_n, bound_n, "defer_combine + PendingCombine.run() (replay)")
     if point["SCHED"] != spmm_mod.SCHED_STREAM:
         _row_map(run, feat, ref)
 

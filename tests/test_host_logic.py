@@ -107,6 +107,33 @@ def test_remap_columns_addresses_the_padded_gather_buffer():
     assert got == [0, 31, 52, 52 + 15, 104, 104 + 51]
 
 
+def test_launch_plan_keeps_every_table_argument_alive():
+    """A cached launch plan holds the ADDRESSES of its whole argument list: it keeps alive every tensor argument but the
+    operands and partial tiles every call passes anew and ``hspa_packed`` (the plan lives on it) -- also one added later."""
+    per_call = {"input", "output", "out_scale", "values", "partials", "partials_p", "partials_s", "hspa_packed"}
+    defs = spmm_mod.arg_defs_for(torch.float16) + (("new_table", torch.int32),)
+    named = {name: torch.zeros(1, dtype=t) if isinstance(t, torch.dtype) else 0 for name, t in defs}
+    kept = {id(t) for t in spmm_mod.plan_keepalive(named)}
+    want = {name for name, t in defs if isinstance(t, torch.dtype) and name not in per_call}
+    assert {name for name, value in named.items() if id(value) in kept} == want
+    assert want == {"blk_offsets", "hind", "win_order_a", "win_order_b", "win_order_c", "units", "unit_ptr", "cuts", "units_p",
+                    "unit_ptr_p", "cuts_p", "row_map", "s_units", "s_runs", "s_run_ptr", "cuts_s", "new_table"}
+    # the argument tuple is built by name: every name of the list, no other
+    assert spmm_mod._pack(defs, named) == tuple(named[name] for name, _ in defs)
+    with pytest.raises(AssertionError):
+        spmm_mod._pack(defs, {k: v for k, v in named.items() if k != "cuts_p"})
+    with pytest.raises(AssertionError):
+        spmm_mod._pack(defs, dict(named, cuts_q=0))
+    # every table-driven schedule fills launch arguments of the list from attributes its table has
+    from voltrix.schedule import StreamTable, UnitTable
+
+    names = {name for name, _ in spmm_mod.arg_defs_for(torch.float16)}
+    for sched, desc in spmm_mod.TABLE_SCHEDULES.items():
+        table_type = StreamTable if sched == spmm_mod.SCHED_STREAM else UnitTable
+        assert {arg for arg, _ in desc.fields} | {desc.partials} <= names, sched
+        assert {attr for _, attr in desc.fields} <= set(table_type.__dataclass_fields__), sched
+
+
 def test_tile_space_for_two_level_handles_leaves_room_for_the_panel_kernel():
     """Handles of the two-level format run beside the panel kernel: the tuner only sees window tiles whose workgroup fits
     the LDS the panel workgroup (44 KB) leaves on a CU."""

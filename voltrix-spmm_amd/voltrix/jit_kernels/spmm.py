@@ -7,13 +7,17 @@ section 8a quirk 9).
 """
 import contextlib
 import contextvars
+import ctypes
 import os
 import warnings
+from typing import Callable, NamedTuple
 
 import torch
 
 from ..jit.compiler import hash_to_hex
+from ..jit.template import map_ctype
 from ..project import TUNE_SPACE_FLAG
+from ..schedule import balanced_xcd_windows, default_max_stages, stream_tables, unit_table
 from .tuner import jit_tuner
 
 # Per-context override of VOLTRIX_TUNE_SPACE (library-internal callers such as the spectral reorder run their products with
@@ -121,6 +125,13 @@ def _lds_bytes(fs, depth, waves, eb, weighted=False):
     return waves * (depth * 32 * fs * eb + (2 * depth + 1) * (1280 if weighted else 256))
 
 
+def _tile_fits(fs, depth, waves, eb, weighted=False):
+    """Mirrors ``SpmmTile``'s two static_asserts (traits.hpp): ``BLOCK_LDS <= 160 KiB`` and ``VM_PER_STEP * (DEPTH - 1) <= 63``,
+    ``VM_PER_STEP`` = ``META_DMAS`` (1; 2 for a value plane) + the row-gather DMAs of a stage."""
+    return (_lds_bytes(fs, depth, waves, eb, weighted) <= 160 * 1024
+            and ((2 if weighted else 1) + 32 * fs * eb // 1024) * (depth - 1) <= 63)
+
+
 # LDS a window-kernel workgroup may take when a panel-kernel workgroup (two-level format, 44 KB at FS = 128 / DEPTH 3)
 # has to fit on the same CU beside it
 TWO_LEVEL_LDS_BUDGET = 160 * 1024 - 47 * 1024   # panel workgroup: 24 KiB ring + 20 KiB metadata + slack
@@ -145,8 +156,7 @@ def tile_space(embedding_dim: int, elem_bytes: int, bf16: bool = False, max_lds:
     if weighted:
         assert elem_bytes == 2
         points = tuple(p for p in points if p["SCHED"] != SCHED_PAIRS)   # paired units: binary operand only
-        points = tuple(p for p in points if _lds_bytes(p["FS"], p["DEPTH"], p["WAVES"], 2, True) <= 160 * 1024
-                       and (2 + 32 * p["FS"] * 2 // 1024) * (p["DEPTH"] - 1) <= 63)
+        points = tuple(p for p in points if _tile_fits(p["FS"], p["DEPTH"], p["WAVES"], p["EB"], True))
     if (max_lds is not None and not weighted and tune_space_mode() == "none"
             and len(points) == 1
             and points[0]["EB"] == 2 and (points[0]["FS"] >= 64 or embedding_dim <= points[0]["FS"])):
@@ -193,8 +203,7 @@ def _tile_space(embedding_dim: int, elem_bytes: int):
     for fs in fs_list:
         for d in depths:
             for w in waves:
-                ndma = 32 * fs * elem_bytes // 1024
-                if _lds_bytes(fs, d, w, elem_bytes) <= 160 * 1024 and (1 + ndma) * (d - 1) <= 63:
+                if _tile_fits(fs, d, w, elem_bytes):
                     # natural window order / balance schedule per chunk size / unit table (16-bit operands)
                     scheds = (0,) + tuple(ORDER_CHUNKS) + ((SCHED_UNITS,) if elem_bytes == 2 else ())
                     if elem_bytes == 2 and w == 4 and (fs >= 64 or embedding_dim <= fs):
@@ -316,25 +325,37 @@ def sweep_bench(fn) -> float:
     return sorted(times)[1]
 
 
-def window_order(blk_offsets: torch.Tensor, hspa_packed: torch.Tensor, num_nodes: int, sched: int = 1) -> torch.Tensor:
-    """The handle's "balance" schedule ``sched`` (key of ORDER_CHUNKS), computed once on the GPU and cached on the
-    ``hspa_packed`` tensor object."""
-    cache = getattr(hspa_packed, "_voltrix_window_order", None)
-    key = (blk_offsets.data_ptr(), num_nodes, sched)
-    if isinstance(cache, dict) and key in cache:
-        return cache[key]
-    from .. import capi
-
-    order = torch.empty((num_nodes + 15) // 16, dtype=torch.int32, device=blk_offsets.device)
-    capi.launch_window_order(blk_offsets, num_nodes, order, torch.cuda.current_stream().cuda_stream, ORDER_CHUNKS[sched])
+def _cached_on(obj, attr, key, build):
+    """``build()``, kept as ``(key, value)`` in ``obj.<attr>``: one entry, replaced when ``key`` changes."""
+    cache = getattr(obj, attr, None)
+    if isinstance(cache, tuple) and cache[0] == key:
+        return cache[1]
+    value = build()
     try:
-        if not isinstance(cache, dict):
-            cache = {}
-            hspa_packed._voltrix_window_order = cache
-        cache[key] = order
+        setattr(obj, attr, (key, value))
     except AttributeError:
         pass
-    return order
+    return value
+
+
+def window_order(blk_offsets: torch.Tensor, hspa_packed: torch.Tensor, num_nodes: int, sched: int = 1) -> torch.Tensor:
+    """The handle's "balance" schedule ``sched`` (key of ORDER_CHUNKS), computed once on the GPU and cached on the
+    ``hspa_packed`` tensor object (a dict: every window range and chunk size the handle is asked for)."""
+    cache = getattr(hspa_packed, "_voltrix_window_order", None)
+    if not isinstance(cache, dict):
+        cache = {}
+        try:
+            hspa_packed._voltrix_window_order = cache
+        except AttributeError:
+            pass
+    key = (blk_offsets.data_ptr(), num_nodes, sched)
+    if key not in cache:
+        from .. import capi
+
+        order = torch.empty((num_nodes + 15) // 16, dtype=torch.int32, device=blk_offsets.device)
+        capi.launch_window_order(blk_offsets, num_nodes, order, torch.cuda.current_stream().cuda_stream, ORDER_CHUNKS[sched])
+        cache[key] = order
+    return cache[key]
 
 
 def arg_defs_for(dtype):
@@ -383,46 +404,29 @@ def arg_defs_for(dtype):
     )
 
 
+def _pair_max_stages(blk_offsets: torch.Tensor, num_nodes: int) -> int:
+    """Unit length bound of the paired launch: PAIR_UNIT_FACTOR x the median window length."""
+    return max(8, int(PAIR_UNIT_FACTOR * default_max_stages(blk_offsets, num_nodes) / 1.5))
+
+
 def handle_unit_table(blk_offsets: torch.Tensor, hspa_packed: torch.Tensor, num_nodes: int, pairs: bool = False,
                       xcd_ptr: torch.Tensor = None):
     """The handle's unit table (voltrix.schedule.unit_table; default length bound, or 1.25 x the median for the paired
     launch), built once on the GPU and cached on the ``hspa_packed`` tensor object.  XCD ranges: the caller's ``xcd_ptr``
     (the two-level step: the panel kernel's ranges) or, round 4, ranges of equal STAGES instead of equal window counts
     (``schedule.balanced_xcd_windows``: graphs whose rows are not statistically alike)."""
-    attr = "_voltrix_unit_table_pairs" if pairs else "_voltrix_unit_table"
-    cache = getattr(hspa_packed, attr, None)
-    key = (blk_offsets.data_ptr(), num_nodes, xcd_ptr.data_ptr() if xcd_ptr is not None else 0)
-    if isinstance(cache, tuple) and cache[0] == key:
-        return cache[1]
-    from ..schedule import balanced_xcd_windows, default_max_stages, unit_table
+    def build():
+        ranges = xcd_ptr if xcd_ptr is not None else balanced_xcd_windows(blk_offsets, num_nodes)
+        return unit_table(blk_offsets, num_nodes, _pair_max_stages(blk_offsets, num_nodes) if pairs else None, xcd_ptr=ranges)
 
-    ranges = xcd_ptr if xcd_ptr is not None else balanced_xcd_windows(blk_offsets, num_nodes)
-    if pairs:
-        median_x_1_5 = default_max_stages(blk_offsets, num_nodes)
-        table = unit_table(blk_offsets, num_nodes, max(8, int(PAIR_UNIT_FACTOR * median_x_1_5 / 1.5)), xcd_ptr=ranges)
-    else:
-        table = unit_table(blk_offsets, num_nodes, xcd_ptr=ranges)
-    try:
-        setattr(hspa_packed, attr, (key, table))
-    except AttributeError:
-        pass
-    return table
+    key = (blk_offsets.data_ptr(), num_nodes, xcd_ptr.data_ptr() if xcd_ptr is not None else 0)
+    return _cached_on(hspa_packed, "_voltrix_unit_table_pairs" if pairs else "_voltrix_unit_table", key, build)
 
 
 def handle_stream_table(blk_offsets: torch.Tensor, hspa_packed: torch.Tensor, hind: torch.Tensor, num_nodes: int):
     """The handle's stream table (voltrix.schedule.stream_tables), built once and cached on the ``hspa_packed`` tensor object."""
-    cache = getattr(hspa_packed, "_voltrix_stream_table", None)
-    key = (blk_offsets.data_ptr(), num_nodes)
-    if isinstance(cache, tuple) and cache[0] == key:
-        return cache[1]
-    from ..schedule import stream_tables
-
-    table = stream_tables(blk_offsets, hspa_packed, hind, num_nodes)
-    try:
-        hspa_packed._voltrix_stream_table = (key, table)
-    except AttributeError:
-        pass
-    return table
+    return _cached_on(hspa_packed, "_voltrix_stream_table", (blk_offsets.data_ptr(), num_nodes),
+                      lambda: stream_tables(blk_offsets, hspa_packed, hind, num_nodes))
 
 
 def graph_bucket_keys(blk_offsets: torch.Tensor, num_nodes: int, keys: dict):
@@ -434,11 +438,11 @@ def graph_bucket_keys(blk_offsets: torch.Tensor, num_nodes: int, keys: dict):
     first of them.  One small device reduction + one host sync, only when a sweep would otherwise run; cached on the tensor."""
     import math
 
-    cached = getattr(blk_offsets, "_voltrix_bucket", None)
-    if cached is None or cached[0] != (blk_offsets.data_ptr(), num_nodes):
-        num_windows = (num_nodes + 15) // 16
-        if num_windows == 0:
-            return None
+    num_windows = (num_nodes + 15) // 16
+    if num_windows == 0:
+        return None
+
+    def bucket():
         nblk = (blk_offsets[1:num_windows + 1] - blk_offsets[:num_windows]).float()
         sample = nblk[:: max(1, num_windows // (1 << 20))]
         q = torch.quantile(sample, torch.tensor([0.25, 0.5, 0.75], device=nblk.device))
@@ -447,15 +451,11 @@ def graph_bucket_keys(blk_offsets: torch.Tensor, num_nodes: int, keys: dict):
         def half_octave(v):
             return int(round(2 * math.log2(max(v, 1.0))))
 
-        bucket = {"log2_rows": int(round(math.log2(max(num_nodes, 1)))),
-                  "log2_mean_blocks_x2": half_octave(stats[3]),
-                  "quartiles_x2": [half_octave(v) for v in stats[:3]],
-                  "cv_x4": int(round(4 * stats[4] / max(stats[3], 1e-9)))}
-        cached = ((blk_offsets.data_ptr(), num_nodes), bucket)
-        try:
-            blk_offsets._voltrix_bucket = cached
-        except AttributeError:
-            pass
+        return {"log2_rows": int(round(math.log2(max(num_nodes, 1)))),
+                "log2_mean_blocks_x2": half_octave(stats[3]),
+                "quartiles_x2": [half_octave(v) for v in stats[:3]],
+                "cv_x4": int(round(4 * stats[4] / max(stats[3], 1e-9)))}
+
     # the ARCHITECTURE, not the marketing name, keys a bucket: the same gfx950 part reports "AMD Instinct MI355X" or "AMD Radeon
     # Graphics" depending on the driver stack, and the shipped defaults must hit on both
     out = {k: v for k, v in keys.items() if k not in ("feature_hash", "device")}
@@ -463,7 +463,7 @@ def graph_bucket_keys(blk_offsets: torch.Tensor, num_nodes: int, keys: dict):
         out["arch"] = torch.cuda.get_device_properties(blk_offsets.device).gcnArchName.split(":")[0]
     except (AttributeError, RuntimeError):
         out["arch"] = keys.get("device", "unknown")
-    out["graph_bucket"] = str(cached[1])
+    out["graph_bucket"] = str(_cached_on(blk_offsets, "_voltrix_bucket", (blk_offsets.data_ptr(), num_nodes), bucket))
     if isinstance(out.get("embedding_dim"), int) and out["embedding_dim"] > 128:
         # wide operands run as 128-column slabs, one launch per slab (spmm_kernels.hpp::slab_launch_group): a width the
         # store has not seen takes the choice of any other wide operand of the bucket (the exact width is asked first)
@@ -508,28 +508,81 @@ def _raw_stream(device) -> int:
         return torch.cuda.current_stream(device).cuda_stream
 
 
+class _TableSchedule(NamedTuple):
+    """A schedule whose launch reads a table of the handle: the launch arguments the table fills, how the table of a window
+    range is built, and what its ``PendingCombine`` gets."""
+    fields: tuple            # (launch argument, table attribute) pairs
+    partials: str            # launch argument of the partial-tile buffer (one [16][F] fp32 tile per slot of a cut window)
+    handle_table: Callable   # (blk_offsets, hspa_packed, hind, num_nodes, xcd_ptr) -> the whole handle's table, cached on it
+    range_table: Callable    # (blk_offsets, hspa_packed, hind, num_nodes, handle's table) -> a window range's own (sweep sample)
+    combine_rows: bool       # combine through atomic_out and row_map (unit tables); False: plain stores, no row map (stream)
+
+    def launch_args(self, table, embedding_dim, device):
+        """The launch arguments of ``table``, with a fresh partial-tile buffer."""
+        out = {arg: getattr(table, attr) for arg, attr in self.fields}
+        out[self.partials] = torch.empty(max(1, table.num_slots) * 16 * embedding_dim, dtype=torch.float32, device=device)
+        return out
+
+
+_UNIT_FIELDS = ("units", "unit_ptr", "max_units_per_xcd", "cuts", "num_cuts")
+TABLE_SCHEDULES = {
+    SCHED_UNITS: _TableSchedule(
+        tuple(zip(_UNIT_FIELDS, _UNIT_FIELDS)), "partials",
+        lambda blk, hspa, hind, n, xcd_ptr: handle_unit_table(blk, hspa, n, xcd_ptr=xcd_ptr),
+        lambda blk, hspa, hind, n, full: unit_table(blk, n), combine_rows=True),
+    SCHED_PAIRS: _TableSchedule(
+        tuple((f + "_p", f) for f in _UNIT_FIELDS), "partials_p",
+        lambda blk, hspa, hind, n, xcd_ptr: handle_unit_table(blk, hspa, n, pairs=True, xcd_ptr=xcd_ptr),
+        lambda blk, hspa, hind, n, full: unit_table(blk, n, _pair_max_stages(blk, n)), combine_rows=True),
+    SCHED_STREAM: _TableSchedule(
+        (("s_units", "units"), ("s_runs", "runs"), ("s_run_ptr", "run_ptr"), ("s_max_runs", "max_runs_per_xcd"), ("cuts_s", "cuts"),
+         ("num_cuts_s", "num_cuts")), "partials_s",
+        lambda blk, hspa, hind, n, xcd_ptr: handle_stream_table(blk, hspa, hind, n),
+        # a sample's own run cost, the whole handle's cut length
+        lambda blk, hspa, hind, n, full: stream_tables(blk, hspa, hind, n, cut_stages=full.cut_stages), combine_rows=False),
+}
+_ORDER_ARGS = {1: "win_order_a", 2: "win_order_b", 3: "win_order_c"}   # key of ORDER_CHUNKS -> launch argument
+
+
+def _pack(arg_defs, named):
+    """The positional arguments of ``launch`` (``arg_defs`` order) from a name -> value mapping that has every name."""
+    names = [name for name, _ in arg_defs]
+    assert named.keys() == set(names), f"missing {set(names) - named.keys()}, unknown {named.keys() - set(names)}"
+    return tuple(named[name] for name in names)
+
+
+_NOT_KEPT = frozenset(("input", "output", "out_scale", "values", "hspa_packed") + tuple(s.partials for s in TABLE_SCHEDULES.values()))
+
+
+def plan_keepalive(named) -> tuple:
+    """The tensors among the launch arguments ``named`` that a cached plan keeps alive (round 6: it holds their ADDRESSES, and a call
+    with another ``xcd_ptr`` / ``blk_offsets`` replaces the one entry of a table cache on ``hspa_packed``): all but the operands
+    every call passes, the partial tiles every call allocates, and ``hspa_packed``, which the plan lives on."""
+    return tuple(value for name, value in named.items() if name not in _NOT_KEPT and isinstance(value, torch.Tensor))
+
+
 class _LaunchPlan:
     """Everything of a ``spmm_kernel`` call that does not change between calls on one handle -- the chosen kernel's entry point,
     its argument list already marshalled to ctypes, which partial-tile buffer the schedule needs, what ``defer_combine`` returns --
     so that a repeated call patches five pointers and launches (round 5: the wrapper cost 57 us of host time per call, more than
     the kernel on the small graphs of the reference's evaluation set: ppi, ddi, FraudYelp).  Kept on the ``hspa_packed`` tensor
     OBJECT (it dies with it; a copy of the tensor starts without plans)."""
-    __slots__ = ("fn", "cargs", "generation", "partials_index", "partials_floats", "combine_table", "combine_args", "device",
-                 "keepalive")
+    __slots__ = ("fn", "cargs", "generation", "operand_index", "partials_index", "partials_floats", "combine_table", "combine_args",
+                 "device", "keepalive")
+    PATCHED = ("input", "output", "out_scale", "values", "stream")   # operand_index: positions of these in ``cargs``
 
     def launch(self, input, output, out_scale, values, defer_combine):
-        import ctypes
-
+        i_input, i_output, i_scale, i_values, i_stream = self.operand_index
         cargs = list(self.cargs)
-        cargs[6] = ctypes.c_void_p(input.data_ptr())
-        cargs[7] = ctypes.c_void_p(output.data_ptr())
-        cargs[11] = ctypes.c_void_p(out_scale.data_ptr())
-        cargs[28] = ctypes.c_void_p((values if values is not None else input).data_ptr())
+        cargs[i_input] = ctypes.c_void_p(input.data_ptr())
+        cargs[i_output] = ctypes.c_void_p(output.data_ptr())
+        cargs[i_scale] = ctypes.c_void_p(out_scale.data_ptr())
+        cargs[i_values] = ctypes.c_void_p((values if values is not None else input).data_ptr())
         partials = None
         if self.partials_index is not None:
             partials = torch.empty(self.partials_floats, dtype=torch.float32, device=input.device)
             cargs[self.partials_index] = ctypes.c_void_p(partials.data_ptr())
-        cargs[38] = ctypes.c_void_p(_raw_stream(self.device))
+        cargs[i_stream] = ctypes.c_void_p(_raw_stream(self.device))
         rc = ctypes.c_int(-1)
         self.fn(*cargs, ctypes.byref(rc))
         assert rc.value == 0, f"spmm_kernel failed with return code {rc.value}"
@@ -614,112 +667,65 @@ def spmm_kernel(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_
     # unit tables / partial-tile buffers: before the choice is made, those of every schedule in the space (the sweep runs
     # them all); afterwards only the chosen schedule's
     chosen = jit_tuner.tuned_point("spmm_kernel", keys).get("SCHED") if jit_tuner.is_tuned("spmm_kernel", keys) else None
-    if chosen is not None:
-        want = lambda sched: chosen == sched                                    # noqa: E731
-    else:
-        want = lambda sched: any(p["SCHED"] == sched for p in space)           # noqa: E731
-    if want(SCHED_UNITS):
-        table = handle_unit_table(blk_offsets, hspa_packed, num_nodes, xcd_ptr=xcd_ptr)
-        partials = torch.empty(max(1, table.num_slots) * 16 * embedding_dim, dtype=torch.float32, device=input.device)
-        units, unit_ptr, cuts = table.units, table.unit_ptr, table.cuts
-        max_units, num_cuts = table.max_units_per_xcd, table.num_cuts
-    else:
-        table, partials = None, out_scale
-        units = unit_ptr = cuts = blk_offsets   # never dereferenced (no SCHED 4 point will run)
-        max_units = num_cuts = 0
-    if want(SCHED_PAIRS):
-        table_p = handle_unit_table(blk_offsets, hspa_packed, num_nodes, pairs=True, xcd_ptr=xcd_ptr)
-        partials_p = torch.empty(max(1, table_p.num_slots) * 16 * embedding_dim, dtype=torch.float32, device=input.device)
-    else:
-        table_p, partials_p = None, out_scale
-    if want(SCHED_STREAM):
-        table_s = handle_stream_table(blk_offsets, hspa_packed, hind, num_nodes)
-        partials_s = torch.empty(max(1, table_s.num_slots) * 16 * embedding_dim, dtype=torch.float32, device=input.device)
-    else:
-        table_s, partials_s = None, out_scale
+    tables = {sched: desc.handle_table(blk_offsets, hspa_packed, hind, num_nodes, xcd_ptr) for sched, desc in TABLE_SCHEDULES.items()
+              if (chosen == sched if chosen is not None else any(p["SCHED"] == sched for p in space))}
     needs_orders = chosen is None or chosen in ORDER_CHUNKS
 
-    def order(sched):
-        return window_order(blk_offsets, hspa_packed, num_nodes, sched) if needs_orders else blk_offsets
+    def orders(blk, n):
+        return {arg: window_order(blk, hspa_packed, n, sched) if needs_orders else blk for sched, arg in _ORDER_ARGS.items()}
 
-    def make_args(out, combine_now):
-        return (blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_dim, input, out,
-                order(1), order(2), order(3), out_scale, int(bool(atomic_out)), units, unit_ptr,
-                max_units, cuts, num_cuts, partials,
-                table_p.units if table_p is not None else blk_offsets, table_p.unit_ptr if table_p is not None else blk_offsets,
-                table_p.max_units_per_xcd if table_p is not None else 0, table_p.cuts if table_p is not None else blk_offsets,
-                table_p.num_cuts if table_p is not None else 0, partials_p, int(combine_now),
-                row_map if row_map is not None else blk_offsets, int(row_map is not None),
-                values if values is not None else input, int(input.shape[0]), int(SLAB_POLICY),
-                table_s.units if table_s is not None else blk_offsets, table_s.runs if table_s is not None else blk_offsets,
-                table_s.run_ptr if table_s is not None else blk_offsets, table_s.max_runs_per_xcd if table_s is not None else 0,
-                table_s.cuts if table_s is not None else blk_offsets, table_s.num_cuts if table_s is not None else 0,
-                partials_s, torch.cuda.current_stream())
-
-    args = make_args(output, not defer_combine)
+    arg_defs = arg_defs_for(input.dtype)
+    named = dict(blk_offsets=blk_offsets, hspa_packed=hspa_packed, hind=hind, num_nodes=num_nodes, num_edges=num_edges,
+                 embedding_dim=embedding_dim, input=input, output=output, **orders(blk_offsets, num_nodes), out_scale=out_scale,
+                 atomic_out=int(bool(atomic_out)), combine_now=int(not defer_combine),
+                 row_map=row_map if row_map is not None else blk_offsets, has_row_map=int(row_map is not None),
+                 values=values if values is not None else input, input_rows=int(input.shape[0]), slab_policy=int(SLAB_POLICY),
+                 stream=torch.cuda.current_stream())
+    types = dict(arg_defs)
+    for sched, desc in TABLE_SCHEDULES.items():
+        if sched in tables:
+            named.update(desc.launch_args(tables[sched], embedding_dim, input.device))
+        else:   # never dereferenced: no point of this schedule will run
+            named.update({arg: 0 if types[arg] is int else blk_offsets for arg, _ in desc.fields}, **{desc.partials: out_scale})
+    args = _pack(arg_defs, named)
     # tuning runs: every candidate is timed with its COMPLETE work (the unit-table schedules with their combine pass, also
     # when the caller defers it), and a launch that adds onto its output gets a scratch one
-    tune_args = args
+    tune_named = named
     if len(space) > 1 and chosen is None and (atomic_out or defer_combine):
-        tune_args = make_args(torch.zeros_like(output) if atomic_out else output, True)
+        tune_named = dict(named, output=torch.zeros_like(output) if atomic_out else output, combine_now=1)
+    tune_args = _pack(arg_defs, tune_named)
 
     def sample_args():
         """(argument tuples of the sample launches, fraction of the handle they cover): called by the tuner only when a
         sweep really runs.  Every range gets its own schedule arrays (window orders, unit tables, partial tiles)."""
-        from ..schedule import default_max_stages, stream_tables, unit_table
-
         num_windows = (num_nodes + 15) // 16
         ranges = sample_ranges(num_windows, int(blk_offsets[num_windows]))
         if len(ranges) == 1 and ranges[0] == (0, num_windows):
             return [tune_args], 1.0
-        out_full = tune_args[7]
+        out_full = tune_named["output"]
         launches, covered = [], 0
         for w0, w1 in ranges:
             sub = blk_offsets[w0:w1 + 1]
             n_sub = min(num_nodes, 16 * w1) - 16 * w0
             covered += w1 - w0
-            a = list(tune_args)
-            a[0], a[3] = sub, n_sub
-            a[7] = out_full if row_map is not None else out_full[16 * w0:16 * w0 + n_sub]
-            for slot, sched in ((8, 1), (9, 2), (10, 3)):
-                a[slot] = window_order(sub, hspa_packed, n_sub, sched) if needs_orders else sub
-            if want(SCHED_UNITS):
-                t = unit_table(sub, n_sub)
-                a[13], a[14], a[15], a[16], a[17] = t.units, t.unit_ptr, t.max_units_per_xcd, t.cuts, t.num_cuts
-                a[18] = torch.empty(max(1, t.num_slots) * 16 * embedding_dim, dtype=torch.float32, device=input.device)
-            if want(SCHED_PAIRS):
-                t = unit_table(sub, n_sub, max(8, int(PAIR_UNIT_FACTOR * default_max_stages(sub, n_sub) / 1.5)))
-                a[19], a[20], a[21], a[22], a[23] = t.units, t.unit_ptr, t.max_units_per_xcd, t.cuts, t.num_cuts
-                a[24] = torch.empty(max(1, t.num_slots) * 16 * embedding_dim, dtype=torch.float32, device=input.device)
-            if want(SCHED_STREAM):
-                t = stream_tables(sub, hspa_packed, hind, n_sub, cut_stages=table_s.cut_stages)   # run cost: the sample's own
-                a[31], a[32], a[33], a[34], a[35], a[36] = t.units, t.runs, t.run_ptr, t.max_runs_per_xcd, t.cuts, t.num_cuts
-                a[37] = torch.empty(max(1, t.num_slots) * 16 * embedding_dim, dtype=torch.float32, device=input.device)
-            a[25] = 1                                       # combine now: the candidate's complete work
+            a = dict(tune_named, blk_offsets=sub, num_nodes=n_sub, **orders(sub, n_sub),
+                     output=out_full if row_map is not None else out_full[16 * w0:16 * w0 + n_sub],
+                     combine_now=1)                  # the candidate's complete work
+            for sched, table in tables.items():
+                desc = TABLE_SCHEDULES[sched]
+                a.update(desc.launch_args(desc.range_table(sub, hspa_packed, hind, n_sub, table), embedding_dim, input.device))
             if row_map is not None:
-                a[26] = row_map[16 * w0:16 * w1]
-            launches.append(tuple(a))
+                a["row_map"] = row_map[16 * w0:16 * w1]
+            launches.append(_pack(arg_defs, a))
         return launches, covered / max(1, num_windows)
 
     staged = tune_space_mode() != "full"    # "full": every point of the (larger) space, still on the sample
 
     def tune(use_store=True):
         return jit_tuner.compile_and_tune(
-            name="spmm_kernel",
-            keys=keys,
-            space=space,
-            includes=includes,
-            arg_defs=arg_defs_for(input.dtype),
-            template=template,
-            args=tune_args,
-            kernel_tag="spmm",
-            bench=sweep_bench,
-            bucket_keys=lambda: graph_bucket_keys(blk_offsets, num_nodes, keys),
-            use_store=use_store,
-            sample_args=sample_args,
-            stages=sweep_stages if staged else None,
-            budget_s=sweep_budget_s,
-        )
+            name="spmm_kernel", keys=keys, space=space, includes=includes, arg_defs=arg_defs, template=template, args=tune_args,
+            kernel_tag="spmm", bench=sweep_bench, bucket_keys=lambda: graph_bucket_keys(blk_offsets, num_nodes, keys),
+            use_store=use_store, sample_args=sample_args, stages=sweep_stages if staged else None, budget_s=sweep_budget_s)
 
     runtime = tune()
     rc = runtime(*args)
@@ -733,45 +739,29 @@ def spmm_kernel(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_
     jit_tuner.unvalidated.discard(signature)
     assert rc == 0, f"spmm_kernel failed with return code {rc}"
     sched = jit_tuner.tuned_point("spmm_kernel", keys).get("SCHED")
-    # ---- the plan for the next call: the marshalled argument list of THIS launch; only the schedule's own partial-tile buffer
-    # ---- (when it has cut windows) is allocated per call
+    table = tables.get(sched)   # the chosen schedule's table, if it has one
+    combine_args = None
+    if defer_combine and table is not None and table.num_cuts > 0:
+        combine_args = (num_nodes, embedding_dim) + ((bool(atomic_out), row_map) if TABLE_SCHEDULES[sched].combine_rows else (False, None))
+    # ---- the plan for the next call: the marshalled argument list of THIS launch, in the order of the names the loaded kernel
+    # ---- reports; only the schedule's own partial-tile buffer (when it has cut windows) is allocated per call
+    fn, kernel_args = runtime.launcher()
+    names = [name for name, _ in kernel_args]
+    plan = _LaunchPlan()
+    plan.fn, plan.generation, plan.device = fn, jit_tuner.generation, input.device
+    plan.cargs = [map_ctype(named[name]) for name in names]
+    plan.operand_index = tuple(names.index(name) for name in _LaunchPlan.PATCHED)
+    plan.keepalive = plan_keepalive(named) + tuple(tables.values()) + ((xcd_ptr,) if xcd_ptr is not None else ())
+    has_partials = table is not None and table.num_slots > 0   # every cut window takes two slots or more
+    plan.partials_index = names.index(TABLE_SCHEDULES[sched].partials) if has_partials else None
+    plan.partials_floats = table.num_slots * 16 * embedding_dim if has_partials else 0
+    plan.combine_table, plan.combine_args = (table, combine_args) if combine_args is not None else (None, None)
     try:
-        import ctypes
-
-        from ..jit.template import map_ctype
-
-        fn, _ = runtime.launcher()
-        plan = _LaunchPlan()
-        plan.fn, plan.generation, plan.device = fn, jit_tuner.generation, input.device
-        plan.cargs = [map_ctype(a) for a in args]
-        # every tensor whose ADDRESS the list holds stays alive with the plan (round 6): the schedule-table caches on
-        # hspa_packed keep one entry each, so a call with another xcd_ptr / blk_offsets replaces a table this plan still points at
-        # -- the handle's own tensors, window orders, the three schedules' tables, row map, XCD ranges; NOT the per-call operands
-        # (input, output, out_scale, values, partial tiles: patched at every launch) and not hspa_packed (the plan lives on it)
-        plan.keepalive = tuple(args[i] for i in (0, 2, 8, 9, 10, 13, 14, 16, 19, 20, 22, 26, 31, 32, 33, 35)
-                               if isinstance(args[i], torch.Tensor)) + tuple(
-            t for t in (table, table_p, table_s, xcd_ptr) if t is not None)
-        plan.partials_index, plan.partials_floats, plan.combine_table, plan.combine_args = None, 0, None, None
-        chosen_table = {SCHED_UNITS: (table, 18), SCHED_PAIRS: (table_p, 24), SCHED_STREAM: (table_s, 37)}.get(sched)
-        if chosen_table is not None and chosen_table[0] is not None and chosen_table[0].num_slots > 0:
-            plan.partials_index = chosen_table[1]
-            plan.partials_floats = max(1, chosen_table[0].num_slots) * 16 * embedding_dim
-            if chosen_table[0].num_cuts > 0 and defer_combine:
-                plan.combine_table = chosen_table[0]
-                plan.combine_args = ((num_nodes, embedding_dim, False, None) if sched == SCHED_STREAM else
-                                     (num_nodes, embedding_dim, bool(atomic_out), row_map))
         if plans is None:
-            plans = {}
-            hspa_packed._voltrix_plans = plans
+            plans = hspa_packed._voltrix_plans = {}
         plans[plan_key] = plan
-        del ctypes
     except AttributeError:
         pass
-    if defer_combine:
-        if sched == SCHED_UNITS and table is not None and table.num_cuts > 0:
-            return PendingCombine(table, partials, output, num_nodes, embedding_dim, bool(atomic_out), row_map)
-        if sched == SCHED_PAIRS and table_p is not None and table_p.num_cuts > 0:
-            return PendingCombine(table_p, partials_p, output, num_nodes, embedding_dim, bool(atomic_out), row_map)
-        if sched == SCHED_STREAM and table_s is not None and table_s.num_cuts > 0:
-            return PendingCombine(table_s, partials_s, output, num_nodes, embedding_dim, False, None)
+    if combine_args is not None:
+        return PendingCombine(table, named[TABLE_SCHEDULES[sched].partials], output, *combine_args)
     return None
