@@ -442,6 +442,18 @@ void voltrix_launch_spmm_csr_rows_weighted(void* indptr, void* indices, void* va
  * of rebuilding the plane (sorts and searches over all edges).  No reference counterpart. */
 void voltrix_launch_scatter_values(void* values, void* slots, void* plane, int64_t count, int dtype, void* stream, int* return_code);
 
+/* Sampled dense-dense product (sddmm_kernels.hpp): out[e] = sum_k x[row_e, k] * y[indices[e], k] for every entry e < nnz of a DEVICE CSR
+ * (int32 indptr[num_rows + 1], indices[nnz]), row_e = the row whose indptr range holds e; out = device float[nnz] in CSR order, every
+ * element written (duplicate entries each get the same value).  x [num_rows, embedding_dim] and y [*, embedding_dim] row-major, 16-byte
+ * aligned; dtype pairs (x_dtype, y_dtype), codes 0 fp32 / 1 fp16 / 2 bfloat16: (0, 1), (0, 2), (1, 1), (2, 2), (0, 0); embedding_dim a
+ * multiple of 8 when either is 16-bit, else of 4.  fp32 products and sum, one fused multiply-add per element, in an order fixed by
+ * embedding_dim alone: |out - ref| <= embedding_dim * 2^-23 (|x| |y|)[e], the same bits on every launch.  The gradient of a weighted
+ * SpMM with respect to its edge values (dv = sddmm(dC, B)) and attention scores.  VOLTRIX_ERR_BAD_SHAPE: negative sizes, a bad width, an
+ * unsupported pair, a null or misaligned pointer; VOLTRIX_OK without a launch for nnz == 0 or embedding_dim == 0.  No reference
+ * counterpart (the reference is forward-only and has no edge values). */
+void voltrix_launch_sddmm_csr(void* indptr, void* indices, int num_rows, int64_t nnz, int embedding_dim, void* x, int x_dtype, void* y,
+                              int y_dtype, void* out, void* stream, int* return_code);
+
 /* Rows of a dense row-major matrix times a per-row factor: dst[i, :] = T(float(src[i, :]) * scale[i]); dst may be src.
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,

@@ -12,6 +12,16 @@ gradient; the same kernels run it on a second handle built from the transposed C
 The forward keeps ``voltrix.spmm``'s numerics (fp16 / bf16 operand or scaled-fp16 rounding of an fp32 operand, fp32
 accumulate); the backward treats the incoming gradient the same way, i.e. the pair is the exact adjoint up to the
 operand rounding the forward applies too.
+
+Edge values that are learnt (attention coefficients, edge gates) get a gradient too.  What flows where:
+
+    op = voltrix.autograd.SpMM(indptr, indices, num_nodes, values=v0)   # built with values
+    out = op(feat, values=v)              # csr(v) @ feat; feat.grad = csr(v)^T @ dC, v.grad[e] = <dC[row_e], feat[col_e]>
+    s = voltrix.autograd.SDDMM(indptr, indices, num_nodes)(q, k)     # s[e] = <q[row_e], k[col_e]>
+                                          # q.grad = csr(ds) @ k, k.grad = csr(ds)^T @ q
+
+``v.grad`` and both SDDMM forwards are the sampled dense-dense product (``voltrix.sddmm``: fp32 products and sum, within
+``F 2^-23 (|x| |y|)[e]``); the SDDMM's backward is the CSR row-gather kernel with values on the CSR and on its transpose.
 """
 from __future__ import annotations
 
@@ -51,6 +61,81 @@ class _SpMMFunction(torch.autograd.Function):
             return spmm_weighted(op.weighted_t, grad_out.contiguous()).to(ctx.in_dtype), None
         grad = spmm(*op.handle_t, num_nodes=op.num_cols, num_edges=op.num_edges, feat=grad_out.contiguous())
         return grad.to(ctx.in_dtype), None
+
+
+class _SpMMValuesFunction(torch.autograd.Function):
+    """``csr(values) @ feat`` with gradients for ``feat`` and ``values``; ``op`` holds the pattern and the installed values."""
+
+    @staticmethod
+    def forward(ctx, feat, values, op):
+        from .weighted import spmm_weighted
+
+        op._install(values.detach())
+        ctx.op, ctx.install = op, op._installs
+        ctx.save_for_backward(feat, values)
+        return spmm_weighted(op.weighted, feat)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .sddmm import sddmm
+        from .weighted import spmm_weighted
+
+        op = ctx.op
+        feat, values = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        grad_feat = grad_values = None
+        if ctx.needs_input_grad[0]:
+            if op._installs != ctx.install:         # a later forward installed other values: put this forward's back
+                op._install(values.detach())
+            grad_feat = spmm_weighted(op.weighted_t, grad_out).to(feat.dtype)
+        if ctx.needs_input_grad[1]:
+            grad_values = sddmm(op.weighted.csr[0], op.weighted.csr[1], grad_out, feat).to(values.dtype)
+        return grad_feat, grad_values, None
+
+
+class _SDDMMFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, op):
+        from .sddmm import sddmm
+
+        ctx.op = op
+        ctx.save_for_backward(x, y)
+        return sddmm(op.indptr, op.indices, x, y)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .sddmm import csr_values_product
+
+        op = ctx.op
+        x, y = ctx.saved_tensors
+        g = grad_out.float().contiguous()
+        grad_x = grad_y = None
+        if ctx.needs_input_grad[0]:           # csr(g) @ y
+            grad_x = csr_values_product(op.indptr, op.indices, g, op.num_rows, y).to(x.dtype)
+        if ctx.needs_input_grad[1]:           # csr(g)^T @ x: the transposed CSR, g in its edge order
+            grad_y = csr_values_product(op.t_indptr, op.t_indices, g[op.t_order], op.num_cols, x).to(y.dtype)
+        return grad_x, grad_y, None
+
+
+class SDDMM:
+    """``s[e] = <x[row_e], y[col_e]>`` for every entry of a CSR pattern [num_rows, num_cols] (``num_cols`` defaults to ``num_rows``),
+    differentiable in both operands: attention scores ``SDDMM(...)(q, k)``.  Built once per pattern: the device CSR, its transpose
+    (``csr_transpose_device``) and the transposed edge order (``weighted.transpose_order``).  Gradients come back in the operands'
+    dtypes."""
+
+    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, num_rows: int, num_cols: int = None):
+        from .weighted import transpose_order
+
+        assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+        self.num_rows = num_rows
+        self.num_cols = num_rows if num_cols is None else int(num_cols)
+        self.indptr, self.indices = indptr.contiguous().cuda(), indices.contiguous().cuda()
+        self.t_indptr, self.t_indices = csr_transpose_device(self.indptr, self.indices, num_rows, self.num_cols)
+        self.t_order = transpose_order(self.indptr, self.indices, num_rows)
+
+    def __call__(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        assert x.shape[0] == self.num_rows and y.shape[0] == self.num_cols and x.shape[1] == y.shape[1]
+        return _SDDMMFunction.apply(x, y, self)
 
 
 class SpMM:
@@ -97,9 +182,9 @@ class SpMM:
 
     def update_values(self, values: torch.Tensor) -> None:
         """New edge values on the same pattern (CSR order of the constructor's ``indices``): both directions, in place
-        (``weighted.update_values``: one scatter per plane, no rebuild).  No gradient flows to ``values`` -- that is a sampled
-        dense-dense product, not on this path."""
-        from .weighted import csr_preprocess_weighted, transpose_order, transpose_weighted, update_values
+        (``weighted.update_values``: one scatter per plane, no rebuild).  No gradient flows to values installed here; pass them per
+        call instead (``op(feat, values=v)``), which gives ``v`` its gradient through the sampled dense-dense product."""
+        from .weighted import transpose_order, update_values
 
         assert self.weighted is not None, "this operator was built without values"
         values_d = values.contiguous().cuda()
@@ -109,18 +194,45 @@ class SpMM:
         if self.weighted.separable:                    # A^T has the factors swapped
             self.weighted_t.row_scale, self.weighted_t.col_scale = self.weighted.col_scale, self.weighted.row_scale
         elif was_separable:                            # the new values do not factor: A^T needs a value plane of its own now
-            t_indptr, t_indices, t_values = transpose_weighted(indptr_d, indices_d, values_d, self.num_rows, self.num_cols)
-            tag = getattr(self.handle_t[1], "hash_tag", None)
-            self.weighted_t = csr_preprocess_weighted(t_indptr, t_indices, t_values, self.num_cols, num_cols=self.num_rows,
-                                                      separable=False)
-            self.handle_t = (self.weighted_t.blk_offsets, self.weighted_t.hspa_packed, self.weighted_t.hind)
-            if tag is not None:
-                self.handle_t[1].hash_tag = tag
+            self._general_transposed(values_d)
         else:
             if getattr(self, "_t_order", None) is None:
                 self._t_order = transpose_order(indptr_d, indices_d, self.num_rows)
             update_values(self.weighted_t, values_d[self._t_order])
 
-    def __call__(self, feat: torch.Tensor) -> torch.Tensor:
+    def _general_transposed(self, values_d: torch.Tensor) -> None:
+        """``A^T`` with a value plane of its own, built from ``values`` (CSR order of ``A``)."""
+        from .weighted import csr_preprocess_weighted, transpose_weighted
+
+        indptr_d, indices_d = self.weighted.csr[0], self.weighted.csr[1]
+        t_indptr, t_indices, t_values = transpose_weighted(indptr_d, indices_d, values_d, self.num_rows, self.num_cols)
+        tag = getattr(self.handle_t[1], "hash_tag", None)
+        self.weighted_t = csr_preprocess_weighted(t_indptr, t_indices, t_values, self.num_cols, num_cols=self.num_rows,
+                                                  separable=False)
+        self.handle_t = (self.weighted_t.blk_offsets, self.weighted_t.hspa_packed, self.weighted_t.hind)
+        if tag is not None:
+            self.handle_t[1].hash_tag = tag
+
+    def _install(self, values: torch.Tensor) -> None:
+        """Values of one forward, in both directions.  The first install on a separable operator makes both directions general, once
+        (as ``update_values`` does for values that do not factor), so that later installs are scatters without the separable check."""
+        from .weighted import make_general
+
+        if self.weighted.separable:
+            values_d = values.contiguous().cuda()
+            make_general(self.weighted, values_d)
+            self._general_transposed(values_d)
+        else:
+            self.update_values(values)
+        self._installs = getattr(self, "_installs", 0) + 1
+
+    def __call__(self, feat: torch.Tensor, values: torch.Tensor = None) -> torch.Tensor:
+        """``A @ feat``; with ``values`` ([nnz], CSR order of the constructor's ``indices``; the operator must have been built with
+        values) ``csr(values) @ feat``, differentiable in ``feat`` and ``values``.  Each call installs its values in both directions;
+        a backward whose forward's values were replaced since installs them again."""
         assert feat.shape[0] == self.num_cols
-        return _SpMMFunction.apply(feat, self)
+        if values is None:
+            return _SpMMFunction.apply(feat, self)
+        assert self.weighted is not None, "this operator was built without values"
+        assert values.numel() == self.num_edges, (values.numel(), self.num_edges)
+        return _SpMMValuesFunction.apply(feat, values, self)

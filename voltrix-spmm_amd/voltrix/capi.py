@@ -71,6 +71,7 @@ SYMBOLS = (
     "voltrix_launch_spmm_csr_rows",
     "voltrix_launch_spmm_csr_rows_weighted",
     "voltrix_launch_scatter_values",
+    "voltrix_launch_sddmm_csr",
     "voltrix_csr_preprocess_workspace_bytes",
     "voltrix_launch_csr_window_count",
     "voltrix_launch_csr_fill",
@@ -593,7 +594,30 @@ def launch_spmm_csr_rows(indptr, indices, num_rows: int, feat, output, stream, x
 
 
 _spmm_csr_rows_weighted = None
+_sddmm_csr = None
 _scatter_values = None
+
+
+def launch_sddmm_csr(indptr, indices, num_rows: int, x, y, out, stream) -> None:
+    """``out[e] = <x[row_e], y[indices[e]]>`` for every entry of a device int32 CSR (the sampled dense-dense product,
+    voltrix/sddmm_kernels.hpp): ``x`` [num_rows, F], ``y`` [*, F], dtype pairs (fp32, fp16 / bf16 / fp32), (fp16, fp16), (bf16, bf16),
+    F a multiple of 16 bytes of ``y``; ``out`` float32 [nnz] in CSR order; see include/voltrix_capi.h."""
+    import torch
+
+    global _sddmm_csr
+    if _sddmm_csr is None:
+        fn = lib().voltrix_launch_sddmm_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        _sddmm_csr = fn
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert x.dim() == 2 and y.dim() == 2 and x.is_contiguous() and y.is_contiguous() and x.shape[0] == num_rows
+    assert x.shape[1] == y.shape[1] and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == indices.numel()
+    codes = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+    rc = ctypes.c_int(-1)
+    _sddmm_csr(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), x.shape[1], x.data_ptr(), codes[x.dtype], y.data_ptr(),
+               codes[y.dtype], out.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_sddmm_csr")
 
 
 def launch_scatter_values(values, slots, plane, stream) -> None:
@@ -666,6 +690,7 @@ launch_cast_f32_f16_scaled = _timed(launch_cast_f32_f16_scaled, "cast_f32_f16_sc
 launch_cast_f32_f16 = _timed(launch_cast_f32_f16, "cast_f32_f16", 2)
 launch_scale_rows = _timed(launch_scale_rows, "scale_rows", 3)
 launch_spmm_csr_rows = _timed(launch_spmm_csr_rows, "spmm_csr_rows", 5)
+launch_sddmm_csr = _timed(launch_sddmm_csr, "sddmm_csr", 6)
 launch_spmm_f32_as_f16 = _timed(launch_spmm_f32_as_f16, "spmm_f32_as_f16", 9)
 launch_window_order = _timed(launch_window_order, "window_order", 3)
 launch_csr_window_count = _timed(launch_csr_window_count, "csr_window_count", 8)

@@ -1,0 +1,76 @@
+"""Sampled dense-dense product (SDDMM): ``out[e] = <x[row_e], y[indices[e]]>`` for every entry of a CSR pattern.
+
+No reference counterpart -- the reference is forward-only and has no edge values.  It is what a model that learns its edge
+values needs: the gradient of ``C = csr(v) @ B`` with respect to the values is ``sddmm(dC, B)``, and dot-product attention scores
+are ``sddmm(Q, K)``.  One HIP kernel (voltrix/sddmm_kernels.hpp) splits the work by edges, so hub rows cost what their edges cost.
+
+    scores = voltrix.sddmm(indptr, indices, q, k)          # float32 [nnz], CSR order
+
+Numerics: fp32 products and sum, one fused multiply-add per element, in an order fixed by the width alone:
+``|out - ref| <= F 2^-23 (|x| |y|)[e]``; the same inputs give the same bits on every call, and duplicate entries the same value.
+"""
+from __future__ import annotations
+
+import torch
+
+_PAIRS = {(torch.float32, torch.float16), (torch.float32, torch.bfloat16), (torch.float16, torch.float16),
+          (torch.bfloat16, torch.bfloat16), (torch.float32, torch.float32)}
+_TYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _padded(t: torch.Tensor, width: int) -> torch.Tensor:
+    """``t`` contiguous, 16-byte aligned, its rows padded with zeros to ``width`` columns."""
+    t = t.contiguous()
+    if width != t.shape[1]:
+        t = torch.nn.functional.pad(t, (0, width - t.shape[1]))
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def sddmm(indptr: torch.Tensor, indices: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """``out[e] = sum_k x[row_e, k] * y[indices[e], k]`` -> float32 [nnz] in CSR order, on the current stream.
+
+    ``indptr`` / ``indices``: device int32 CSR of a [num_rows, num_cols] pattern; ``x`` [num_rows, F], ``y`` [num_cols, F], both CUDA.
+    Pairs (x, y) run as they are: (fp32, fp16), (fp32, bf16), (fp16, fp16), (bf16, bf16), (fp32, fp32); any other pair is cast first
+    (x to fp32, and y too unless it is fp16 / bf16).  Widths that are not a multiple of 16 bytes are padded with zeros."""
+    from . import capi
+    from .jit_kernels.spmm import _raw_stream
+
+    assert indptr.is_cuda and indices.is_cuda and indptr.dtype == torch.int32 and indices.dtype == torch.int32
+    assert x.is_cuda and y.is_cuda and x.dim() == 2 and y.dim() == 2 and x.shape[1] == y.shape[1]
+    num_rows = indptr.numel() - 1
+    assert x.shape[0] == num_rows, (tuple(x.shape), num_rows)
+    if (x.dtype, y.dtype) not in _PAIRS:
+        y = y if y.dtype in _TYPES else y.float()
+        x = x.float()
+    nnz = indices.numel()
+    out = torch.empty(nnz, dtype=torch.float32, device=x.device)
+    num_feats = x.shape[1]
+    if nnz == 0:
+        return out
+    if num_feats == 0:
+        return out.zero_()
+    align = 4 if (x.dtype, y.dtype) == (torch.float32, torch.float32) else 8
+    width = (num_feats + align - 1) // align * align
+    capi.launch_sddmm_csr(indptr.contiguous(), indices.contiguous(), num_rows, _padded(x, width), _padded(y, width), out,
+                          _raw_stream(x.device))
+    return out
+
+
+def csr_values_product(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor, num_rows: int,
+                       feat: torch.Tensor) -> torch.Tensor:
+    """``csr(values) @ feat`` -> float32 [num_rows, F] with the CSR row-gather kernel with values (``spmm_csr_rows_kernel<T, 4,
+    true>``): fp32 / fp16 / bf16 rows as they are (other types as fp32), fp32 values, one fused multiply-add per element."""
+    from . import capi
+    from .jit_kernels.spmm import _raw_stream
+
+    if feat.dtype not in _TYPES:
+        feat = feat.float()
+    num_feats = feat.shape[1]
+    if indices.numel() == 0 or num_feats == 0 or num_rows == 0:
+        return torch.zeros(num_rows, num_feats, dtype=torch.float32, device=feat.device)
+    align = 4 if feat.dtype == torch.float32 else 8
+    width = (num_feats + align - 1) // align * align
+    output = torch.empty((num_rows, width), dtype=torch.float32, device=feat.device)
+    capi.launch_spmm_csr_rows(indptr, indices, num_rows, _padded(feat, width), output, _raw_stream(feat.device), 1,
+                              values=values.float().contiguous())
+    return output if width == num_feats else output[:, :num_feats].contiguous()

@@ -268,16 +268,7 @@ def update_values(handle: WeightedHandle, values: torch.Tensor) -> WeightedHandl
             handle.csr = (indptr, indices, _own_values(values), num_cols)
             handle.planes.clear()                     # lazily built planes of the old values (separable_pays)
             return handle
-        handle.row_scale = handle.col_scale = None    # a general handle from here on: the plane path of spmm_weighted
-        handle.planes.clear()
-        handle.csr = (indptr, indices, _own_values(values), num_cols)
-        total = int(handle.blk_offsets[-1])
-        if total * 512 > MASTER_PLANE_MAX_BYTES:
-            handle.planes[torch.float16] = value_plane(indptr, indices, values, handle.blk_offsets, handle.num_nodes, num_cols,
-                                                       dtype=torch.float16)
-        else:
-            handle.values32 = value_plane(indptr, indices, values, handle.blk_offsets, handle.num_nodes, num_cols)
-        return handle
+        return make_general(handle, values)
     if handle.edge_slot is None:
         handle.edge_slot = edge_slots(indptr, indices, handle.blk_offsets, handle.num_nodes, num_cols)
         handle.slot_duplicates = bool(values.numel()) and int(torch.unique(handle.edge_slot).numel()) != int(values.numel())
@@ -307,6 +298,25 @@ def update_values(handle: WeightedHandle, values: torch.Tensor) -> WeightedHandl
             capi.launch_scatter_values(values32, slot, handle.planes[dt], stream)
     else:
         capi.launch_scatter_values(values32, slot, handle.values32, stream)
+    return handle
+
+
+def make_general(handle: WeightedHandle, values: torch.Tensor) -> WeightedHandle:
+    """A separable handle becomes a general one holding ``values`` (CSR order): value plane built now, no check whether the values
+    factor.  What ``update_values`` does for new values that do not; callers that install values at every step call it once, so
+    that later updates are one scatter each and never run ``separable_scales``.  Returns ``handle``."""
+    assert handle.separable and handle.csr is not None and values.numel() == handle.num_edges
+    indptr, indices, _, num_cols = handle.csr
+    values = values.contiguous().to(indptr.device)
+    handle.row_scale = handle.col_scale = None    # a general handle from here on: the plane path of spmm_weighted
+    handle.planes.clear()
+    handle.csr = (indptr, indices, _own_values(values), num_cols)
+    total = int(handle.blk_offsets[-1])
+    if total * 512 > MASTER_PLANE_MAX_BYTES:
+        handle.planes[torch.float16] = value_plane(indptr, indices, values, handle.blk_offsets, handle.num_nodes, num_cols,
+                                                   dtype=torch.float16)
+    else:
+        handle.values32 = value_plane(indptr, indices, values, handle.blk_offsets, handle.num_nodes, num_cols)
     return handle
 
 
