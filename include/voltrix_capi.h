@@ -454,6 +454,28 @@ void voltrix_launch_scatter_values(void* values, void* slots, void* plane, int64
 void voltrix_launch_sddmm_csr(void* indptr, void* indices, int num_rows, int64_t nnz, int embedding_dim, void* x, int x_dtype, void* y,
                               int y_dtype, void* out, void* stream, int* return_code);
 
+/* Edge softmax (edge_softmax_kernels.hpp): alpha[e] = exp(z_e - m_r) / sum_{e' in row r} exp(z_e' - m_r), z = scale * scores, m_r the
+ * row maximum, for every entry e < nnz of a DEVICE CSR (int32 indptr[num_rows + 1]); scores and out = device float[nnz] in CSR order,
+ * every element written.  The step between attention scores (voltrix_launch_sddmm_csr) and the aggregation with them
+ * (voltrix_launch_spmm_csr_rows_weighted).  Special values: z = -inf gives 0; a row whose entries are all -inf gets zeros, not NaN
+ * (unlike torch.softmax); a NaN makes its own row NaN and no other; scale = 0 gives
+ * 1 / (the row's entries that are not -inf) to each of them.  Accuracy, with deg_r the row's entries and ref the exact softmax:
+ * |alpha - ref| <= ref * 2 (deg_r + |z_e - m_r| + 2) 2^-23 + 2^-126.  Deterministic: no float atomics, sums in an order fixed by
+ * the pattern, the same bits on every launch.  Three kernel launches on `stream`, no host synchronisation; workspace: device, 16-byte
+ * aligned, voltrix_edge_softmax_workspace_bytes(num_rows, nnz) bytes (a function of nnz alone), reused by the backward.
+ * VOLTRIX_ERR_BAD_SHAPE: negative sizes, nnz > INT_MAX, a non-finite scale, a null or misaligned pointer; VOLTRIX_OK without a launch
+ * for nnz == 0.  No reference counterpart (the reference is forward-only and has no edge values). */
+int64_t voltrix_edge_softmax_workspace_bytes(int num_rows, int64_t nnz);
+void voltrix_launch_edge_softmax_csr(void* indptr, int num_rows, int64_t nnz, void* scores, float scale, void* out, void* workspace,
+                                     void* stream, int* return_code);
+
+/* Its backward: grad_scores[e] = scale * alpha[e] * (grad_alpha[e] - sum_{e' in row r} alpha[e'] * grad_alpha[e']), alpha from the
+ * forward, all device float[nnz] in CSR order; rows of zeros (all -inf) get zero gradients.  With D_r = sum alpha g and
+ * A_r = sum alpha |g|: |grad - ref| <= |scale| alpha_e (2 |g_e - D_r| + (deg_r + 2) A_r) 2^-23 + 2^-126.  Same workspace, checks and
+ * determinism as the forward. */
+void voltrix_launch_edge_softmax_backward_csr(void* indptr, int num_rows, int64_t nnz, void* alpha, void* grad_alpha, float scale,
+                                              void* grad_scores, void* workspace, void* stream, int* return_code);
+
 /* Rows of a dense row-major matrix times a per-row factor: dst[i, :] = T(float(src[i, :]) * scale[i]); dst may be src.
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,

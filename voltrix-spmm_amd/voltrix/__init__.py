@@ -16,6 +16,7 @@ from .reorder import ReorderedHandle, csr_preprocess_reordered, permute_features
 from .weighted import WeightedHandle, csr_preprocess_weighted, spmm_weighted
 from .weighted import update_values as update_edge_values
 from .sddmm import sddmm
+from .edge_softmax import edge_softmax
 from .graphed import GraphedSpMM
 from . import autograd, hybrid, jit, sidecar, utils
 

@@ -19,9 +19,13 @@ Edge values that are learnt (attention coefficients, edge gates) get a gradient 
     out = op(feat, values=v)              # csr(v) @ feat; feat.grad = csr(v)^T @ dC, v.grad[e] = <dC[row_e], feat[col_e]>
     s = voltrix.autograd.SDDMM(indptr, indices, num_nodes)(q, k)     # s[e] = <q[row_e], k[col_e]>
                                           # q.grad = csr(ds) @ k, k.grad = csr(ds)^T @ q
+    alpha = voltrix.autograd.EdgeSoftmax(indptr, num_nodes)(s, scale)  # softmax of scale * s over every row
+                                          # s.grad = scale * alpha * (dalpha - rowsum(alpha * dalpha))
 
 ``v.grad`` and both SDDMM forwards are the sampled dense-dense product (``voltrix.sddmm``: fp32 products and sum, within
-``F 2^-23 (|x| |y|)[e]``); the SDDMM's backward is the CSR row-gather kernel with values on the CSR and on its transpose.
+``F 2^-23 (|x| |y|)[e]``); the SDDMM's backward is the CSR row-gather kernel with values on the CSR and on its transpose.  The edge
+softmax's forward and backward are the kernels of ``voltrix.edge_softmax`` (three launches each, deterministic); together the three
+operators make an attention layer: ``SpMM(...)(v, values=EdgeSoftmax(...)(SDDMM(...)(q, k), d ** -0.5))``.
 """
 from __future__ import annotations
 
@@ -136,6 +140,40 @@ class SDDMM:
     def __call__(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         assert x.shape[0] == self.num_rows and y.shape[0] == self.num_cols and x.shape[1] == y.shape[1]
         return _SDDMMFunction.apply(x, y, self)
+
+
+class _EdgeSoftmaxFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, op, scale):
+        from .edge_softmax import edge_softmax
+
+        alpha = edge_softmax(op.indptr, scores, scale)
+        ctx.op, ctx.scale, ctx.in_dtype = op, scale, scores.dtype
+        ctx.save_for_backward(alpha)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, grad_alpha):
+        from .edge_softmax import edge_softmax_backward
+
+        (alpha,) = ctx.saved_tensors
+        grad = edge_softmax_backward(ctx.op.indptr, alpha, grad_alpha, ctx.scale)
+        return grad.to(ctx.in_dtype), None, None
+
+
+class EdgeSoftmax:
+    """``alpha = softmax(scale * scores)`` over every row of a CSR pattern with ``num_rows`` rows (``voltrix.edge_softmax``), differentiable
+    in the scores: the attention weights between ``SDDMM`` and ``SpMM(..., values=)``.  Holds the device ``indptr``; the column ids do not
+    matter.  ``alpha`` is float32; the gradient comes back in the scores' dtype."""
+
+    def __init__(self, indptr: torch.Tensor, num_rows: int):
+        assert indptr.dtype == torch.int32 and indptr.numel() == num_rows + 1
+        self.num_rows = num_rows
+        self.indptr = indptr.contiguous().cuda()
+
+    def __call__(self, scores: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+        assert scores.dim() == 1
+        return _EdgeSoftmaxFunction.apply(scores, self, float(scale))
 
 
 class SpMM:

@@ -72,6 +72,9 @@ SYMBOLS = (
     "voltrix_launch_spmm_csr_rows_weighted",
     "voltrix_launch_scatter_values",
     "voltrix_launch_sddmm_csr",
+    "voltrix_edge_softmax_workspace_bytes",
+    "voltrix_launch_edge_softmax_csr",
+    "voltrix_launch_edge_softmax_backward_csr",
     "voltrix_csr_preprocess_workspace_bytes",
     "voltrix_launch_csr_window_count",
     "voltrix_launch_csr_fill",
@@ -114,6 +117,7 @@ def lib() -> ctypes.CDLL:
         _lib.voltrix_unit_table_fill_workspace_bytes.restype = ctypes.c_int64
         _lib.voltrix_cm_rank_workspace_bytes.restype = ctypes.c_int64
         _lib.voltrix_csr_transpose_workspace_bytes.restype = ctypes.c_int64
+        _lib.voltrix_edge_softmax_workspace_bytes.restype = ctypes.c_int64
         for name in SYMBOLS:
             if name.startswith("voltrix_launch_") or name in ("voltrix_spmm_default_tile", "voltrix_spmm_tile_at"):
                 getattr(_lib, name).restype = None
@@ -620,6 +624,56 @@ def launch_sddmm_csr(indptr, indices, num_rows: int, x, y, out, stream) -> None:
     check(rc.value, "voltrix_launch_sddmm_csr")
 
 
+_edge_softmax = None
+_edge_softmax_backward = None
+
+
+def edge_softmax_workspace_bytes(num_rows: int, nnz: int) -> int:
+    """Bytes of device workspace both edge softmax entry points need (a function of ``nnz`` alone; 0 for nnz == 0)."""
+    return int(lib().voltrix_edge_softmax_workspace_bytes(ctypes.c_int(num_rows), ctypes.c_int64(nnz)))
+
+
+def launch_edge_softmax_csr(indptr, num_rows: int, scores, scale: float, out, workspace, stream) -> None:
+    """``out`` = softmax of ``scale * scores`` over every row of a device int32 CSR (voltrix/edge_softmax_kernels.hpp): ``scores`` and
+    ``out`` float32 [nnz] in CSR order, ``workspace`` uint8 of ``edge_softmax_workspace_bytes`` bytes; see include/voltrix_capi.h."""
+    import torch
+
+    global _edge_softmax
+    if _edge_softmax is None:
+        fn = lib().voltrix_launch_edge_softmax_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        _edge_softmax = fn
+    assert indptr.dtype == torch.int32 and indptr.numel() == num_rows + 1 and indptr.is_contiguous()
+    assert scores.dtype == torch.float32 and out.dtype == torch.float32 and scores.is_contiguous() and out.is_contiguous()
+    assert out.numel() == scores.numel() and workspace.numel() >= edge_softmax_workspace_bytes(num_rows, scores.numel())
+    rc = ctypes.c_int(-1)
+    _edge_softmax(indptr.data_ptr(), num_rows, scores.numel(), scores.data_ptr(), float(scale), out.data_ptr(), workspace.data_ptr(),
+                  stream, rc)
+    check(rc.value, "voltrix_launch_edge_softmax_csr")
+
+
+def launch_edge_softmax_backward_csr(indptr, num_rows: int, alpha, grad_alpha, scale: float, grad_scores, workspace, stream) -> None:
+    """``grad_scores = scale * alpha * (grad_alpha - rowsum(alpha * grad_alpha))`` (the edge softmax's backward), all float32 [nnz] in
+    CSR order; the forward's workspace size; see include/voltrix_capi.h."""
+    import torch
+
+    global _edge_softmax_backward
+    if _edge_softmax_backward is None:
+        fn = lib().voltrix_launch_edge_softmax_backward_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        _edge_softmax_backward = fn
+    assert indptr.dtype == torch.int32 and indptr.numel() == num_rows + 1 and indptr.is_contiguous()
+    for t in (alpha, grad_alpha, grad_scores):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == alpha.numel()
+    assert workspace.numel() >= edge_softmax_workspace_bytes(num_rows, alpha.numel())
+    rc = ctypes.c_int(-1)
+    _edge_softmax_backward(indptr.data_ptr(), num_rows, alpha.numel(), alpha.data_ptr(), grad_alpha.data_ptr(), float(scale),
+                           grad_scores.data_ptr(), workspace.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_edge_softmax_backward_csr")
+
+
 def launch_scatter_values(values, slots, plane, stream) -> None:
     """``plane.view(-1)[slots[e]] = values[e]`` (device float32 values, int64 slots, fp32 / fp16 / bf16 plane); see
     include/voltrix_capi.h."""
@@ -691,6 +745,8 @@ launch_cast_f32_f16 = _timed(launch_cast_f32_f16, "cast_f32_f16", 2)
 launch_scale_rows = _timed(launch_scale_rows, "scale_rows", 3)
 launch_spmm_csr_rows = _timed(launch_spmm_csr_rows, "spmm_csr_rows", 5)
 launch_sddmm_csr = _timed(launch_sddmm_csr, "sddmm_csr", 6)
+launch_edge_softmax_csr = _timed(launch_edge_softmax_csr, "edge_softmax_csr", 6)
+launch_edge_softmax_backward_csr = _timed(launch_edge_softmax_backward_csr, "edge_softmax_backward_csr", 7)
 launch_spmm_f32_as_f16 = _timed(launch_spmm_f32_as_f16, "spmm_f32_as_f16", 9)
 launch_window_order = _timed(launch_window_order, "window_order", 3)
 launch_csr_window_count = _timed(launch_csr_window_count, "csr_window_count", 8)
