@@ -1,5 +1,5 @@
-"""A two-layer single-head GAT trained with the operators of this package (example; no reference counterpart -- the reference is
-forward-only and has no edge values).
+"""A two-layer GAT (single-head by default, multi-head with the fourth argument) trained with the operators of this package (example;
+no reference counterpart -- the reference is forward-only and has no edge values).
 
     Wh = X W,   s_ij = LeakyReLU(a_l . Wh_i + a_r . Wh_j),   alpha = edge softmax of s over every row,   H_i = sum_j alpha_ij Wh_j
 
@@ -8,7 +8,11 @@ column ids; the softmax over every row is ``voltrix.autograd.EdgeSoftmax`` (dete
 aggregation is ``voltrix.autograd.SpMM(..., values=alpha)`` on fp16 ``Wh``, which returns ``alpha``'s gradient through the sampled
 dense-dense product.  Self loops are added so that every node attends to itself.
 
-    python examples/gat_train.py [workload] [hidden] [epochs]      # synthetic stand-in graph, random features and labels
+With ``heads`` > 1 the hidden layer is H heads of ``hidden / H`` features, concatenated, and the output layer averages its H heads, as in
+the paper; the scalars become [n, H], the softmax runs on [nnz, H] and the aggregation is ``voltrix.autograd.SpMMHeads`` (one launch
+for all heads, no value planes).  ``heads`` = 1 is the single-head run, unchanged.
+
+    python examples/gat_train.py [workload] [hidden] [epochs] [heads]      # synthetic stand-in graph, random features and labels
 """
 import os
 import sys
@@ -34,16 +38,19 @@ def with_self_loops(indptr, indices, n):
 
 class Graph:
     """What both layers share: the row ids and column ids of every edge (int64, for the gathers), the edge softmax and the aggregation
-    operator (built once: A and A^T)."""
+    operator (built once: A and A^T).  ``heads`` > 1: the multi-head aggregation (the device CSR and its transpose; no handle)."""
 
-    def __init__(self, indptr, indices, n, hash_tag="example_gat"):
-        from voltrix.autograd import EdgeSoftmax, SpMM
+    def __init__(self, indptr, indices, n, hash_tag="example_gat", heads=1):
+        from voltrix.autograd import EdgeSoftmax, SpMM, SpMMHeads
 
-        self.n = n
+        self.n, self.heads = n, heads
         self.rows = torch.repeat_interleave(torch.arange(n, device="cuda"), (indptr[1:] - indptr[:-1]).long())
         self.cols = indices.long().cuda()
         self.softmax = EdgeSoftmax(indptr, n)
-        self.aggregate = SpMM(indptr, indices, n, values=torch.ones(indices.numel(), device="cuda"), hash_tag=hash_tag)
+        if heads > 1:
+            self.aggregate = SpMMHeads(indptr, indices, n)
+        else:
+            self.aggregate = SpMM(indptr, indices, n, values=torch.ones(indices.numel(), device="cuda"), hash_tag=hash_tag)
 
 
 class GATLayer(torch.nn.Module):
@@ -62,9 +69,32 @@ class GATLayer(torch.nn.Module):
         return g.aggregate(wh.half(), values=alpha)
 
 
+class GATHeadsLayer(torch.nn.Module):
+    """``graph.heads`` heads of ``out_feats`` features each: concatenated ([n, H * out_feats]) or averaged ([n, out_feats])."""
+
+    def __init__(self, graph, in_feats, out_feats, concat, slope=0.2):
+        super().__init__()
+        self.graph, self.slope, self.concat, self.out_feats = graph, slope, concat, out_feats
+        self.w = torch.nn.Linear(in_feats, graph.heads * out_feats, bias=False)
+        self.a_l = torch.nn.Parameter(torch.randn(graph.heads, out_feats) / out_feats ** 0.5)
+        self.a_r = torch.nn.Parameter(torch.randn(graph.heads, out_feats) / out_feats ** 0.5)
+
+    def forward(self, x):
+        g = self.graph
+        wh = self.w(x).view(g.n, g.heads, self.out_feats)
+        s = torch.nn.functional.leaky_relu((wh * self.a_l).sum(-1)[g.rows] + (wh * self.a_r).sum(-1)[g.cols], self.slope)
+        out = g.aggregate(wh.half(), g.softmax(s))            # scores, weights [nnz, H]; out [n, H, out_feats]
+        return out.flatten(1) if self.concat else out.mean(1)
+
+
 class GAT(torch.nn.Module):
     def __init__(self, graph, in_feats, hidden, classes):
         super().__init__()
+        if graph.heads > 1:
+            assert hidden % graph.heads == 0, (hidden, graph.heads)
+            self.l1 = GATHeadsLayer(graph, in_feats, hidden // graph.heads, concat=True)
+            self.l2 = GATHeadsLayer(graph, hidden, classes, concat=False)
+            return
         self.l1 = GATLayer(graph, in_feats, hidden)
         self.l2 = GATLayer(graph, hidden, classes)
 
@@ -78,11 +108,12 @@ def main():
     workload = sys.argv[1] if len(sys.argv) > 1 else "reddit_like"
     hidden = int(sys.argv[2]) if len(sys.argv) > 2 else 64
     epochs = int(sys.argv[3]) if len(sys.argv) > 3 else 10
+    heads = int(sys.argv[4]) if len(sys.argv) > 4 else 1
     indptr, indices, _ = synth_graphs.generate(workload, device="cuda")
     n = indptr.numel() - 1
     indptr, indices = with_self_loops(indptr, indices, n)
     t0 = time.perf_counter()
-    graph = Graph(indptr, indices, n, hash_tag=f"example_gat/{workload}")
+    graph = Graph(indptr, indices, n, hash_tag=f"example_gat/{workload}", heads=heads)
     torch.cuda.synchronize()
     print(f"{workload}: N={n} nnz={indices.numel()} (self loops added); operators built in {time.perf_counter() - t0:.2f} s")
     torch.manual_seed(0)
@@ -104,7 +135,8 @@ def main():
         if epoch in (0, 1, epochs - 1):
             print(f"epoch {epoch}: loss {float(loss):.4f}, {times[-1]:.2f} ms")
     steady = sorted(times[2:])[len(times[2:]) // 2] if len(times) > 2 else times[-1]
-    print(f"steady epoch (forward + backward + Adam, full graph): {steady:.2f} ms -- two attention layers, hidden {hidden}")
+    print(f"steady epoch (forward + backward + Adam, full graph): {steady:.2f} ms -- two attention layers, hidden {hidden}"
+          + (f", {heads} heads" if heads > 1 else ""))
 
 
 if __name__ == "__main__":

@@ -476,6 +476,36 @@ void voltrix_launch_edge_softmax_csr(void* indptr, int num_rows, int64_t nnz, vo
 void voltrix_launch_edge_softmax_backward_csr(void* indptr, int num_rows, int64_t nnz, void* alpha, void* grad_alpha, float scale,
                                               void* grad_scores, void* workspace, void* stream, int* return_code);
 
+/* Multi-head forms of the three attention operators (sddmm_heads_kernels.hpp, edge_softmax_heads_kernels.hpp,
+ * spmm_csr_heads_kernels.hpp).  Layouts: node tensors [n, heads, head_dim] row-major (rows of heads * head_dim, 16-byte aligned), edge
+ * tensors device float[nnz, heads] in CSR order with the head index fastest.  Per head each computes what its single-head entry point
+ * computes on the head's contiguous slice, to the bit, within the same bounds (head_dim in place of embedding_dim); one index read and
+ * one gathered row per edge serve all heads.  Element offsets are 64-bit; nnz <= INT_MAX, heads * head_dim <= INT_MAX.
+ * VOLTRIX_ERR_BAD_SHAPE from each, on the host and before any launch: heads < 1, negative sizes, head_dim not a multiple of 16 bytes of
+ * the gathered operand (8 for 16-bit, 4 for fp32), a dtype or pair outside the single-head set, a null or misaligned pointer;
+ * VOLTRIX_OK without a launch when there is nothing to do.  No reference counterpart.
+ *
+ * out[e, h] = sum_d x[row_e, h, d] * y[indices[e], h, d]; dtype pairs of voltrix_launch_sddmm_csr. */
+void voltrix_launch_sddmm_heads_csr(void* indptr, void* indices, int num_rows, int64_t nnz, int heads, int head_dim, void* x, int x_dtype,
+                                    void* y, int y_dtype, void* out, void* stream, int* return_code);
+
+/* out[:, h] = edge softmax of scale * scores[:, h] for every head, special values per head (a NaN or a row of -inf stays in its own
+ * row and its own head); three launches, deterministic, no host synchronisation.  Workspace: device, 16-byte aligned,
+ * voltrix_edge_softmax_heads_workspace_bytes(num_rows, nnz, heads) bytes -- a function of (nnz, heads) alone; heads == 1: the single-head
+ * size -- shared with the backward: grad_scores = scale * alpha * (grad_alpha - rowsum(alpha * grad_alpha)) per head. */
+int64_t voltrix_edge_softmax_heads_workspace_bytes(int num_rows, int64_t nnz, int heads);
+void voltrix_launch_edge_softmax_heads_csr(void* indptr, int num_rows, int64_t nnz, int heads, void* scores, float scale, void* out,
+                                           void* workspace, void* stream, int* return_code);
+void voltrix_launch_edge_softmax_heads_backward_csr(void* indptr, int num_rows, int64_t nnz, int heads, void* alpha, void* grad_alpha,
+                                                    float scale, void* grad_scores, void* workspace, void* stream, int* return_code);
+
+/* output[r, h, :] = sum_{e in row r} values[e, h] * input[indices[e], h, :]: fp32 / fp16 / bf16 input (dtype 0 / 1 / 2), fp32 values
+ * [nnz, heads] and output [num_rows, heads, head_dim]; fp32 products, one fused multiply-add per element, summed in CSR order; every
+ * row written, empty rows zero.  No value planes and no block-format handle.  VOLTRIX_OK without a launch for num_rows == 0 or
+ * head_dim == 0. */
+void voltrix_launch_spmm_csr_heads(void* indptr, void* indices, void* values, int num_rows, int heads, int head_dim, void* input,
+                                   int dtype, void* output, void* stream, int* return_code);
+
 /* Rows of a dense row-major matrix times a per-row factor: dst[i, :] = T(float(src[i, :]) * scale[i]); dst may be src.
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,

@@ -26,6 +26,12 @@ Edge values that are learnt (attention coefficients, edge gates) get a gradient 
 ``F 2^-23 (|x| |y|)[e]``); the SDDMM's backward is the CSR row-gather kernel with values on the CSR and on its transpose.  The edge
 softmax's forward and backward are the kernels of ``voltrix.edge_softmax`` (three launches each, deterministic); together the three
 operators make an attention layer: ``SpMM(...)(v, values=EdgeSoftmax(...)(SDDMM(...)(q, k), d ** -0.5))``.
+
+Multi-head: ``SDDMM`` takes ``q, k`` [n, H, D] and gives scores [nnz, H], ``EdgeSoftmax`` takes [nnz, H], and ``SpMMHeads`` aggregates
+``v`` [n, H, D] with weights [nnz, H] -- one launch per operator for all heads, the per-head bits of the single-head kernels:
+
+    alpha = EdgeSoftmax(indptr, n)(SDDMM(indptr, indices, n)(q, k), d ** -0.5)       # [nnz, H]
+    out = voltrix.autograd.SpMMHeads(indptr, indices, n)(v, alpha)                   # float32 [n, H, D]
 """
 from __future__ import annotations
 
@@ -114,6 +120,14 @@ class _SDDMMFunction(torch.autograd.Function):
         x, y = ctx.saved_tensors
         g = grad_out.float().contiguous()
         grad_x = grad_y = None
+        if x.dim() == 3:                      # multi-head: g [nnz, H]; the aggregation kernel on the CSR and on its transpose
+            from .sddmm import spmm_heads
+
+            if ctx.needs_input_grad[0]:
+                grad_x = spmm_heads(op.indptr, op.indices, g, y, op.num_rows).to(x.dtype)
+            if ctx.needs_input_grad[1]:
+                grad_y = spmm_heads(op.t_indptr, op.t_indices, g[op.t_order], x, op.num_cols).to(y.dtype)
+            return grad_x, grad_y, None
         if ctx.needs_input_grad[0]:           # csr(g) @ y
             grad_x = csr_values_product(op.indptr, op.indices, g, op.num_rows, y).to(x.dtype)
         if ctx.needs_input_grad[1]:           # csr(g)^T @ x: the transposed CSR, g in its edge order
@@ -125,7 +139,7 @@ class SDDMM:
     """``s[e] = <x[row_e], y[col_e]>`` for every entry of a CSR pattern [num_rows, num_cols] (``num_cols`` defaults to ``num_rows``),
     differentiable in both operands: attention scores ``SDDMM(...)(q, k)``.  Built once per pattern: the device CSR, its transpose
     (``csr_transpose_device``) and the transposed edge order (``weighted.transpose_order``).  Gradients come back in the operands'
-    dtypes."""
+    dtypes.  Multi-head: ``x`` [num_rows, H, D], ``y`` [num_cols, H, D] -> ``s`` [nnz, H]; the backward is ``voltrix.spmm_heads``."""
 
     def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, num_rows: int, num_cols: int = None):
         from .weighted import transpose_order
@@ -138,7 +152,8 @@ class SDDMM:
         self.t_order = transpose_order(self.indptr, self.indices, num_rows)
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-        assert x.shape[0] == self.num_rows and y.shape[0] == self.num_cols and x.shape[1] == y.shape[1]
+        assert x.dim() in (2, 3) and x.dim() == y.dim()
+        assert x.shape[0] == self.num_rows and y.shape[0] == self.num_cols and x.shape[1:] == y.shape[1:]
         return _SDDMMFunction.apply(x, y, self)
 
 
@@ -164,7 +179,7 @@ class _EdgeSoftmaxFunction(torch.autograd.Function):
 class EdgeSoftmax:
     """``alpha = softmax(scale * scores)`` over every row of a CSR pattern with ``num_rows`` rows (``voltrix.edge_softmax``), differentiable
     in the scores: the attention weights between ``SDDMM`` and ``SpMM(..., values=)``.  Holds the device ``indptr``; the column ids do not
-    matter.  ``alpha`` is float32; the gradient comes back in the scores' dtype."""
+    matter.  ``alpha`` is float32; the gradient comes back in the scores' dtype.  ``scores`` [nnz] or, multi-head, [nnz, H]."""
 
     def __init__(self, indptr: torch.Tensor, num_rows: int):
         assert indptr.dtype == torch.int32 and indptr.numel() == num_rows + 1
@@ -172,8 +187,57 @@ class EdgeSoftmax:
         self.indptr = indptr.contiguous().cuda()
 
     def __call__(self, scores: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
-        assert scores.dim() == 1
+        assert scores.dim() in (1, 2)
         return _EdgeSoftmaxFunction.apply(scores, self, float(scale))
+
+
+class _SpMMHeadsFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, values, op):
+        from .sddmm import spmm_heads
+
+        ctx.op = op
+        ctx.save_for_backward(feat, values)
+        return spmm_heads(op.indptr, op.indices, values, feat, op.num_rows)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .sddmm import sddmm, spmm_heads
+
+        op = ctx.op
+        feat, values = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        grad_feat = grad_values = None
+        if ctx.needs_input_grad[0]:           # csr(values)^T @ dC per head: the transposed CSR, the values in its edge order
+            grad_feat = spmm_heads(op.t_indptr, op.t_indices, values.detach()[op.t_order], grad_out, op.num_cols).to(feat.dtype)
+        if ctx.needs_input_grad[1]:           # dv[e, h] = <dC[row_e, h], feat[col_e, h]>
+            grad_values = sddmm(op.indptr, op.indices, grad_out, feat).to(values.dtype)
+        return grad_feat, grad_values, None
+
+
+class SpMMHeads:
+    """Multi-head aggregation ``out[r, h] = sum_{e in row r} values[e, h] feat[col_e, h]`` on a CSR pattern [num_rows, num_cols]
+    (``num_cols`` defaults to ``num_rows``), differentiable in ``feat`` [num_cols, H, D] and ``values`` [nnz, H]: the last step of a
+    multi-head attention layer, ``SpMMHeads(...)(v, EdgeSoftmax(...)(SDDMM(...)(q, k), d ** -0.5))``.  Built once per pattern: the
+    device CSR, its transpose and the transposed edge order -- no block-format handle, and nothing is installed per call
+    (``voltrix.spmm_heads`` reads the values where it uses them).  ``out`` is float32 [num_rows, H, D]; ``feat.grad =
+    spmm_heads(csr^T, values[t_order], dC)`` and ``values.grad = sddmm(dC, feat)`` come back in the inputs' dtypes."""
+
+    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, num_rows: int, num_cols: int = None):
+        from .weighted import transpose_order
+
+        assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+        self.num_rows = num_rows
+        self.num_cols = num_rows if num_cols is None else int(num_cols)
+        self.num_edges = int(indices.numel())
+        self.indptr, self.indices = indptr.contiguous().cuda(), indices.contiguous().cuda()
+        self.t_indptr, self.t_indices = csr_transpose_device(self.indptr, self.indices, num_rows, self.num_cols)
+        self.t_order = transpose_order(self.indptr, self.indices, num_rows)
+
+    def __call__(self, feat: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
+        assert feat.dim() == 3 and values.dim() == 2 and feat.shape[0] == self.num_cols
+        assert values.shape == (self.num_edges, feat.shape[1]), (tuple(values.shape), self.num_edges, feat.shape[1])
+        return _SpMMHeadsFunction.apply(feat, values, self)
 
 
 class SpMM:

@@ -75,6 +75,11 @@ SYMBOLS = (
     "voltrix_edge_softmax_workspace_bytes",
     "voltrix_launch_edge_softmax_csr",
     "voltrix_launch_edge_softmax_backward_csr",
+    "voltrix_launch_sddmm_heads_csr",
+    "voltrix_edge_softmax_heads_workspace_bytes",
+    "voltrix_launch_edge_softmax_heads_csr",
+    "voltrix_launch_edge_softmax_heads_backward_csr",
+    "voltrix_launch_spmm_csr_heads",
     "voltrix_csr_preprocess_workspace_bytes",
     "voltrix_launch_csr_window_count",
     "voltrix_launch_csr_fill",
@@ -118,6 +123,7 @@ def lib() -> ctypes.CDLL:
         _lib.voltrix_cm_rank_workspace_bytes.restype = ctypes.c_int64
         _lib.voltrix_csr_transpose_workspace_bytes.restype = ctypes.c_int64
         _lib.voltrix_edge_softmax_workspace_bytes.restype = ctypes.c_int64
+        _lib.voltrix_edge_softmax_heads_workspace_bytes.restype = ctypes.c_int64
         for name in SYMBOLS:
             if name.startswith("voltrix_launch_") or name in ("voltrix_spmm_default_tile", "voltrix_spmm_tile_at"):
                 getattr(_lib, name).restype = None
@@ -674,6 +680,117 @@ def launch_edge_softmax_backward_csr(indptr, num_rows: int, alpha, grad_alpha, s
     check(rc.value, "voltrix_launch_edge_softmax_backward_csr")
 
 
+# ---- multi-head forms (csrc/capi_heads.hip): node tensors [n, H, D], edge tensors [nnz, H] with the head index fastest
+_CODES = None
+_sddmm_heads = None
+_edge_softmax_heads = None
+_edge_softmax_heads_backward = None
+_spmm_csr_heads = None
+
+
+def _dtype_code(dtype) -> int:
+    import torch
+
+    global _CODES
+    if _CODES is None:
+        _CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+    return _CODES[dtype]
+
+
+def launch_sddmm_heads_csr(indptr, indices, num_rows: int, x, y, out, stream) -> None:
+    """``out[e, h] = <x[row_e, h], y[indices[e], h]>`` for every entry of a device int32 CSR (voltrix/sddmm_heads_kernels.hpp): ``x``
+    [num_rows, H, D], ``y`` [*, H, D], the dtype pairs of ``launch_sddmm_csr``, D a multiple of 16 bytes of ``y``; ``out`` float32
+    [nnz, H]; see include/voltrix_capi.h."""
+    import torch
+
+    global _sddmm_heads
+    if _sddmm_heads is None:
+        fn = lib().voltrix_launch_sddmm_heads_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                       ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        _sddmm_heads = fn
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert x.dim() == 3 and y.dim() == 3 and x.is_contiguous() and y.is_contiguous() and x.shape[0] == num_rows
+    assert x.shape[1:] == y.shape[1:] and out.dtype == torch.float32 and out.is_contiguous()
+    assert out.shape == (indices.numel(), x.shape[1])
+    rc = ctypes.c_int(-1)
+    _sddmm_heads(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), x.shape[1], x.shape[2], x.data_ptr(),
+                 _dtype_code(x.dtype), y.data_ptr(), _dtype_code(y.dtype), out.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_sddmm_heads_csr")
+
+
+def edge_softmax_heads_workspace_bytes(num_rows: int, nnz: int, heads: int) -> int:
+    """Bytes of device workspace both multi-head edge softmax entry points need (a function of ``nnz`` and ``heads`` alone; with
+    ``heads == 1`` the single-head size)."""
+    return int(lib().voltrix_edge_softmax_heads_workspace_bytes(ctypes.c_int(num_rows), ctypes.c_int64(nnz), ctypes.c_int(heads)))
+
+
+def launch_edge_softmax_heads_csr(indptr, num_rows: int, scores, scale: float, out, workspace, stream) -> None:
+    """``out[:, h]`` = softmax of ``scale * scores[:, h]`` over every row of a device int32 CSR, for every head
+    (voltrix/edge_softmax_heads_kernels.hpp): ``scores`` and ``out`` float32 [nnz, H], ``workspace`` uint8 of
+    ``edge_softmax_heads_workspace_bytes`` bytes; see include/voltrix_capi.h."""
+    import torch
+
+    global _edge_softmax_heads
+    if _edge_softmax_heads is None:
+        fn = lib().voltrix_launch_edge_softmax_heads_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        _edge_softmax_heads = fn
+    assert indptr.dtype == torch.int32 and indptr.numel() == num_rows + 1 and indptr.is_contiguous()
+    assert scores.dim() == 2 and scores.dtype == torch.float32 and out.dtype == torch.float32
+    assert scores.is_contiguous() and out.is_contiguous() and out.shape == scores.shape
+    nnz, heads = scores.shape
+    assert workspace.numel() >= edge_softmax_heads_workspace_bytes(num_rows, nnz, heads)
+    rc = ctypes.c_int(-1)
+    _edge_softmax_heads(indptr.data_ptr(), num_rows, nnz, heads, scores.data_ptr(), float(scale), out.data_ptr(), workspace.data_ptr(),
+                        stream, rc)
+    check(rc.value, "voltrix_launch_edge_softmax_heads_csr")
+
+
+def launch_edge_softmax_heads_backward_csr(indptr, num_rows: int, alpha, grad_alpha, scale: float, grad_scores, workspace, stream) -> None:
+    """The multi-head edge softmax's backward, all float32 [nnz, H]; the forward's workspace size; see include/voltrix_capi.h."""
+    import torch
+
+    global _edge_softmax_heads_backward
+    if _edge_softmax_heads_backward is None:
+        fn = lib().voltrix_launch_edge_softmax_heads_backward_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        _edge_softmax_heads_backward = fn
+    assert indptr.dtype == torch.int32 and indptr.numel() == num_rows + 1 and indptr.is_contiguous()
+    for t in (alpha, grad_alpha, grad_scores):
+        assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous() and t.shape == alpha.shape
+    nnz, heads = alpha.shape
+    assert workspace.numel() >= edge_softmax_heads_workspace_bytes(num_rows, nnz, heads)
+    rc = ctypes.c_int(-1)
+    _edge_softmax_heads_backward(indptr.data_ptr(), num_rows, nnz, heads, alpha.data_ptr(), grad_alpha.data_ptr(), float(scale),
+                                 grad_scores.data_ptr(), workspace.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_edge_softmax_heads_backward_csr")
+
+
+def launch_spmm_csr_heads(indptr, indices, values, num_rows: int, feat, output, stream) -> None:
+    """``output[r, h] = sum_{e in row r} values[e, h] * feat[indices[e], h]`` (voltrix/spmm_csr_heads_kernels.hpp): device int32 CSR,
+    ``values`` float32 [nnz, H], fp32 / fp16 / bf16 ``feat`` [*, H, D] with D a multiple of 16 bytes, fp32 ``output`` [num_rows, H, D];
+    see include/voltrix_capi.h."""
+    import torch
+
+    global _spmm_csr_heads
+    if _spmm_csr_heads is None:
+        fn = lib().voltrix_launch_spmm_csr_heads
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                       ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        _spmm_csr_heads = fn
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert feat.dim() == 3 and feat.is_contiguous() and output.is_contiguous() and output.dtype == torch.float32
+    assert output.shape == (num_rows,) + tuple(feat.shape[1:])
+    assert values.dtype == torch.float32 and values.is_contiguous() and values.shape == (indices.numel(), feat.shape[1])
+    rc = ctypes.c_int(-1)
+    _spmm_csr_heads(indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), num_rows, feat.shape[1], feat.shape[2], feat.data_ptr(),
+                    _dtype_code(feat.dtype), output.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_spmm_csr_heads")
+
+
 def launch_scatter_values(values, slots, plane, stream) -> None:
     """``plane.view(-1)[slots[e]] = values[e]`` (device float32 values, int64 slots, fp32 / fp16 / bf16 plane); see
     include/voltrix_capi.h."""
@@ -747,6 +864,10 @@ launch_spmm_csr_rows = _timed(launch_spmm_csr_rows, "spmm_csr_rows", 5)
 launch_sddmm_csr = _timed(launch_sddmm_csr, "sddmm_csr", 6)
 launch_edge_softmax_csr = _timed(launch_edge_softmax_csr, "edge_softmax_csr", 6)
 launch_edge_softmax_backward_csr = _timed(launch_edge_softmax_backward_csr, "edge_softmax_backward_csr", 7)
+launch_sddmm_heads_csr = _timed(launch_sddmm_heads_csr, "sddmm_heads_csr", 6)
+launch_edge_softmax_heads_csr = _timed(launch_edge_softmax_heads_csr, "edge_softmax_heads_csr", 6)
+launch_edge_softmax_heads_backward_csr = _timed(launch_edge_softmax_heads_backward_csr, "edge_softmax_heads_backward_csr", 7)
+launch_spmm_csr_heads = _timed(launch_spmm_csr_heads, "spmm_csr_heads", 6)
 launch_spmm_f32_as_f16 = _timed(launch_spmm_f32_as_f16, "spmm_f32_as_f16", 9)
 launch_window_order = _timed(launch_window_order, "window_order", 3)
 launch_csr_window_count = _timed(launch_csr_window_count, "csr_window_count", 8)

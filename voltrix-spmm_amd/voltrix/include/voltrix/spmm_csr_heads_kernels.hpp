@@ -1,0 +1,135 @@
+// Voltrix-SpMM for MI355X (gfx950) -- multi-head aggregation straight from the CSR: out[r, h, :] = sum_{e in row r} v[e, h] feat[col_e, h, :]
+// for feat [*, H, D] (rows of H D), v [nnz, H] fp32 with the head index fastest, out [num_rows, H, D] fp32.
+//
+// Why it exists.  It is the last step of a multi-head attention layer (scores: sddmm_heads_kernels.hpp, weights:
+// edge_softmax_heads_kernels.hpp) and the backward of the multi-head SDDMM.  Through the single-head operators every head is a pass of
+// its own at F = D: H reads of indptr / indices, H gathers of a D-wide slice, and -- on the block-format path -- the head's values
+// scattered into the value planes of A and A^T first.  Here nothing is installed: the values are read where they are used.
+//
+// Shape.  spmm_csr_rows_kernel<T, 4, true> where a lane multiplies by the value of ITS head: a group of L = min(64, next_pow2(H D / V))
+// lanes owns one row, grid.y walks slabs of 64 pieces, a lane owns 16 bytes of every gathered row and its head is piece / (D / V).  One
+// indices read and one gathered row per edge serve all heads; the H values of an edge are 4 H consecutive bytes, read by every lane as
+// the one float of its head (the lanes of a head share the address, the group shares the one or two 32-byte sectors).  Batches of 4
+// edges in flight, the tail batch clamped, as in the single-head kernel.
+//
+// Numerics.  fp32 products, one fused multiply-add per element, summed in CSR edge order: out[:, h] has the BITS of
+// spmm_csr_rows_kernel<T, 4, true> on the contiguous slices v[:, h], feat[:, h].  |out - ref| <= deg_r 2^-23 sum_e |v[e, h]| |feat[col_e, h, d]|.
+// Offsets e H + h and row H D are 64-bit.
+//
+// Bound and known limit: the CUs' line-request rate / HBM; a row per lane group keeps the single-head kernel's weakness on hub rows (a
+// hub row of a web graph serialises its wave).  Splitting hub rows with a fixed-order combine is the follow-up.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdint>
+
+#include "voltrix/spmm_csr_kernels.hpp"
+
+namespace voltrix {
+
+template <typename T>
+struct CsrHeadsArgs {
+  const int* indptr;    // [num_rows + 1]
+  const int* indices;   // [nnz] column ids = rows of `input`
+  const T* input;       // [*, H, D] row-major, rows 16-byte aligned
+  float* output;        // [num_rows, H, D]
+  const float* values;  // [nnz, H] fp32 edge values in CSR order (duplicate entries add)
+  int num_rows;
+  int heads;            // H
+  int head_pieces;      // D / V
+  int F;                // H * D
+  int lanes_per_row;    // power of two <= 64
+  int groups_per_xcd;   // ceil(row groups / 8): sizes the grid; a row group = 256 / lanes_per_row rows
+};
+
+template <typename T, int UNROLL>
+static __global__ __launch_bounds__(256) void spmm_csr_heads_kernel(const CsrHeadsArgs<T> a) {
+  constexpr int V = 16 / (int)sizeof(T);
+  const int L = a.lanes_per_row;
+  const int rows_per_group = 256 / L;
+  // XCD x owns the row groups [x * groups_per_xcd, (x + 1) * groups_per_xcd)
+  const long long group = (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd;
+  const long long row = group * rows_per_group + (int)threadIdx.x / L;
+  if (row >= a.num_rows) return;
+  const int lane = (int)threadIdx.x & (L - 1);
+  const int piece = (int)blockIdx.y * 64 + lane;                       // this lane's 16 bytes of every gathered row
+  const long long col0 = (long long)piece * V;
+  if (col0 >= a.F) return;
+  const long long H = a.heads;
+  const float* const vals = a.values + piece / a.head_pieces;          // this lane's head: v[e, head] = vals[e H]
+  float acc[V];
+#pragma unroll
+  for (int i = 0; i < V; ++i) acc[i] = 0.0f;
+  int e = a.indptr[row];
+  const int end = a.indptr[row + 1];
+  const T* const base = a.input + col0;
+  const long long F = a.F;
+  // full batches of UNROLL edges, then one more batch for the tail with clamped ids (spmm_csr_rows_kernel: every load issued before the
+  // first is consumed)
+  for (; e + UNROLL <= end; e += UNROLL) {
+    uint4_t raw[UNROLL];
+    float v[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[e + u] * F);
+      v[u] = vals[(long long)(e + u) * H];
+    }
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) csr_accumulate_scaled<T>(acc, raw[u], v[u]);
+  }
+  if (e < end) {
+    uint4_t raw[UNROLL];
+    float v[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const int ee = e + u < end ? e + u : end - 1;
+      raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
+      v[u] = vals[(long long)ee * H];
+    }
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u)
+      if (e + u < end) csr_accumulate_scaled<T>(acc, raw[u], v[u]);
+  }
+  float4_t* out = reinterpret_cast<float4_t*>(a.output + row * F + col0);
+#pragma unroll
+  for (int i = 0; i < V / 4; ++i) out[i] = float4_t{acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]};
+}
+
+// dtype: 0 fp32, 1 fp16, 2 bfloat16.  head_dim % (16 / sizeof(T)) == 0 (a head is a whole number of 16-byte pieces).  Every row of
+// `output` is written (empty rows: zeros).  Nothing is checked on the device: indptr must be a valid CSR of num_rows rows whose last
+// entry is the number of rows of `values`, and every index a row of `input`.
+inline int launch_spmm_csr_heads(const int* indptr, const int* indices, const float* values, int num_rows, int heads, int head_dim,
+                                 const void* input, int dtype, float* output, hipStream_t stream) {
+  if (num_rows < 0 || head_dim < 0 || heads < 1 || dtype < 0 || dtype > 2 || (long long)heads * head_dim > INT_MAX) return kErrBadShape;
+  const int v = dtype == 0 ? 4 : 8;
+  if (head_dim % v) return kErrBadShape;
+  if (num_rows == 0 || head_dim == 0) return kOk;
+  if (indptr == nullptr || indices == nullptr || values == nullptr || input == nullptr || output == nullptr || ((uintptr_t)indptr & 3) ||
+      ((uintptr_t)indices & 3) || ((uintptr_t)values & 3) || ((uintptr_t)input & 15) || ((uintptr_t)output & 15))
+    return kErrBadShape;
+  const int head_pieces = head_dim / v;
+  const int pieces = heads * head_pieces;                // 16-byte pieces per row
+  const int slab_pieces = pieces < 64 ? pieces : 64;
+  int lanes = 1;
+  while (lanes < slab_pieces) lanes <<= 1;
+  const int slabs = (pieces + 63) / 64;
+  const int rows_per_group = 256 / lanes;
+  const long long groups = ((long long)num_rows + rows_per_group - 1) / rows_per_group;
+  const long long per_xcd = (groups + kNumXcd - 1) / kNumXcd;
+  if (per_xcd * kNumXcd > 0x7fffffffLL || slabs > 65535) return kErrBadShape;
+  const dim3 grid((unsigned)(per_xcd * kNumXcd), (unsigned)slabs);
+  auto go = [&](auto tag) {
+    using T = decltype(tag);
+    const CsrHeadsArgs<T> a{indptr, indices, static_cast<const T*>(input), output, values, num_rows, heads, head_pieces,
+                            heads * head_dim, lanes, (int)per_xcd};
+    hipLaunchKernelGGL((spmm_csr_heads_kernel<T, 4>), grid, dim3(256), 0, stream, a);
+  };
+  if (dtype == 0) go(float{});
+  else if (dtype == 1) go(_Float16{});
+  else go(bfloat16_bits{});
+  return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+}  // namespace voltrix
