@@ -3,8 +3,9 @@ no reference counterpart -- the reference is forward-only and has no edge values
 
     Wh = X W,   s_ij = LeakyReLU(a_l . Wh_i + a_r . Wh_j),   alpha = edge softmax of s over every row,   H_i = sum_j alpha_ij Wh_j
 
-(Velickovic et al.).  The per-node scalars a_l . Wh and a_r . Wh are gathered to the edges with torch over a cached row-id tensor and the
-column ids; the softmax over every row is ``voltrix.autograd.EdgeSoftmax`` (deterministic HIP kernels, forward and backward); the
+(Velickovic et al.).  The per-node scalars a_l . Wh and a_r . Wh are torch matmuls; the scores are ``voltrix.autograd.GATScore`` (one
+column id per edge, no row-id or int64 column-id tensor, and two segment sums instead of two atomic scatters in the backward); the softmax
+over every row is ``voltrix.autograd.EdgeSoftmax`` (deterministic HIP kernels, forward and backward); the
 aggregation is ``voltrix.autograd.SpMM(..., values=alpha)`` on fp16 ``Wh``, which returns ``alpha``'s gradient through the sampled
 dense-dense product.  Self loops are added so that every node attends to itself.
 
@@ -37,20 +38,37 @@ def with_self_loops(indptr, indices, n):
 
 
 class Graph:
-    """What both layers share: the row ids and column ids of every edge (int64, for the gathers), the edge softmax and the aggregation
-    operator (built once: A and A^T).  ``heads`` > 1: the multi-head aggregation (the device CSR and its transpose; no handle)."""
+    """What both layers share: the edge scores, the edge softmax and the aggregation operator (built once: A and A^T).  ``heads`` > 1:
+    the multi-head aggregation (the device CSR and its transpose; no handle), whose transpose the scores share.  ``rows`` / ``cols``
+    (int64 row and column id of every edge) are built when something asks for them; the training run never does."""
 
     def __init__(self, indptr, indices, n, hash_tag="example_gat", heads=1):
-        from voltrix.autograd import EdgeSoftmax, SpMM, SpMMHeads
+        from voltrix.autograd import EdgeSoftmax, GATScore, SpMM, SpMMHeads
 
         self.n, self.heads = n, heads
-        self.rows = torch.repeat_interleave(torch.arange(n, device="cuda"), (indptr[1:] - indptr[:-1]).long())
-        self.cols = indices.long().cuda()
+        self._indptr, self._indices = indptr, indices
+        self._rows = self._cols = None
         self.softmax = EdgeSoftmax(indptr, n)
         if heads > 1:
             self.aggregate = SpMMHeads(indptr, indices, n)
+            agg = self.aggregate
+            self.score = GATScore(indptr, indices, n, transposed=(agg.t_indptr, agg.t_indices, agg.t_order))
         else:
             self.aggregate = SpMM(indptr, indices, n, values=torch.ones(indices.numel(), device="cuda"), hash_tag=hash_tag)
+            self.score = GATScore(indptr, indices, n)
+
+    @property
+    def rows(self):
+        if self._rows is None:
+            deg = (self._indptr[1:] - self._indptr[:-1]).long().cuda()
+            self._rows = torch.repeat_interleave(torch.arange(self.n, device="cuda"), deg)
+        return self._rows
+
+    @property
+    def cols(self):
+        if self._cols is None:
+            self._cols = self._indices.long().cuda()
+        return self._cols
 
 
 class GATLayer(torch.nn.Module):
@@ -64,7 +82,7 @@ class GATLayer(torch.nn.Module):
     def forward(self, x):
         g = self.graph
         wh = self.w(x)
-        s = torch.nn.functional.leaky_relu((wh @ self.a_l)[g.rows] + (wh @ self.a_r)[g.cols], self.slope)
+        s = g.score(wh @ self.a_l, wh @ self.a_r, self.slope)
         alpha = g.softmax(s)
         return g.aggregate(wh.half(), values=alpha)
 
@@ -82,7 +100,7 @@ class GATHeadsLayer(torch.nn.Module):
     def forward(self, x):
         g = self.graph
         wh = self.w(x).view(g.n, g.heads, self.out_feats)
-        s = torch.nn.functional.leaky_relu((wh * self.a_l).sum(-1)[g.rows] + (wh * self.a_r).sum(-1)[g.cols], self.slope)
+        s = g.score((wh * self.a_l).sum(-1), (wh * self.a_r).sum(-1), self.slope)
         out = g.aggregate(wh.half(), g.softmax(s))            # scores, weights [nnz, H]; out [n, H, out_feats]
         return out.flatten(1) if self.concat else out.mean(1)
 
@@ -136,7 +154,7 @@ def main():
             print(f"epoch {epoch}: loss {float(loss):.4f}, {times[-1]:.2f} ms")
     steady = sorted(times[2:])[len(times[2:]) // 2] if len(times) > 2 else times[-1]
     print(f"steady epoch (forward + backward + Adam, full graph): {steady:.2f} ms -- two attention layers, hidden {hidden}"
-          + (f", {heads} heads" if heads > 1 else ""))
+          + (f", {heads} heads" if heads > 1 else "") + f"; peak memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
 
 
 if __name__ == "__main__":

@@ -506,6 +506,36 @@ void voltrix_launch_edge_softmax_heads_backward_csr(void* indptr, int num_rows, 
 void voltrix_launch_spmm_csr_heads(void* indptr, void* indices, void* values, int num_rows, int heads, int head_dim, void* input,
                                    int dtype, void* output, void* stream, int* return_code);
 
+/* GAT edge scores (gat_score_kernels.hpp): out[e, h] = leaky_relu(el[row_e, h] + er[indices[e], h], slope) for every entry e < nnz of a
+ * DEVICE CSR (int32 indptr[num_rows + 1], indices[nnz]); el = device float[num_rows, heads], er = device float[*, heads] (gathered by
+ * indices), out = device float[nnz, heads] in CSR order with the head index fastest, every element written (duplicate entries are
+ * edges of their own).  z = el + er is one fp32 add; z > 0 gives z, anything else (z == 0 and NaN included, as torch's leaky_relu)
+ * float(slope) * z.  slope: any finite float (1: the plain sum; 0: ReLU; negative allowed).  Against float64 from the fp32 inputs:
+ * |out - ref| <= 1.5 * 2^-23 |ref| + 2^-149, and 2^-24 |ref| + 2^-149 when slope is 1 or a power of two; the sign of z is the sign of
+ * the exact sum.  A NaN or +-inf in el[r, h] reaches only row r's entries of head h.  One launch split by edges (`indices` is read once
+ * per edge), no workspace, no host synchronisation, 64-bit element offsets.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: heads < 1 or > 65535, negative sizes, nnz > INT_MAX, nnz > 0 with
+ * num_rows == 0, heads * num_rows > INT_MAX, a non-finite slope, a null or misaligned (4 bytes) pointer; VOLTRIX_OK without a launch
+ * for nnz == 0.  No reference counterpart (the reference is forward-only and has no edge values). */
+void voltrix_launch_gat_score_csr(void* indptr, void* indices, int num_rows, int64_t nnz, int heads, void* el, void* er, float slope,
+                                  void* out, void* stream, int* return_code);
+
+/* The segment sum of its backward: out[r, h] = sum_{e in row r} gz, gz = z > 0 ? g : float(slope) * g with
+ * z = a[r, h] + b[indices[e], h] and g = grad[order ? order[e] : e, h]; out = device float[num_rows, heads], every element written,
+ * empty rows 0.  d_el is this on the CSR with (a, b) = (el, er) and order = NULL; d_er is this on the transposed CSR
+ * (voltrix_launch_csr_transpose) with (a, b) = (er, el) and order = device int32[nnz], the entry of the CSR that entry e of the
+ * transpose is: fp32 addition commutes, so the gate is the forward's decision to the bit.  Every term is g or one rounded product and a
+ * row of deg entries has deg - 1 additions in an order fixed by the pattern alone:
+ * |out - ref| <= deg * 2^-23 * sum |gz| + 2^-149 per row and head.  Deterministic: no float atomics, the same bits on every launch, and
+ * out[:, h] of a call with `heads` heads has the bits of the single-head call on the contiguous slices a[:, h], b[:, h], grad[:, h].  A
+ * NaN in grad[e, h] reaches only the one sum that holds it.  Three launches (zero fill, chunk sums, merge of the rows that cross a chunk
+ * of 2048 edges), split by edges so a hub row costs what its edges cost; no host synchronisation.  workspace: device, 16-byte aligned,
+ * voltrix_gat_score_workspace_bytes(num_rows, nnz, heads) bytes -- a function of (nnz, heads) alone, a multiple of 16, 0 for nnz == 0.
+ * The checks of voltrix_launch_gat_score_csr; nnz == 0 zero-fills out (num_rows > 0 then needs a valid out) and is VOLTRIX_OK. */
+int64_t voltrix_gat_score_workspace_bytes(int num_rows, int64_t nnz, int heads);
+void voltrix_launch_gat_score_rowsum_csr(void* indptr, void* indices, void* order, int num_rows, int64_t nnz, int heads, void* a, void* b,
+                                         void* grad, float slope, void* out, void* workspace, void* stream, int* return_code);
+
 /* Rows of a dense row-major matrix times a per-row factor: dst[i, :] = T(float(src[i, :]) * scale[i]); dst may be src.
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,

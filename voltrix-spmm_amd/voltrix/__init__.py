@@ -17,6 +17,7 @@ from .weighted import WeightedHandle, csr_preprocess_weighted, spmm_weighted
 from .weighted import update_values as update_edge_values
 from .sddmm import sddmm, spmm_heads
 from .edge_softmax import edge_softmax
+from .gat_score import gat_score
 from .graphed import GraphedSpMM
 from . import autograd, hybrid, jit, sidecar, utils
 

@@ -27,6 +27,9 @@ Edge values that are learnt (attention coefficients, edge gates) get a gradient 
 softmax's forward and backward are the kernels of ``voltrix.edge_softmax`` (three launches each, deterministic); together the three
 operators make an attention layer: ``SpMM(...)(v, values=EdgeSoftmax(...)(SDDMM(...)(q, k), d ** -0.5))``.
 
+GAT's scores are ``voltrix.autograd.GATScore(indptr, indices, n)(el, er, slope)``: ``leaky_relu(el[row] + er[col])`` per edge, with
+``el.grad`` / ``er.grad`` as deterministic segment sums over the rows / the columns (``voltrix.gat_score``; [n] or [n, H] scalars).
+
 Multi-head: ``SDDMM`` takes ``q, k`` [n, H, D] and gives scores [nnz, H], ``EdgeSoftmax`` takes [nnz, H], and ``SpMMHeads`` aggregates
 ``v`` [n, H, D] with weights [nnz, H] -- one launch per operator for all heads, the per-head bits of the single-head kernels:
 
@@ -238,6 +241,61 @@ class SpMMHeads:
         assert feat.dim() == 3 and values.dim() == 2 and feat.shape[0] == self.num_cols
         assert values.shape == (self.num_edges, feat.shape[1]), (tuple(values.shape), self.num_edges, feat.shape[1])
         return _SpMMHeadsFunction.apply(feat, values, self)
+
+
+class _GATScoreFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, el, er, op, slope):
+        from .gat_score import gat_score
+
+        ctx.op, ctx.slope = op, slope
+        ctx.save_for_backward(el, er)
+        return gat_score(op.indptr, op.indices, el, er, slope)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .gat_score import gat_score_backward
+
+        op = ctx.op
+        el, er = ctx.saved_tensors
+        g = grad_out.float().contiguous()
+        grad_el = grad_er = None
+        if ctx.needs_input_grad[0]:           # the sum over every row of the CSR
+            grad_el = gat_score_backward(op.indptr, op.indices, el.detach(), er.detach(), g, ctx.slope).to(el.dtype)
+        if ctx.needs_input_grad[1]:           # the sum over every column: the transposed CSR, g read through its edge order
+            grad_er = gat_score_backward(op.t_indptr, op.t_indices, er.detach(), el.detach(), g, ctx.slope, order=op.t_order).to(er.dtype)
+        return grad_el, grad_er, None, None
+
+
+class GATScore:
+    """GAT's edge scores ``s[e] = leaky_relu(el[row_e] + er[col_e], slope)`` on a CSR pattern [num_rows, num_cols] (``num_cols`` defaults
+    to ``num_rows``), differentiable in both node scalars: the first step of ``SpMMHeads(...)(wh, EdgeSoftmax(...)(GATScore(...)(el,
+    er)))``.  ``el`` [num_rows] or [num_rows, H], ``er`` [num_cols] or [num_cols, H] -> float32 [nnz] or [nnz, H].  Built once per
+    pattern: the device CSR, its transpose and the transposed edge order (kept as int32); ``transposed=(t_indptr, t_indices, t_order)``
+    takes ones that exist already (an ``SpMMHeads`` or ``SDDMM`` of the same pattern).  The backward is two segment sums
+    (``voltrix.gat_score.gat_score_backward``): no index op, no float atomics, the same bits on every run; gradients come back in the
+    inputs' dtypes, and a side that needs none is skipped."""
+
+    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, num_rows: int, num_cols: int = None, transposed=None):
+        assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+        self.num_rows = num_rows
+        self.num_cols = num_rows if num_cols is None else int(num_cols)
+        self.num_edges = int(indices.numel())
+        self.indptr, self.indices = indptr.contiguous().cuda(), indices.contiguous().cuda()
+        if transposed is None:
+            from .weighted import transpose_order
+
+            t_indptr, t_indices = csr_transpose_device(self.indptr, self.indices, num_rows, self.num_cols)
+            t_order = transpose_order(self.indptr, self.indices, num_rows)
+        else:
+            t_indptr, t_indices, t_order = transposed
+            assert t_indptr.numel() == self.num_cols + 1 and t_indices.numel() == self.num_edges == t_order.numel()
+        self.t_indptr, self.t_indices, self.t_order = t_indptr, t_indices, t_order.to(torch.int32).contiguous()
+
+    def __call__(self, el: torch.Tensor, er: torch.Tensor, slope: float = 0.2) -> torch.Tensor:
+        assert el.dim() in (1, 2) and el.dim() == er.dim() and el.shape[1:] == er.shape[1:]
+        assert el.shape[0] == self.num_rows and er.shape[0] == self.num_cols
+        return _GATScoreFunction.apply(el, er, self, float(slope))
 
 
 class SpMM:

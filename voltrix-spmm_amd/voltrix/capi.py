@@ -80,6 +80,9 @@ SYMBOLS = (
     "voltrix_launch_edge_softmax_heads_csr",
     "voltrix_launch_edge_softmax_heads_backward_csr",
     "voltrix_launch_spmm_csr_heads",
+    "voltrix_launch_gat_score_csr",
+    "voltrix_gat_score_workspace_bytes",
+    "voltrix_launch_gat_score_rowsum_csr",
     "voltrix_csr_preprocess_workspace_bytes",
     "voltrix_launch_csr_window_count",
     "voltrix_launch_csr_fill",
@@ -124,6 +127,7 @@ def lib() -> ctypes.CDLL:
         _lib.voltrix_csr_transpose_workspace_bytes.restype = ctypes.c_int64
         _lib.voltrix_edge_softmax_workspace_bytes.restype = ctypes.c_int64
         _lib.voltrix_edge_softmax_heads_workspace_bytes.restype = ctypes.c_int64
+        _lib.voltrix_gat_score_workspace_bytes.restype = ctypes.c_int64
         for name in SYMBOLS:
             if name.startswith("voltrix_launch_") or name in ("voltrix_spmm_default_tile", "voltrix_spmm_tile_at"):
                 getattr(_lib, name).restype = None
@@ -791,6 +795,68 @@ def launch_spmm_csr_heads(indptr, indices, values, num_rows: int, feat, output, 
     check(rc.value, "voltrix_launch_spmm_csr_heads")
 
 
+# ---- GAT edge scores (csrc/capi_gat_score.hip): node scalars [n, H], edge tensors [nnz, H] with the head index fastest
+_gat_score = None
+_gat_score_rowsum = None
+
+
+def gat_score_workspace_bytes(num_rows: int, nnz: int, heads: int = 1) -> int:
+    """Bytes of device workspace ``launch_gat_score_rowsum_csr`` needs (a function of ``nnz`` and ``heads`` alone; 0 for nnz == 0)."""
+    return int(lib().voltrix_gat_score_workspace_bytes(ctypes.c_int(num_rows), ctypes.c_int64(nnz), ctypes.c_int(heads)))
+
+
+def launch_gat_score_csr(indptr, indices, num_rows: int, el, er, slope: float, out, stream) -> None:
+    """``out[e, h] = leaky_relu(el[row_e, h] + er[indices[e], h], slope)`` for every entry of a device int32 CSR
+    (voltrix/gat_score_kernels.hpp): ``el`` float32 [num_rows, H], ``er`` float32 [*, H], ``out`` float32 [nnz, H]; see
+    include/voltrix_capi.h."""
+    import torch
+
+    global _gat_score
+    if _gat_score is None:
+        fn = lib().voltrix_launch_gat_score_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        _gat_score = fn
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    for t in (el, er, out):
+        assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous() and t.shape[1] == out.shape[1]
+    assert el.shape[0] == num_rows and out.shape[0] == indices.numel()
+    rc = ctypes.c_int(-1)
+    _gat_score(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), out.shape[1], el.data_ptr(), er.data_ptr(), float(slope),
+               out.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_gat_score_csr")
+
+
+def launch_gat_score_rowsum_csr(indptr, indices, order, num_rows: int, a, b, grad, slope: float, out, workspace, stream) -> None:
+    """``out[r, h] = sum_{e in row r} gate(a[r, h] + b[indices[e], h]) grad[order[e] if order is not None else e, h]`` with ``gate(z) =
+    1 if z > 0 else slope``: ``a`` float32 [num_rows, H], ``b`` float32 [*, H], ``grad`` float32 [nnz, H], ``order`` None or int32
+    [nnz], ``out`` float32 [num_rows, H] (every element written), ``workspace`` uint8 of ``gat_score_workspace_bytes`` bytes; see
+    include/voltrix_capi.h."""
+    import torch
+
+    global _gat_score_rowsum
+    if _gat_score_rowsum is None:
+        fn = lib().voltrix_launch_gat_score_rowsum_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.POINTER(ctypes.c_int)]
+        _gat_score_rowsum = fn
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    nnz, heads = grad.shape
+    for t in (a, b, grad, out):
+        assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous() and t.shape[1] == heads
+    assert a.shape[0] == num_rows and out.shape[0] == num_rows and nnz == indices.numel()
+    if order is not None:
+        assert order.dtype == torch.int32 and order.is_contiguous() and order.numel() == nnz
+    assert workspace.numel() >= gat_score_workspace_bytes(num_rows, nnz, heads)
+    rc = ctypes.c_int(-1)
+    _gat_score_rowsum(indptr.data_ptr(), indices.data_ptr(), order.data_ptr() if order is not None else None, num_rows, nnz, heads,
+                      a.data_ptr(), b.data_ptr(), grad.data_ptr(), float(slope), out.data_ptr(), workspace.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_gat_score_rowsum_csr")
+
+
 def launch_scatter_values(values, slots, plane, stream) -> None:
     """``plane.view(-1)[slots[e]] = values[e]`` (device float32 values, int64 slots, fp32 / fp16 / bf16 plane); see
     include/voltrix_capi.h."""
@@ -868,6 +934,8 @@ launch_sddmm_heads_csr = _timed(launch_sddmm_heads_csr, "sddmm_heads_csr", 6)
 launch_edge_softmax_heads_csr = _timed(launch_edge_softmax_heads_csr, "edge_softmax_heads_csr", 6)
 launch_edge_softmax_heads_backward_csr = _timed(launch_edge_softmax_heads_backward_csr, "edge_softmax_heads_backward_csr", 7)
 launch_spmm_csr_heads = _timed(launch_spmm_csr_heads, "spmm_csr_heads", 6)
+launch_gat_score_csr = _timed(launch_gat_score_csr, "gat_score_csr", 7)
+launch_gat_score_rowsum_csr = _timed(launch_gat_score_rowsum_csr, "gat_score_rowsum_csr", 10)
 launch_spmm_f32_as_f16 = _timed(launch_spmm_f32_as_f16, "spmm_f32_as_f16", 9)
 launch_window_order = _timed(launch_window_order, "window_order", 3)
 launch_csr_window_count = _timed(launch_csr_window_count, "csr_window_count", 8)
