@@ -13,7 +13,11 @@ With ``heads`` > 1 the hidden layer is H heads of ``hidden / H`` features, conca
 the paper; the scalars become [n, H], the softmax runs on [nnz, H] and the aggregation is ``voltrix.autograd.SpMMHeads`` (one launch
 for all heads, no value planes).  ``heads`` = 1 is the single-head run, unchanged.
 
-    python examples/gat_train.py [workload] [hidden] [epochs] [heads]      # synthetic stand-in graph, random features and labels
+With a fifth argument ``v2`` the layers are GATv2 (Brody et al.): two linear maps, ``s_ij = a . LeakyReLU(W_l x_i + W_r x_j)`` per head
+through ``voltrix.autograd.GATv2Score`` (nothing of size [nnz, H, D] exists, forward or backward), and the aggregation runs on ``W_r x``
+through ``SpMMHeads`` (also with one head); score, softmax and aggregation share one transpose.  Without ``v2`` the run is unchanged.
+
+    python examples/gat_train.py [workload] [hidden] [epochs] [heads] [v2]   # synthetic stand-in graph, random features and labels
 """
 import os
 import sys
@@ -42,14 +46,18 @@ class Graph:
     the multi-head aggregation (the device CSR and its transpose; no handle), whose transpose the scores share.  ``rows`` / ``cols``
     (int64 row and column id of every edge) are built when something asks for them; the training run never does."""
 
-    def __init__(self, indptr, indices, n, hash_tag="example_gat", heads=1):
-        from voltrix.autograd import EdgeSoftmax, GATScore, SpMM, SpMMHeads
+    def __init__(self, indptr, indices, n, hash_tag="example_gat", heads=1, v2=False):
+        from voltrix.autograd import EdgeSoftmax, GATScore, GATv2Score, SpMM, SpMMHeads
 
-        self.n, self.heads = n, heads
+        self.n, self.heads, self.v2 = n, heads, v2
         self._indptr, self._indices = indptr, indices
         self._rows = self._cols = None
         self.softmax = EdgeSoftmax(indptr, n)
-        if heads > 1:
+        if v2:                  # GATv2: the multi-head aggregation for any number of heads; the scores share its transpose
+            self.aggregate = SpMMHeads(indptr, indices, n)
+            agg = self.aggregate
+            self.score = GATv2Score(indptr, indices, n, transposed=(agg.t_indptr, agg.t_indices, agg.t_order))
+        elif heads > 1:
             self.aggregate = SpMMHeads(indptr, indices, n)
             agg = self.aggregate
             self.score = GATScore(indptr, indices, n, transposed=(agg.t_indptr, agg.t_indices, agg.t_order))
@@ -105,9 +113,33 @@ class GATHeadsLayer(torch.nn.Module):
         return out.flatten(1) if self.concat else out.mean(1)
 
 
+class GATv2HeadsLayer(torch.nn.Module):
+    """GATv2: ``graph.heads`` heads of ``out_feats`` features each, two linear maps; concatenated or averaged like ``GATHeadsLayer``."""
+
+    def __init__(self, graph, in_feats, out_feats, concat, slope=0.2):
+        super().__init__()
+        self.graph, self.slope, self.concat, self.out_feats = graph, slope, concat, out_feats
+        self.wl = torch.nn.Linear(in_feats, graph.heads * out_feats, bias=False)
+        self.wr = torch.nn.Linear(in_feats, graph.heads * out_feats, bias=False)
+        self.a = torch.nn.Parameter(torch.randn(graph.heads, out_feats) / out_feats ** 0.5)
+
+    def forward(self, x):
+        g = self.graph
+        xl = self.wl(x).view(g.n, g.heads, self.out_feats).half()
+        xr = self.wr(x).view(g.n, g.heads, self.out_feats).half()
+        s = g.score(xl, xr, self.a, self.slope)               # [nnz, H] from fp16 rows; the gradients come back in fp16
+        out = g.aggregate(xr, g.softmax(s))                   # out [n, H, out_feats]
+        return out.flatten(1) if self.concat else out.mean(1)
+
+
 class GAT(torch.nn.Module):
     def __init__(self, graph, in_feats, hidden, classes):
         super().__init__()
+        if graph.v2:
+            assert hidden % graph.heads == 0, (hidden, graph.heads)
+            self.l1 = GATv2HeadsLayer(graph, in_feats, hidden // graph.heads, concat=True)
+            self.l2 = GATv2HeadsLayer(graph, hidden, classes, concat=False)
+            return
         if graph.heads > 1:
             assert hidden % graph.heads == 0, (hidden, graph.heads)
             self.l1 = GATHeadsLayer(graph, in_feats, hidden // graph.heads, concat=True)
@@ -127,11 +159,13 @@ def main():
     hidden = int(sys.argv[2]) if len(sys.argv) > 2 else 64
     epochs = int(sys.argv[3]) if len(sys.argv) > 3 else 10
     heads = int(sys.argv[4]) if len(sys.argv) > 4 else 1
+    v2 = len(sys.argv) > 5
+    assert not v2 or sys.argv[5] == "v2", sys.argv[5]
     indptr, indices, _ = synth_graphs.generate(workload, device="cuda")
     n = indptr.numel() - 1
     indptr, indices = with_self_loops(indptr, indices, n)
     t0 = time.perf_counter()
-    graph = Graph(indptr, indices, n, hash_tag=f"example_gat/{workload}", heads=heads)
+    graph = Graph(indptr, indices, n, hash_tag=f"example_gat/{workload}", heads=heads, v2=v2)
     torch.cuda.synchronize()
     print(f"{workload}: N={n} nnz={indices.numel()} (self loops added); operators built in {time.perf_counter() - t0:.2f} s")
     torch.manual_seed(0)
@@ -154,7 +188,7 @@ def main():
             print(f"epoch {epoch}: loss {float(loss):.4f}, {times[-1]:.2f} ms")
     steady = sorted(times[2:])[len(times[2:]) // 2] if len(times) > 2 else times[-1]
     print(f"steady epoch (forward + backward + Adam, full graph): {steady:.2f} ms -- two attention layers, hidden {hidden}"
-          + (f", {heads} heads" if heads > 1 else "") + f"; peak memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+          + (f", {heads} heads" if heads > 1 else "") + (", GATv2" if v2 else "") + f"; peak memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
 
 
 if __name__ == "__main__":

@@ -536,6 +536,35 @@ int64_t voltrix_gat_score_workspace_bytes(int num_rows, int64_t nnz, int heads);
 void voltrix_launch_gat_score_rowsum_csr(void* indptr, void* indices, void* order, int num_rows, int64_t nnz, int heads, void* a, void* b,
                                          void* grad, float slope, void* out, void* workspace, void* stream, int* return_code);
 
+/* GATv2 edge scores (gatv2_score_kernels.hpp): out[e, h] = sum_d a[h, d] * leaky(xl[row_e, h, d] + xr[indices[e], h, d]) for every
+ * entry e < nnz of a DEVICE CSR, leaky(z) = z > 0 ? z : float(slope) * z (z == 0 and NaN take the slope branch).  xl = device
+ * [num_rows, heads, head_dim], xr = device [*, heads, head_dim] (gathered by indices), one type for both: dtype 0 fp32 / 1 fp16 /
+ * 2 bfloat16, rows 16-byte aligned; a = device float[heads, head_dim], 16-byte aligned; out = device float[nnz, heads] in CSR order with
+ * the head index fastest, every element written (duplicate entries are edges of their own).  Per element one fp32 add, one product with
+ * slope on the slope branch and one fused multiply-add into the sum, in an order fixed by head_dim alone:
+ * |out - ref| <= (head_dim + 2) * 2^-23 * sum_d |a_d| |leaky(z_d)| + 2^-149 against float64 from the inputs as stored, and out[:, h]
+ * has the bits of the single-head call on the contiguous slices.  Nothing of size [nnz, heads, head_dim] exists.  One launch split by
+ * edges, no workspace, no host synchronisation, 64-bit element offsets.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: heads < 1, negative sizes, nnz > INT_MAX, heads * head_dim > INT_MAX, nnz > 0
+ * with num_rows == 0, head_dim not a multiple of 16 bytes of xr (8 for 16-bit, 4 for fp32), an unknown dtype, a non-finite slope, a
+ * null or misaligned pointer (4 bytes for indptr, indices, out; 16 for xl, xr, a); VOLTRIX_OK without a launch for nnz == 0 or
+ * head_dim == 0.  No reference counterpart (the reference is forward-only and has no edge values). */
+void voltrix_launch_gatv2_score_csr(void* indptr, void* indices, int num_rows, int64_t nnz, int heads, int head_dim, void* xl, void* xr,
+                                    int dtype, void* a, float slope, void* out, void* stream, int* return_code);
+
+/* The gated row sum of its backward: out[r, h, d] = sum_{e in row r} (p[r, h, d] + q[indices[e], h, d] > 0 ? g : float(slope) * g) with
+ * g = grad[order ? order[e] : e, h]; p, q as xl, xr above, grad = device float[nnz, heads], out = device float[num_rows, heads,
+ * head_dim], 16-byte aligned, every row written, empty rows 0.  G_l is this on the CSR with (p, q) = (xl, xr) and order = NULL; G_r is
+ * this on the transposed CSR (voltrix_launch_csr_transpose) with (p, q) = (xr, xl) and order = device int32[nnz], the entry of the CSR
+ * that entry e of the transpose is: fp32 addition commutes, so the gate is the forward's decision to the bit.  Then d_xl = a * G_l,
+ * d_xr = a * G_r and d_a = sum_r xl * G_l + sum_c xr * G_r are dense.  Every term is g or one rounded product, summed in CSR edge order:
+ * |out - ref| <= deg * 2^-23 * sum_e |term_e| + 2^-149 per element; a NaN in grad[e, h] reaches only out[row_e, h, :].  One launch, a
+ * row per lane group (a hub row serialises its wave, as in voltrix_launch_spmm_csr_heads), no workspace, no float atomics, no host
+ * synchronisation.  The checks above, and grad 4-byte, out 16-byte aligned; VOLTRIX_OK without a launch for num_rows == 0 or
+ * head_dim == 0; with nnz == 0 every row is zero-filled and indices, q, grad are not read. */
+void voltrix_launch_gatv2_rowsum_csr(void* indptr, void* indices, void* order, int num_rows, int64_t nnz, int heads, int head_dim, void* p,
+                                     void* q, int dtype, void* grad, float slope, void* out, void* stream, int* return_code);
+
 /* Rows of a dense row-major matrix times a per-row factor: dst[i, :] = T(float(src[i, :]) * scale[i]); dst may be src.
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,

@@ -18,6 +18,7 @@ from .weighted import update_values as update_edge_values
 from .sddmm import sddmm, spmm_heads
 from .edge_softmax import edge_softmax
 from .gat_score import gat_score
+from .gatv2_score import gatv2_score
 from .graphed import GraphedSpMM
 from . import autograd, hybrid, jit, sidecar, utils
 

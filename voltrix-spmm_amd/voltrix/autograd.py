@@ -29,6 +29,9 @@ operators make an attention layer: ``SpMM(...)(v, values=EdgeSoftmax(...)(SDDMM(
 
 GAT's scores are ``voltrix.autograd.GATScore(indptr, indices, n)(el, er, slope)``: ``leaky_relu(el[row] + er[col])`` per edge, with
 ``el.grad`` / ``er.grad`` as deterministic segment sums over the rows / the columns (``voltrix.gat_score``; [n] or [n, H] scalars).
+GATv2's are ``voltrix.autograd.GATv2Score(indptr, indices, n)(xl, xr, a, slope)``: ``sum_d a[h, d] leaky_relu(xl[row, h, d] + xr[col, h, d])``
+with ``xl.grad = a G_l``, ``xr.grad = a G_r``, ``a.grad = sum xl G_l + sum xr G_r`` from two gated row sums [n, H, D]
+(``voltrix.gatv2_score``); nothing of size [nnz, H, D] exists in either direction.
 
 Multi-head: ``SDDMM`` takes ``q, k`` [n, H, D] and gives scores [nnz, H], ``EdgeSoftmax`` takes [nnz, H], and ``SpMMHeads`` aggregates
 ``v`` [n, H, D] with weights [nnz, H] -- one launch per operator for all heads, the per-head bits of the single-head kernels:
@@ -296,6 +299,70 @@ class GATScore:
         assert el.dim() in (1, 2) and el.dim() == er.dim() and el.shape[1:] == er.shape[1:]
         assert el.shape[0] == self.num_rows and er.shape[0] == self.num_cols
         return _GATScoreFunction.apply(el, er, self, float(slope))
+
+
+class _GATv2ScoreFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xl, xr, a, op, slope):
+        from .gatv2_score import gatv2_score
+
+        ctx.op, ctx.slope = op, slope
+        ctx.save_for_backward(xl, xr, a)      # never s, never anything [nnz, H, D]
+        return gatv2_score(op.indptr, op.indices, xl, xr, a, slope)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .gatv2_score import gatv2_rowsum
+
+        op = ctx.op
+        xl, xr, a = (t.detach() for t in ctx.saved_tensors)
+        g = grad_out.float().contiguous()
+        need_l, need_r, need_a = ctx.needs_input_grad[:3]
+        grad_xl = grad_xr = grad_a = big_l = big_r = None
+        if need_l or need_a:                  # G_l: the gated sum over every row of the CSR
+            big_l = gatv2_rowsum(op.indptr, op.indices, xl, xr, g, ctx.slope)
+        if need_r or need_a:                  # G_r: over every column: the transposed CSR, g read through its edge order
+            big_r = gatv2_rowsum(op.t_indptr, op.t_indices, xr, xl, g, ctx.slope, order=op.t_order)
+        if need_l:
+            grad_xl = (a.float() * big_l).to(xl.dtype)
+        if need_r:
+            grad_xr = (a.float() * big_r).to(xr.dtype)
+        if need_a:                            # leaky_relu(z) = gate(z) z: two dense reductions over the nodes
+            grad_a = ((xl.float() * big_l).sum(0) + (xr.float() * big_r).sum(0)).to(a.dtype)
+        return grad_xl, grad_xr, grad_a, None, None
+
+
+class GATv2Score:
+    """GATv2's edge scores ``s[e, h] = sum_d a[h, d] leaky_relu(xl[row_e, h, d] + xr[col_e, h, d], slope)`` on a CSR pattern [num_rows,
+    num_cols] (``num_cols`` defaults to ``num_rows``), differentiable in ``xl``, ``xr`` and ``a``: the first step of
+    ``SpMMHeads(...)(xr, EdgeSoftmax(...)(GATv2Score(...)(xl, xr, a)))``.  ``xl`` [num_rows, H, D], ``xr`` [num_cols, H, D], ``a`` [H, D]
+    -> float32 [nnz, H]; the 2-D form ([n, D], [D] -> [nnz]) is one head.  Built once per pattern, exactly like ``GATScore``: the device
+    CSR, its transpose and the transposed edge order (kept as int32), or ``transposed=(t_indptr, t_indices, t_order)`` of an
+    ``SpMMHeads`` / ``SDDMM`` / ``GATScore`` of the same pattern.  Saves ``xl``, ``xr``, ``a`` only.  The backward is two gated row sums
+    (``voltrix.gatv2_score.gatv2_rowsum``) and dense torch products: ``xl.grad = a G_l``, ``xr.grad = a G_r``, ``a.grad = sum xl G_l +
+    sum xr G_r`` -- no index op, no float atomics, nothing of size [nnz, H, D]; gradients come back in the inputs' dtypes, and a side
+    nobody needs is skipped."""
+
+    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, num_rows: int, num_cols: int = None, transposed=None):
+        assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+        self.num_rows = num_rows
+        self.num_cols = num_rows if num_cols is None else int(num_cols)
+        self.num_edges = int(indices.numel())
+        self.indptr, self.indices = indptr.contiguous().cuda(), indices.contiguous().cuda()
+        if transposed is None:
+            from .weighted import transpose_order
+
+            t_indptr, t_indices = csr_transpose_device(self.indptr, self.indices, num_rows, self.num_cols)
+            t_order = transpose_order(self.indptr, self.indices, num_rows)
+        else:
+            t_indptr, t_indices, t_order = transposed
+            assert t_indptr.numel() == self.num_cols + 1 and t_indices.numel() == self.num_edges == t_order.numel()
+        self.t_indptr, self.t_indices, self.t_order = t_indptr, t_indices, t_order.to(torch.int32).contiguous()
+
+    def __call__(self, xl: torch.Tensor, xr: torch.Tensor, a: torch.Tensor, slope: float = 0.2) -> torch.Tensor:
+        assert xl.dim() in (2, 3) and xl.dim() == xr.dim() and xl.shape[1:] == xr.shape[1:] == a.shape
+        assert xl.shape[0] == self.num_rows and xr.shape[0] == self.num_cols
+        return _GATv2ScoreFunction.apply(xl, xr, a, self, float(slope))
 
 
 class SpMM:

@@ -83,6 +83,8 @@ SYMBOLS = (
     "voltrix_launch_gat_score_csr",
     "voltrix_gat_score_workspace_bytes",
     "voltrix_launch_gat_score_rowsum_csr",
+    "voltrix_launch_gatv2_score_csr",
+    "voltrix_launch_gatv2_rowsum_csr",
     "voltrix_csr_preprocess_workspace_bytes",
     "voltrix_launch_csr_window_count",
     "voltrix_launch_csr_fill",
@@ -857,6 +859,64 @@ def launch_gat_score_rowsum_csr(indptr, indices, order, num_rows: int, a, b, gra
     check(rc.value, "voltrix_launch_gat_score_rowsum_csr")
 
 
+# ---- GATv2 edge scores (csrc/capi_gatv2_score.hip): node tensors [n, H, D], a [H, D], edge tensors [nnz, H] with the head index fastest
+_gatv2_score = None
+_gatv2_rowsum = None
+
+
+def launch_gatv2_score_csr(indptr, indices, num_rows: int, xl, xr, a, slope: float, out, stream) -> None:
+    """``out[e, h] = sum_d a[h, d] * leaky_relu(xl[row_e, h, d] + xr[indices[e], h, d], slope)`` for every entry of a device int32 CSR
+    (voltrix/gatv2_score_kernels.hpp): ``xl`` [num_rows, H, D] and ``xr`` [*, H, D] of one type (fp32 / fp16 / bf16), D a multiple of
+    16 bytes; ``a`` float32 [H, D]; ``out`` float32 [nnz, H]; see include/voltrix_capi.h."""
+    import torch
+
+    global _gatv2_score
+    if _gatv2_score is None:
+        fn = lib().voltrix_launch_gatv2_score_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.POINTER(ctypes.c_int)]
+        _gatv2_score = fn
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    assert xl.dim() == 3 and xr.dim() == 3 and xl.is_contiguous() and xr.is_contiguous() and xl.shape[0] == num_rows
+    assert xl.shape[1:] == xr.shape[1:] and xl.dtype == xr.dtype
+    assert a.dtype == torch.float32 and a.is_contiguous() and a.shape == xl.shape[1:]
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (indices.numel(), xl.shape[1])
+    rc = ctypes.c_int(-1)
+    _gatv2_score(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), xl.shape[1], xl.shape[2], xl.data_ptr(), xr.data_ptr(),
+                 _dtype_code(xl.dtype), a.data_ptr(), float(slope), out.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_gatv2_score_csr")
+
+
+def launch_gatv2_rowsum_csr(indptr, indices, order, num_rows: int, p, q, grad, slope: float, out, stream) -> None:
+    """``out[r, h, d] = sum_{e in row r} gate(p[r, h, d] + q[indices[e], h, d]) grad[order[e] if order is not None else e, h]`` with
+    ``gate(z) = 1 if z > 0 else slope``: ``p`` [num_rows, H, D] and ``q`` [*, H, D] of one type, ``grad`` float32 [nnz, H], ``order``
+    None or int32 [nnz], ``out`` float32 [num_rows, H, D] (every row written); see include/voltrix_capi.h."""
+    import torch
+
+    global _gatv2_rowsum
+    if _gatv2_rowsum is None:
+        fn = lib().voltrix_launch_gatv2_rowsum_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.POINTER(ctypes.c_int)]
+        _gatv2_rowsum = fn
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    assert p.dim() == 3 and q.dim() == 3 and p.is_contiguous() and q.is_contiguous() and p.shape[0] == num_rows
+    assert p.shape[1:] == q.shape[1:] and p.dtype == q.dtype
+    nnz, heads = grad.shape
+    assert grad.dtype == torch.float32 and grad.is_contiguous() and nnz == indices.numel() and heads == p.shape[1]
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == p.shape
+    if order is not None:
+        assert order.dtype == torch.int32 and order.is_contiguous() and order.numel() == nnz
+    rc = ctypes.c_int(-1)
+    _gatv2_rowsum(indptr.data_ptr(), indices.data_ptr(), order.data_ptr() if order is not None else None, num_rows, nnz, heads,
+                  p.shape[2], p.data_ptr(), q.data_ptr(), _dtype_code(p.dtype), grad.data_ptr(), float(slope), out.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_gatv2_rowsum_csr")
+
+
 def launch_scatter_values(values, slots, plane, stream) -> None:
     """``plane.view(-1)[slots[e]] = values[e]`` (device float32 values, int64 slots, fp32 / fp16 / bf16 plane); see
     include/voltrix_capi.h."""
@@ -936,6 +996,8 @@ launch_edge_softmax_heads_backward_csr = _timed(launch_edge_softmax_heads_backwa
 launch_spmm_csr_heads = _timed(launch_spmm_csr_heads, "spmm_csr_heads", 6)
 launch_gat_score_csr = _timed(launch_gat_score_csr, "gat_score_csr", 7)
 launch_gat_score_rowsum_csr = _timed(launch_gat_score_rowsum_csr, "gat_score_rowsum_csr", 10)
+launch_gatv2_score_csr = _timed(launch_gatv2_score_csr, "gatv2_score_csr", 8)
+launch_gatv2_rowsum_csr = _timed(launch_gatv2_rowsum_csr, "gatv2_rowsum_csr", 9)
 launch_spmm_f32_as_f16 = _timed(launch_spmm_f32_as_f16, "spmm_f32_as_f16", 9)
 launch_window_order = _timed(launch_window_order, "window_order", 3)
 launch_csr_window_count = _timed(launch_csr_window_count, "csr_window_count", 8)
