@@ -424,7 +424,9 @@ void voltrix_launch_cast_f32_f16_scaled(void* src, void* dst, int64_t count, voi
  * `output` [num_rows, embedding_dim], every row written; exact products, fp32 sum in entry order.  No workspace, no tables.
  * xcd_ranges: 0 = consecutive row groups go round the XCDs (default), 1 = every XCD owns a contiguous eighth of the rows.  The
  * operator takes it for handles of short windows where it measured faster than the block-format kernels (fp32 features; wide
- * operands): voltrix/spmm/spmm.py.  No reference counterpart (the reference has the block format only). */
+ * operands): voltrix/spmm/spmm.py.  No reference counterpart (the reference has the block format only).
+ * Alignment: input and output 16 bytes -- rows are read and written 16 bytes per lane, anything else is VOLTRIX_ERR_BAD_SHAPE on the
+ * host, before any launch; indptr, indices (and values below) 4 bytes suffice: 4-byte loads. */
 void voltrix_launch_spmm_csr_rows(void* indptr, void* indices, int num_rows, int embedding_dim, void* input, int dtype, void* output,
                                   int xcd_ranges, void* stream, int* return_code);
 
@@ -450,7 +452,9 @@ void voltrix_launch_scatter_values(void* values, void* slots, void* plane, int64
  * embedding_dim alone: |out - ref| <= embedding_dim * 2^-23 (|x| |y|)[e], the same bits on every launch.  The gradient of a weighted
  * SpMM with respect to its edge values (dv = sddmm(dC, B)) and attention scores.  VOLTRIX_ERR_BAD_SHAPE: negative sizes, a bad width, an
  * unsupported pair, a null or misaligned pointer; VOLTRIX_OK without a launch for nnz == 0 or embedding_dim == 0.  No reference
- * counterpart (the reference is forward-only and has no edge values). */
+ * counterpart (the reference is forward-only and has no edge values).
+ * Alignment: x and y 16 bytes, anything else is VOLTRIX_ERR_BAD_SHAPE on the host, before any launch; indptr, indices and out 4 bytes
+ * suffice: 4-byte loads, and out is stored one float at a time, so nothing beyond out[nnz - 1] is written. */
 void voltrix_launch_sddmm_csr(void* indptr, void* indices, int num_rows, int64_t nnz, int embedding_dim, void* x, int x_dtype, void* y,
                               int y_dtype, void* out, void* stream, int* return_code);
 
@@ -464,7 +468,10 @@ void voltrix_launch_sddmm_csr(void* indptr, void* indices, int num_rows, int64_t
  * the pattern, the same bits on every launch.  Three kernel launches on `stream`, no host synchronisation; workspace: device, 16-byte
  * aligned, voltrix_edge_softmax_workspace_bytes(num_rows, nnz) bytes (a function of nnz alone), reused by the backward.
  * VOLTRIX_ERR_BAD_SHAPE: negative sizes, nnz > INT_MAX, a non-finite scale, a null or misaligned pointer; VOLTRIX_OK without a launch
- * for nnz == 0.  No reference counterpart (the reference is forward-only and has no edge values). */
+ * for nnz == 0.  No reference counterpart (the reference is forward-only and has no edge values).
+ * Alignment: indptr, scores and out 4 bytes suffice (the backward's alpha, grad_alpha and grad_scores likewise): a thread moves its 8
+ * edges with 16-byte loads / stores when the tensor's base allows and with 4-byte ones when it does not -- the same values, the same
+ * bits -- and never writes past out[nnz - 1]; workspace 16 bytes.  Anything less is VOLTRIX_ERR_BAD_SHAPE on the host, before any launch. */
 int64_t voltrix_edge_softmax_workspace_bytes(int num_rows, int64_t nnz);
 void voltrix_launch_edge_softmax_csr(void* indptr, int num_rows, int64_t nnz, void* scores, float scale, void* out, void* workspace,
                                      void* stream, int* return_code);
@@ -484,6 +491,9 @@ void voltrix_launch_edge_softmax_backward_csr(void* indptr, int num_rows, int64_
  * VOLTRIX_ERR_BAD_SHAPE from each, on the host and before any launch: heads < 1, negative sizes, head_dim not a multiple of 16 bytes of
  * the gathered operand (8 for 16-bit, 4 for fp32), a dtype or pair outside the single-head set, a null or misaligned pointer;
  * VOLTRIX_OK without a launch when there is nothing to do.  No reference counterpart.
+ * Alignment: the gathered node tensors (x, y; input) and the node-shaped output of voltrix_launch_spmm_csr_heads 16 bytes, required and
+ * rejected otherwise; every edge tensor (out of the product, scores / alpha / grad_alpha / out of the softmax, values), indptr and indices
+ * 4 bytes suffice: they are read and written one float at a time; the softmax's workspace 16 bytes.
  *
  * out[e, h] = sum_d x[row_e, h, d] * y[indices[e], h, d]; dtype pairs of voltrix_launch_sddmm_csr. */
 void voltrix_launch_sddmm_heads_csr(void* indptr, void* indices, int num_rows, int64_t nnz, int heads, int head_dim, void* x, int x_dtype,
@@ -516,7 +526,10 @@ void voltrix_launch_spmm_csr_heads(void* indptr, void* indices, void* values, in
  * per edge), no workspace, no host synchronisation, 64-bit element offsets.
  * VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: heads < 1 or > 65535, negative sizes, nnz > INT_MAX, nnz > 0 with
  * num_rows == 0, heads * num_rows > INT_MAX, a non-finite slope, a null or misaligned (4 bytes) pointer; VOLTRIX_OK without a launch
- * for nnz == 0.  No reference counterpart (the reference is forward-only and has no edge values). */
+ * for nnz == 0.  No reference counterpart (the reference is forward-only and has no edge values).
+ * Alignment: 4 bytes suffice for every pointer.  heads == 4 / 8 move 16 bytes per lane when el, er and out all sit on 16 bytes and take
+ * the any-heads kernel (4-byte accesses, the same two rounded operations per element: the same bits) when one does not; a thread reads
+ * its 8 column ids (and the row sum its 8 `order` entries) with two 16-byte loads when the array's base allows, else one by one. */
 void voltrix_launch_gat_score_csr(void* indptr, void* indices, int num_rows, int64_t nnz, int heads, void* el, void* er, float slope,
                                   void* out, void* stream, int* return_code);
 
@@ -531,7 +544,8 @@ void voltrix_launch_gat_score_csr(void* indptr, void* indices, int num_rows, int
  * NaN in grad[e, h] reaches only the one sum that holds it.  Three launches (zero fill, chunk sums, merge of the rows that cross a chunk
  * of 2048 edges), split by edges so a hub row costs what its edges cost; no host synchronisation.  workspace: device, 16-byte aligned,
  * voltrix_gat_score_workspace_bytes(num_rows, nnz, heads) bytes -- a function of (nnz, heads) alone, a multiple of 16, 0 for nnz == 0.
- * The checks of voltrix_launch_gat_score_csr; nnz == 0 zero-fills out (num_rows > 0 then needs a valid out) and is VOLTRIX_OK. */
+ * The checks of voltrix_launch_gat_score_csr -- 4 bytes suffice for indptr, indices, order, a, b, grad and out (one float at a time);
+ * workspace 16 bytes, required --; nnz == 0 zero-fills out (num_rows > 0 then needs a valid out) and is VOLTRIX_OK. */
 int64_t voltrix_gat_score_workspace_bytes(int num_rows, int64_t nnz, int heads);
 void voltrix_launch_gat_score_rowsum_csr(void* indptr, void* indices, void* order, int num_rows, int64_t nnz, int heads, void* a, void* b,
                                          void* grad, float slope, void* out, void* workspace, void* stream, int* return_code);
@@ -569,7 +583,8 @@ void voltrix_launch_gatv2_rowsum_csr(void* indptr, void* indices, void* order, i
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,
  * C's rows times r after -- the normalised adjacencies of GCN / mean aggregation); the reference has no edge values at all
- * (spmm_kernels.cuh:1632-1644: bits -> 1.0). */
+ * (spmm_kernels.cuh:1632-1644: bits -> 1.0).  Alignment: src and dst 16 bytes (16 bytes per lane; anything else is
+ * VOLTRIX_ERR_BAD_SHAPE on the host, before any launch), scale 4 bytes. */
 void voltrix_launch_scale_rows(void* src, void* scale, void* dst, int64_t rows, int num_feats, int dtype, void* stream,
                                int* return_code);
 

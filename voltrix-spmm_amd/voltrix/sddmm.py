@@ -13,6 +13,8 @@ from __future__ import annotations
 
 import torch
 
+from .utils import aligned16
+
 _PAIRS = {(torch.float32, torch.float16), (torch.float32, torch.bfloat16), (torch.float16, torch.float16),
           (torch.bfloat16, torch.bfloat16), (torch.float32, torch.float32)}
 _TYPES = (torch.float32, torch.float16, torch.bfloat16)
@@ -23,7 +25,7 @@ def _padded(t: torch.Tensor, width: int) -> torch.Tensor:
     t = t.contiguous()
     if width != t.shape[1]:
         t = torch.nn.functional.pad(t, (0, width - t.shape[1]))
-    return t.clone() if t.data_ptr() % 16 else t
+    return aligned16(t)
 
 
 def sddmm(indptr: torch.Tensor, indices: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
@@ -65,7 +67,7 @@ def _padded_heads(t: torch.Tensor, width: int) -> torch.Tensor:
     t = t.contiguous()
     if width != t.shape[2]:
         t = torch.nn.functional.pad(t, (0, width - t.shape[2]))
-    return t.clone() if t.data_ptr() % 16 else t
+    return aligned16(t)
 
 
 def _sddmm_heads(indptr: torch.Tensor, indices: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:

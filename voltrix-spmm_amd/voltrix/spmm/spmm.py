@@ -17,6 +17,7 @@ from ..jit_kernels import (
 )
 from .. import capi, hybrid, sidecar
 from ..project import CSR_PATH_FLAG, FP32_MODE_FLAG, PREPROCESS_FLAG
+from ..utils import aligned16
 
 BLK_H = 16
 BLK_W = 8
@@ -251,6 +252,7 @@ def _operand(feat: torch.Tensor, mode: str = None):
     padded = (num_feats + align - 1) // align * align
     if padded != num_feats:  # keep gathered rows 16-byte aligned
         feat = torch.nn.functional.pad(feat, (0, padded - num_feats))
+    feat = aligned16(feat)   # every kernel below reads 16 bytes at a time (a contiguous view at an odd offset: copied; else as it is)
     if exact or feat.dtype in (torch.float16, torch.bfloat16):
         return feat, None, padded, exact
     # fp32 -> fp16 with one power-of-two scale per call (undone in the kernel's epilogue): keeps fp32's range, which
@@ -334,7 +336,7 @@ def _spmm_csr(csr, feat: torch.Tensor) -> torch.Tensor:
     if padded != num_feats:
         feat = torch.nn.functional.pad(feat, (0, padded - num_feats))
     output = torch.empty((csr.num_rows, padded), dtype=torch.float32, device=feat.device)
-    capi.launch_spmm_csr_rows(csr.indptr, csr.indices, csr.num_rows, feat, output, _raw_stream(feat.device), 1)
+    capi.launch_spmm_csr_rows(csr.indptr, csr.indices, csr.num_rows, aligned16(feat), output, _raw_stream(feat.device), 1)
     return output if padded == num_feats else output[:, :num_feats].contiguous()
 
 

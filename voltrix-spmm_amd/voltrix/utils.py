@@ -18,6 +18,14 @@ import time
 import torch
 
 
+def aligned16(t: torch.Tensor) -> torch.Tensor:
+    """``t`` (contiguous) with its first byte on a 16-byte boundary: ``t`` ITSELF when it already is -- an aligned operand is never
+    copied --, else a fresh copy (the allocator's blocks are aligned far beyond 16 bytes).  The kernels that read rows 16 bytes at a
+    time reject any other base pointer on the host (return code 1, include/voltrix_capi.h); contiguous views at an odd element offset --
+    a slice of ``torch.cat``'s gradient, a parameter inside a flat buffer -- reach the Python layer all the time."""
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 def relative_error(value: torch.Tensor, real: torch.Tensor, exclude_zeros: bool = True) -> float:
     value = value.double().flatten()
     real = real.double().flatten()

@@ -21,6 +21,7 @@ import dataclasses
 import torch
 
 from .jit_kernels import csr_fused_preprocess_kernel, spmm_kernel
+from .utils import aligned16
 
 
 # A value plane is 512 B per TC block in fp32 (the master the 16-bit planes are rounded from) and 256 B in a 16-bit type.  Above
@@ -391,7 +392,7 @@ def _spmm_weighted_csr(handle: WeightedHandle, feat: torch.Tensor) -> torch.Tens
     if padded != num_feats:
         feat = torch.nn.functional.pad(feat, (0, padded - num_feats))
     output = torch.empty((handle.num_nodes, padded), dtype=torch.float32, device=feat.device)
-    capi.launch_spmm_csr_rows(indptr, indices, handle.num_nodes, feat, output, _raw_stream(feat.device), 1, values=values)
+    capi.launch_spmm_csr_rows(indptr, indices, handle.num_nodes, aligned16(feat), output, _raw_stream(feat.device), 1, values=values)
     return output if padded == num_feats else output[:, :num_feats].contiguous()
 
 
@@ -485,6 +486,7 @@ def _spmm_separable(handle: WeightedHandle, feat: torch.Tensor, prescaled: bool 
     padded = (num_feats + align - 1) // align * align
     if padded != num_feats:
         feat = torch.nn.functional.pad(feat, (0, padded - num_feats))
+    feat = aligned16(feat)
     stream = _raw_stream(feat.device)
     scaled = feat
     if not prescaled:
@@ -510,8 +512,7 @@ def scale_rows_of(feat: torch.Tensor, scale: torch.Tensor, in_place: bool = Fals
     src = feat.contiguous()
     if padded != num_feats:
         src = torch.nn.functional.pad(src, (0, padded - num_feats))
-    if src.data_ptr() % 16:
-        src = src.clone()
+    src = aligned16(src)
     dst = src if (in_place or src is not feat) else torch.empty_like(src)
     capi.launch_scale_rows(src, scale.contiguous(), dst, _raw_stream(feat.device))
     return dst if padded == num_feats else dst[:, :num_feats].contiguous()
