@@ -17,7 +17,11 @@ With a fifth argument ``v2`` the layers are GATv2 (Brody et al.): two linear map
 through ``voltrix.autograd.GATv2Score`` (nothing of size [nnz, H, D] exists, forward or backward), and the aggregation runs on ``W_r x``
 through ``SpMMHeads`` (also with one head); score, softmax and aggregation share one transpose.  Without ``v2`` the run is unchanged.
 
-    python examples/gat_train.py [workload] [hidden] [epochs] [heads] [v2]   # synthetic stand-in graph, random features and labels
+With a trailing argument ``fused`` the multi-head and the ``v2`` layers replace ``softmax`` plus ``aggregate`` by
+``voltrix.autograd.AttnAggregate``: one launch forward, the attention weights [nnz, H] are never stored and their gradient never exists.
+Without ``fused`` every run is unchanged.
+
+    python examples/gat_train.py [workload] [hidden] [epochs] [heads] [v2] [fused]   # synthetic stand-in graph, random features and labels
 """
 import os
 import sys
@@ -46,9 +50,10 @@ class Graph:
     the multi-head aggregation (the device CSR and its transpose; no handle), whose transpose the scores share.  ``rows`` / ``cols``
     (int64 row and column id of every edge) are built when something asks for them; the training run never does."""
 
-    def __init__(self, indptr, indices, n, hash_tag="example_gat", heads=1, v2=False):
-        from voltrix.autograd import EdgeSoftmax, GATScore, GATv2Score, SpMM, SpMMHeads
+    def __init__(self, indptr, indices, n, hash_tag="example_gat", heads=1, v2=False, fused=False):
+        from voltrix.autograd import AttnAggregate, EdgeSoftmax, GATScore, GATv2Score, SpMM, SpMMHeads
 
+        assert not fused or v2 or heads > 1, "fused: the multi-head and the v2 layers"
         self.n, self.heads, self.v2 = n, heads, v2
         self._indptr, self._indices = indptr, indices
         self._rows = self._cols = None
@@ -64,6 +69,16 @@ class Graph:
         else:
             self.aggregate = SpMM(indptr, indices, n, values=torch.ones(indices.numel(), device="cuda"), hash_tag=hash_tag)
             self.score = GATScore(indptr, indices, n)
+        self.fused = None
+        if fused:               # softmax and aggregation in one operator, on the transpose the others share
+            agg = self.aggregate
+            self.fused = AttnAggregate(indptr, indices, n, transposed=(agg.t_indptr, agg.t_indices, agg.t_order))
+
+    def attend(self, feat, s):
+        """``aggregate(feat, softmax(s))``: scores [nnz, H], out [n, H, out_feats]; one operator with ``fused``."""
+        if self.fused is not None:
+            return self.fused(feat, s)
+        return self.aggregate(feat, self.softmax(s))
 
     @property
     def rows(self):
@@ -109,7 +124,7 @@ class GATHeadsLayer(torch.nn.Module):
         g = self.graph
         wh = self.w(x).view(g.n, g.heads, self.out_feats)
         s = g.score((wh * self.a_l).sum(-1), (wh * self.a_r).sum(-1), self.slope)
-        out = g.aggregate(wh.half(), g.softmax(s))            # scores, weights [nnz, H]; out [n, H, out_feats]
+        out = g.attend(wh.half(), s)                          # scores, weights [nnz, H]; out [n, H, out_feats]
         return out.flatten(1) if self.concat else out.mean(1)
 
 
@@ -128,7 +143,7 @@ class GATv2HeadsLayer(torch.nn.Module):
         xl = self.wl(x).view(g.n, g.heads, self.out_feats).half()
         xr = self.wr(x).view(g.n, g.heads, self.out_feats).half()
         s = g.score(xl, xr, self.a, self.slope)               # [nnz, H] from fp16 rows; the gradients come back in fp16
-        out = g.aggregate(xr, g.softmax(s))                   # out [n, H, out_feats]
+        out = g.attend(xr, s)                                 # out [n, H, out_feats]
         return out.flatten(1) if self.concat else out.mean(1)
 
 
@@ -159,13 +174,14 @@ def main():
     hidden = int(sys.argv[2]) if len(sys.argv) > 2 else 64
     epochs = int(sys.argv[3]) if len(sys.argv) > 3 else 10
     heads = int(sys.argv[4]) if len(sys.argv) > 4 else 1
-    v2 = len(sys.argv) > 5
-    assert not v2 or sys.argv[5] == "v2", sys.argv[5]
+    flags = sys.argv[5:]
+    assert flags in ([], ["v2"], ["fused"], ["v2", "fused"]), flags
+    v2, fused = "v2" in flags, "fused" in flags
     indptr, indices, _ = synth_graphs.generate(workload, device="cuda")
     n = indptr.numel() - 1
     indptr, indices = with_self_loops(indptr, indices, n)
     t0 = time.perf_counter()
-    graph = Graph(indptr, indices, n, hash_tag=f"example_gat/{workload}", heads=heads, v2=v2)
+    graph = Graph(indptr, indices, n, hash_tag=f"example_gat/{workload}", heads=heads, v2=v2, fused=fused)
     torch.cuda.synchronize()
     print(f"{workload}: N={n} nnz={indices.numel()} (self loops added); operators built in {time.perf_counter() - t0:.2f} s")
     torch.manual_seed(0)
@@ -188,7 +204,7 @@ def main():
             print(f"epoch {epoch}: loss {float(loss):.4f}, {times[-1]:.2f} ms")
     steady = sorted(times[2:])[len(times[2:]) // 2] if len(times) > 2 else times[-1]
     print(f"steady epoch (forward + backward + Adam, full graph): {steady:.2f} ms -- two attention layers, hidden {hidden}"
-          + (f", {heads} heads" if heads > 1 else "") + (", GATv2" if v2 else "") + f"; peak memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+          + (f", {heads} heads" if heads > 1 else "") + (", GATv2" if v2 else "") + (", fused" if fused else "") + f"; peak memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
 
 
 if __name__ == "__main__":

@@ -579,6 +579,49 @@ void voltrix_launch_gatv2_score_csr(void* indptr, void* indices, int num_rows, i
 void voltrix_launch_gatv2_rowsum_csr(void* indptr, void* indices, void* order, int num_rows, int64_t nnz, int heads, int head_dim, void* p,
                                      void* q, int dtype, void* grad, float slope, void* out, void* stream, int* return_code);
 
+/* Edge softmax and multi-head aggregation in one launch (attn_aggregate_kernels.hpp):
+ * out[r, h, :] = sum_{e in row r} alpha[e, h] * feat[indices[e], h, :] with alpha the softmax of scale * scores[:, h] over every row of a
+ * DEVICE CSR, never stored.  scores = device float[nnz, heads] in CSR order with the head index fastest; feat = device
+ * [*, heads, head_dim], dtype 0 fp32 / 1 fp16 / 2 bfloat16; out = device float[num_rows, heads, head_dim]; m, l = device
+ * float[num_rows, heads]: m = the row maximum of sign(scale) * scores (-inf for a row without entries), l = sum exp(|scale| *
+ * (sign(scale) * scores - m)).  Every element of out, m and l is written; rows without entries and rows or heads whose scores are all
+ * -inf give zeros and l = 0; a NaN or +inf score stays in its own row and head; scale = 0 is the mean over the entries that are not
+ * -inf; the special values of voltrix_launch_spmm_csr_heads on voltrix_launch_edge_softmax_heads_csr.  Per row two passes (the maximum,
+ * then fused multiply-adds of exp(.) * feat and the sum l in CSR edge order) and one reciprocal:
+ * |out - ref| <= 2 (deg + 3) 2^-23 sum_e alpha_e |feat_e| + 2^-23 sum_e |feat_e| / l + 2^-126; out[:, h], m[:, h], l[:, h] have the bits
+ * of the heads == 1 call on the contiguous slices.  One launch, a row per lane group (a hub row serialises its wave, twice), no
+ * workspace, no float atomics, no host synchronisation.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: heads < 1, negative sizes, nnz > INT_MAX, heads * head_dim > INT_MAX, nnz > 0
+ * with num_rows == 0, head_dim not a multiple of 16 bytes of feat (8 for 16-bit, 4 for fp32), an unknown dtype, a non-finite scale, a
+ * null or misaligned pointer; VOLTRIX_OK without a launch for num_rows == 0 or head_dim == 0; with nnz == 0 out and l are zero-filled
+ * (m: -inf) and indices, scores, feat are not read.
+ * Alignment: indptr, indices, scores, m, l 4 bytes; feat and out 16 bytes (16 bytes per lane). */
+void voltrix_launch_attn_aggregate_csr(void* indptr, void* indices, void* scores, int num_rows, int64_t nnz, int heads, int head_dim,
+                                       void* feat, int dtype, float scale, void* out, void* m, void* l, void* stream, int* return_code);
+
+/* Its gradient for the scores: grad_scores[e, h] = scale * alpha[e, h] * (<grad_out[row_e, h], feat[indices[e], h]> - delta[row_e, h]),
+ * alpha recomputed from scores, m and l of the forward; delta[r, h] = <grad_out[r, h], out[r, h]> is the caller's dense product (device
+ * float[num_rows, heads]).  grad_out = device float[num_rows, heads, head_dim]; feat, dtype as above; grad_scores = device
+ * float[nnz, heads], every element written; a row or head with l == 0 gives 0.  One launch split by edges (a hub row costs what its
+ * edges cost), fp32 fused multiply-adds in column order and a fixed butterfly, grad_scores[:, h] has the bits of the heads == 1 call.  The
+ * checks above; VOLTRIX_OK without a launch for nnz == 0 or head_dim == 0.
+ * Alignment: indptr, indices, scores, m, l, delta, grad_scores 4 bytes; grad_out and feat 16 bytes. */
+void voltrix_launch_attn_aggregate_grad_scores_csr(void* indptr, void* indices, int num_rows, int64_t nnz, int heads, int head_dim,
+                                                   void* grad_out, void* feat, int dtype, void* scores, void* m, void* l, void* delta,
+                                                   float scale, void* grad_scores, void* stream, int* return_code);
+
+/* Its gradient for feat, on the TRANSPOSED CSR (voltrix_launch_csr_transpose; num_cols rows):
+ * grad_feat[c, h, :] = sum_{e in row c} alpha[order[e], h] * grad_out[t_indices[e], h, :], order = device int32[nnz], the entry of the CSR
+ * that entry e of the transpose is; scores stays in CSR order and grad_out is never permuted; m, l = the forward's, indexed by
+ * t_indices.  grad_out = device [*, heads, head_dim] of dtype 0 fp32 / 1 fp16 / 2 bfloat16 (head_dim a multiple of 16 bytes of it);
+ * grad_feat = device float[num_cols, heads, head_dim], every row written, rows without entries zero.  One fused multiply-add per element
+ * in the transposed CSR's edge order; a row per lane group (a hub column serialises its wave).  The checks above; VOLTRIX_OK without a
+ * launch for num_cols == 0 or head_dim == 0; with nnz == 0 grad_feat is zero-filled and nothing but t_indptr is read.
+ * Alignment: t_indptr, t_indices, order, scores, m, l 4 bytes; grad_out and grad_feat 16 bytes. */
+void voltrix_launch_attn_aggregate_grad_feat_csr(void* t_indptr, void* t_indices, void* order, int num_cols, int64_t nnz, int heads,
+                                                 int head_dim, void* grad_out, int dtype, void* scores, void* m, void* l, float scale,
+                                                 void* grad_feat, void* stream, int* return_code);
+
 /* Rows of a dense row-major matrix times a per-row factor: dst[i, :] = T(float(src[i, :]) * scale[i]); dst may be src.
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,

@@ -19,6 +19,7 @@ from .sddmm import sddmm, spmm_heads
 from .edge_softmax import edge_softmax
 from .gat_score import gat_score
 from .gatv2_score import gatv2_score
+from .attn_aggregate import attn_aggregate
 from .graphed import GraphedSpMM
 from . import autograd, hybrid, jit, sidecar, utils
 

@@ -38,6 +38,10 @@ Multi-head: ``SDDMM`` takes ``q, k`` [n, H, D] and gives scores [nnz, H], ``Edge
 
     alpha = EdgeSoftmax(indptr, n)(SDDMM(indptr, indices, n)(q, k), d ** -0.5)       # [nnz, H]
     out = voltrix.autograd.SpMMHeads(indptr, indices, n)(v, alpha)                   # float32 [n, H, D]
+
+``AttnAggregate`` is the last two steps in one operator, ``AttnAggregate(indptr, indices, n)(v, s, scale)`` ==
+``SpMMHeads(...)(v, EdgeSoftmax(...)(s, scale))``: one launch forward, ``alpha`` recomputed in the backward from two numbers per row
+and head instead of being stored (``voltrix.attn_aggregate``).
 """
 from __future__ import annotations
 
@@ -363,6 +367,67 @@ class GATv2Score:
         assert xl.dim() in (2, 3) and xl.dim() == xr.dim() and xl.shape[1:] == xr.shape[1:] == a.shape
         assert xl.shape[0] == self.num_rows and xr.shape[0] == self.num_cols
         return _GATv2ScoreFunction.apply(xl, xr, a, self, float(slope))
+
+
+class _AttnAggregateFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, scores, op, scale):
+        from .attn_aggregate import attn_aggregate
+
+        out, m, l = attn_aggregate(op.indptr, op.indices, scores, feat, op.num_rows, scale, return_stats=True)
+        ctx.op, ctx.scale = op, scale
+        ctx.save_for_backward(feat, scores, out, m, l)      # never alpha
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .attn_aggregate import attn_aggregate_grad_feat, attn_aggregate_grad_scores
+
+        op = ctx.op
+        feat, scores, out, m, l = (t.detach() for t in ctx.saved_tensors)
+        grad_out = grad_out.float().contiguous()
+        grad_feat = grad_scores = None
+        if ctx.needs_input_grad[0]:           # the transposed CSR, alpha recomputed through its edge order; dC is not permuted
+            grad_feat = attn_aggregate_grad_feat(op.t_indptr, op.t_indices, op.t_order, grad_out, scores, m, l, op.num_cols,
+                                                 ctx.scale).to(feat.dtype)
+        if ctx.needs_input_grad[1]:           # the softmax backward's row sum is the dense product <dC, out>
+            delta = (grad_out * out).sum(-1)
+            grad_scores = attn_aggregate_grad_scores(op.indptr, op.indices, grad_out, feat, scores, m, l, delta,
+                                                     ctx.scale).to(scores.dtype)
+        return grad_feat, grad_scores, None, None
+
+
+class AttnAggregate:
+    """``out[r, h] = sum_{e in row r} softmax(scale * scores)[e, h] feat[col_e, h]`` on a CSR pattern [num_rows, num_cols] (``num_cols``
+    defaults to ``num_rows``) in one launch (``voltrix.attn_aggregate``), differentiable in ``feat`` [num_cols, H, D] and ``scores``
+    [nnz, H]: ``SpMMHeads(...)(feat, EdgeSoftmax(...)(scores, scale))`` without the attention weights ever being stored.  The 2-D form
+    (``feat`` [num_cols, D], ``scores`` [nnz]) is one head.  Built once per pattern, exactly like ``GATScore``: the device CSR, its
+    transpose and the transposed edge order (kept as int32), or ``transposed=(t_indptr, t_indices, t_order)`` of an ``SpMMHeads`` /
+    ``SDDMM`` / ``GATScore`` of the same pattern.  Saves ``feat``, ``scores``, ``out`` and the row statistics ``m``, ``l`` [num_rows, H].
+    The backward is ``delta = (dC * out).sum(-1)`` (dense torch), one launch split by edges for ``scores.grad`` and one on the transposed
+    CSR for ``feat.grad`` (``voltrix.attn_aggregate.attn_aggregate_grad_scores`` / ``attn_aggregate_grad_feat``): no index op, no float
+    atomics, no [nnz, H] tensor but ``scores.grad``; gradients come back in the inputs' dtypes, and a side nobody needs is skipped."""
+
+    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, num_rows: int, num_cols: int = None, transposed=None):
+        assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+        self.num_rows = num_rows
+        self.num_cols = num_rows if num_cols is None else int(num_cols)
+        self.num_edges = int(indices.numel())
+        self.indptr, self.indices = indptr.contiguous().cuda(), indices.contiguous().cuda()
+        if transposed is None:
+            from .weighted import transpose_order
+
+            t_indptr, t_indices = csr_transpose_device(self.indptr, self.indices, num_rows, self.num_cols)
+            t_order = transpose_order(self.indptr, self.indices, num_rows)
+        else:
+            t_indptr, t_indices, t_order = transposed
+            assert t_indptr.numel() == self.num_cols + 1 and t_indices.numel() == self.num_edges == t_order.numel()
+        self.t_indptr, self.t_indices, self.t_order = t_indptr, t_indices, t_order.to(torch.int32).contiguous()
+
+    def __call__(self, feat: torch.Tensor, scores: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+        assert feat.dim() in (2, 3) and scores.dim() == feat.dim() - 1 and feat.shape[0] == self.num_cols
+        assert scores.shape[0] == self.num_edges and scores.shape[1:] == feat.shape[1:-1], (tuple(scores.shape), tuple(feat.shape))
+        return _AttnAggregateFunction.apply(feat, scores, self, float(scale))
 
 
 class SpMM:

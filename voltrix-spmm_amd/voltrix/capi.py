@@ -85,6 +85,9 @@ SYMBOLS = (
     "voltrix_launch_gat_score_rowsum_csr",
     "voltrix_launch_gatv2_score_csr",
     "voltrix_launch_gatv2_rowsum_csr",
+    "voltrix_launch_attn_aggregate_csr",
+    "voltrix_launch_attn_aggregate_grad_scores_csr",
+    "voltrix_launch_attn_aggregate_grad_feat_csr",
     "voltrix_csr_preprocess_workspace_bytes",
     "voltrix_launch_csr_window_count",
     "voltrix_launch_csr_fill",
@@ -917,6 +920,100 @@ def launch_gatv2_rowsum_csr(indptr, indices, order, num_rows: int, p, q, grad, s
     check(rc.value, "voltrix_launch_gatv2_rowsum_csr")
 
 
+# ---- edge softmax + aggregation in one launch (csrc/capi_attn_aggregate.hip): scores [nnz, H], feat [n, H, D], row statistics [n, H]
+_attn_aggregate = None
+_attn_aggregate_grad_scores = None
+_attn_aggregate_grad_feat = None
+
+
+def launch_attn_aggregate_csr(indptr, indices, scores, num_rows: int, feat, scale: float, out, m, l, stream) -> None:
+    """``out[r, h] = sum_{e in row r} softmax(scale * scores)[e, h] * feat[indices[e], h]`` with the row statistics ``m``, ``l``
+    (voltrix/attn_aggregate_kernels.hpp): device int32 CSR, ``scores`` float32 [nnz, H], fp32 / fp16 / bf16 ``feat`` [*, H, D] with D a
+    multiple of 16 bytes, fp32 ``out`` [num_rows, H, D], fp32 ``m`` and ``l`` [num_rows, H]; see include/voltrix_capi.h."""
+    import torch
+
+    global _attn_aggregate
+    if _attn_aggregate is None:
+        fn = lib().voltrix_launch_attn_aggregate_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                       ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.POINTER(ctypes.c_int)]
+        _attn_aggregate = fn
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    assert feat.dim() == 3 and feat.is_contiguous() and out.is_contiguous() and out.dtype == torch.float32
+    heads = feat.shape[1]
+    assert out.shape == (num_rows,) + tuple(feat.shape[1:])
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.shape == (indices.numel(), heads)
+    for t in (m, l):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (num_rows, heads)
+    rc = ctypes.c_int(-1)
+    _attn_aggregate(indptr.data_ptr(), indices.data_ptr(), scores.data_ptr(), num_rows, indices.numel(), heads, feat.shape[2],
+                    feat.data_ptr(), _dtype_code(feat.dtype), float(scale), out.data_ptr(), m.data_ptr(), l.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_attn_aggregate_csr")
+
+
+def launch_attn_aggregate_grad_scores_csr(indptr, indices, num_rows: int, grad_out, feat, scores, m, l, delta, scale: float, out,
+                                          stream) -> None:
+    """``out[e, h] = scale * alpha[e, h] * (<grad_out[row_e, h], feat[indices[e], h]> - delta[row_e, h])`` with ``alpha`` recomputed from
+    ``scores``, ``m``, ``l``: fp32 ``grad_out`` [num_rows, H, D], ``feat`` [*, H, D], fp32 ``scores`` and ``out`` [nnz, H], fp32 ``m``,
+    ``l``, ``delta`` [num_rows, H]; see include/voltrix_capi.h."""
+    import torch
+
+    global _attn_aggregate_grad_scores
+    if _attn_aggregate_grad_scores is None:
+        fn = lib().voltrix_launch_attn_aggregate_grad_scores_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        _attn_aggregate_grad_scores = fn
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    assert grad_out.dim() == 3 and feat.dim() == 3 and grad_out.is_contiguous() and feat.is_contiguous()
+    assert grad_out.dtype == torch.float32 and grad_out.shape[0] == num_rows and grad_out.shape[1:] == feat.shape[1:]
+    nnz, heads = indices.numel(), feat.shape[1]
+    for t in (scores, out):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (nnz, heads)
+    for t in (m, l, delta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (num_rows, heads)
+    rc = ctypes.c_int(-1)
+    _attn_aggregate_grad_scores(indptr.data_ptr(), indices.data_ptr(), num_rows, nnz, heads, feat.shape[2], grad_out.data_ptr(),
+                                feat.data_ptr(), _dtype_code(feat.dtype), scores.data_ptr(), m.data_ptr(), l.data_ptr(), delta.data_ptr(),
+                                float(scale), out.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_attn_aggregate_grad_scores_csr")
+
+
+def launch_attn_aggregate_grad_feat_csr(t_indptr, t_indices, order, num_cols: int, grad_out, scores, m, l, scale: float, out,
+                                        stream) -> None:
+    """``out[c, h] = sum_{e in row c of the transposed CSR} alpha[order[e], h] * grad_out[t_indices[e], h]`` with ``alpha`` recomputed
+    from ``scores`` (CSR order), ``m``, ``l``: int32 ``order`` [nnz], fp32 / fp16 / bf16 ``grad_out`` [num_rows, H, D], fp32 ``out``
+    [num_cols, H, D]; see include/voltrix_capi.h."""
+    import torch
+
+    global _attn_aggregate_grad_feat
+    if _attn_aggregate_grad_feat is None:
+        fn = lib().voltrix_launch_attn_aggregate_grad_feat_csr
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        _attn_aggregate_grad_feat = fn
+    assert t_indptr.dtype == torch.int32 and t_indices.dtype == torch.int32 and t_indptr.numel() == num_cols + 1
+    assert t_indptr.is_contiguous() and t_indices.is_contiguous()
+    nnz = t_indices.numel()
+    assert order.dtype == torch.int32 and order.is_contiguous() and order.numel() == nnz
+    assert grad_out.dim() == 3 and grad_out.is_contiguous() and out.is_contiguous() and out.dtype == torch.float32
+    heads = grad_out.shape[1]
+    assert out.shape == (num_cols,) + tuple(grad_out.shape[1:])
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.shape == (nnz, heads)
+    for t in (m, l):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (grad_out.shape[0], heads)
+    rc = ctypes.c_int(-1)
+    _attn_aggregate_grad_feat(t_indptr.data_ptr(), t_indices.data_ptr(), order.data_ptr(), num_cols, nnz, heads, grad_out.shape[2],
+                              grad_out.data_ptr(), _dtype_code(grad_out.dtype), scores.data_ptr(), m.data_ptr(), l.data_ptr(),
+                              float(scale), out.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_attn_aggregate_grad_feat_csr")
+
+
 def launch_scatter_values(values, slots, plane, stream) -> None:
     """``plane.view(-1)[slots[e]] = values[e]`` (device float32 values, int64 slots, fp32 / fp16 / bf16 plane); see
     include/voltrix_capi.h."""
@@ -998,6 +1095,9 @@ launch_gat_score_csr = _timed(launch_gat_score_csr, "gat_score_csr", 7)
 launch_gat_score_rowsum_csr = _timed(launch_gat_score_rowsum_csr, "gat_score_rowsum_csr", 10)
 launch_gatv2_score_csr = _timed(launch_gatv2_score_csr, "gatv2_score_csr", 8)
 launch_gatv2_rowsum_csr = _timed(launch_gatv2_rowsum_csr, "gatv2_rowsum_csr", 9)
+launch_attn_aggregate_csr = _timed(launch_attn_aggregate_csr, "attn_aggregate_csr", 9)
+launch_attn_aggregate_grad_scores_csr = _timed(launch_attn_aggregate_grad_scores_csr, "attn_aggregate_grad_scores_csr", 11)
+launch_attn_aggregate_grad_feat_csr = _timed(launch_attn_aggregate_grad_feat_csr, "attn_aggregate_grad_feat_csr", 10)
 launch_spmm_f32_as_f16 = _timed(launch_spmm_f32_as_f16, "spmm_f32_as_f16", 9)
 launch_window_order = _timed(launch_window_order, "window_order", 3)
 launch_csr_window_count = _timed(launch_csr_window_count, "csr_window_count", 8)
