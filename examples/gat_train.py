@@ -47,32 +47,24 @@ def with_self_loops(indptr, indices, n):
 
 class Graph:
     """What both layers share: the edge scores, the edge softmax and the aggregation operator (built once: A and A^T).  ``heads`` > 1:
-    the multi-head aggregation (the device CSR and its transpose; no handle), whose transpose the scores share.  ``rows`` / ``cols``
+    the multi-head aggregation (no handle); every operator but the block-format ``SpMM`` shares one ``CsrPattern``.  ``rows`` / ``cols``
     (int64 row and column id of every edge) are built when something asks for them; the training run never does."""
 
     def __init__(self, indptr, indices, n, hash_tag="example_gat", heads=1, v2=False, fused=False):
-        from voltrix.autograd import AttnAggregate, EdgeSoftmax, GATScore, GATv2Score, SpMM, SpMMHeads
+        from voltrix.autograd import AttnAggregate, CsrPattern, EdgeSoftmax, GATScore, GATv2Score, SpMM, SpMMHeads
 
         assert not fused or v2 or heads > 1, "fused: the multi-head and the v2 layers"
         self.n, self.heads, self.v2 = n, heads, v2
         self._indptr, self._indices = indptr, indices
         self._rows = self._cols = None
-        self.softmax = EdgeSoftmax(indptr, n)
-        if v2:                  # GATv2: the multi-head aggregation for any number of heads; the scores share its transpose
-            self.aggregate = SpMMHeads(indptr, indices, n)
-            agg = self.aggregate
-            self.score = GATv2Score(indptr, indices, n, transposed=(agg.t_indptr, agg.t_indices, agg.t_order))
-        elif heads > 1:
-            self.aggregate = SpMMHeads(indptr, indices, n)
-            agg = self.aggregate
-            self.score = GATScore(indptr, indices, n, transposed=(agg.t_indptr, agg.t_indices, agg.t_order))
+        pattern = CsrPattern(indptr, indices, n)      # the device CSR and its transpose, once for every operator below
+        self.softmax = EdgeSoftmax(pattern)
+        self.score = GATv2Score(pattern) if v2 else GATScore(pattern)
+        if v2 or heads > 1:     # GATv2: the multi-head aggregation for any number of heads
+            self.aggregate = SpMMHeads(pattern)
         else:
             self.aggregate = SpMM(indptr, indices, n, values=torch.ones(indices.numel(), device="cuda"), hash_tag=hash_tag)
-            self.score = GATScore(indptr, indices, n)
-        self.fused = None
-        if fused:               # softmax and aggregation in one operator, on the transpose the others share
-            agg = self.aggregate
-            self.fused = AttnAggregate(indptr, indices, n, transposed=(agg.t_indptr, agg.t_indices, agg.t_order))
+        self.fused = AttnAggregate(pattern) if fused else None      # softmax and aggregation in one operator
 
     def attend(self, feat, s):
         """``aggregate(feat, softmax(s))``: scores [nnz, H], out [n, H, out_feats]; one operator with ``fused``."""

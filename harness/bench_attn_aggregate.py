@@ -27,7 +27,7 @@ import torch  # noqa: E402
 import synth_graphs  # noqa: E402
 from gat_train import with_self_loops  # noqa: E402
 from voltrix.attn_aggregate import attn_aggregate, attn_aggregate_grad_feat, attn_aggregate_grad_scores  # noqa: E402
-from voltrix.autograd import AttnAggregate, EdgeSoftmax, SpMMHeads  # noqa: E402
+from voltrix.autograd import AttnAggregate, CsrPattern, EdgeSoftmax, SpMMHeads  # noqa: E402
 
 DEFAULT_CASES = ("amazon0601_like", "web_berkstan_like", "reddit_like")
 DEFAULT_SHAPES = ("1x64", "8x8", "8x16", "4x64")
@@ -113,8 +113,8 @@ def main(argv=None):
         indptr, indices, _ = synth_graphs.generate(name, device="cuda", scale=args.scale)
         n = indptr.numel() - 1
         indptr, indices = with_self_loops(indptr.int(), indices.int(), n)
-        heads_op, softmax = SpMMHeads(indptr, indices, n), EdgeSoftmax(indptr, n)
-        fused = AttnAggregate(indptr, indices, n, transposed=(heads_op.t_indptr, heads_op.t_indices, heads_op.t_order))
+        pattern = CsrPattern(indptr, indices, n)
+        heads_op, softmax, fused = SpMMHeads(pattern), EdgeSoftmax(pattern), AttnAggregate(pattern)
         for heads, dim in (tuple(int(t) for t in s.split("x")) for s in args.shapes):
             if args.fused_only:
                 feat = torch.randn(n, heads, dim, device="cuda").half().requires_grad_(True)
@@ -125,7 +125,7 @@ def main(argv=None):
                 continue
             print(json.dumps(run_case(name, fused, softmax, heads_op, heads, dim, args.steps, args.warmup)), flush=True)
             torch.cuda.empty_cache()
-        del fused, heads_op, softmax
+        del fused, heads_op, softmax, pattern
         torch.cuda.empty_cache()
 
 

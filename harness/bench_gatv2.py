@@ -25,9 +25,8 @@ import torch  # noqa: E402
 
 import synth_graphs  # noqa: E402
 import voltrix  # noqa: E402
-from voltrix.autograd import csr_transpose_device  # noqa: E402
+from voltrix.autograd import CsrPattern  # noqa: E402
 from voltrix.gatv2_score import gatv2_rowsum  # noqa: E402
-from voltrix.weighted import transpose_order  # noqa: E402
 
 DEFAULT_CASES = ("amazon0601_like", "web_berkstan_like", "reddit_like")
 DEFAULT_SHAPES = ("1x64", "8x8", "4x64")
@@ -71,8 +70,8 @@ def run_graph(name, shapes, steps, warmup, torch_steps, scale):
     n = indptr.numel() - 1
     indptr, indices = with_self_loops(indptr, indices, n)
     nnz = indices.numel()
-    t_indptr, t_indices = csr_transpose_device(indptr, indices, n, n)
-    t_order = transpose_order(indptr, indices, n).to(torch.int32)
+    pattern = CsrPattern(indptr, indices, n)
+    t_indptr, t_indices, t_order = pattern.t_indptr, pattern.t_indices, pattern.t_order
     deg, t_deg = indptr[1:] - indptr[:-1], t_indptr[1:] - t_indptr[:-1]
     for heads, dim in shapes:
         torch.manual_seed(0)

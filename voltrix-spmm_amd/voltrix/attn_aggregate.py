@@ -29,12 +29,7 @@ import math
 
 import torch
 
-from .sddmm import _TYPES, _padded_heads
-
-
-def _width(head_dim: int, dtype) -> int:
-    align = 4 if dtype == torch.float32 else 8
-    return max(align, (head_dim + align - 1) // align * align)
+from .utils import FEATURE_TYPES, padded_last_dim, piece_width
 
 
 def _scores(scores: torch.Tensor, nnz: int, heads: int) -> torch.Tensor:
@@ -72,17 +67,17 @@ def attn_aggregate(indptr: torch.Tensor, indices: torch.Tensor, scores: torch.Te
         feat = feat.unsqueeze(1)
     else:
         assert scores.dim() == 2 and scores.shape[1] == feat.shape[1], (tuple(scores.shape), tuple(feat.shape))
-    if feat.dtype not in _TYPES:
+    if feat.dtype not in FEATURE_TYPES:
         feat = feat.float()
     heads, head_dim = feat.shape[1], feat.shape[2]
     assert heads >= 1
     scores = _scores(scores, indices.numel(), heads)
-    width = _width(head_dim, feat.dtype)
+    width = piece_width(max(head_dim, 1), feat.dtype)
     out = torch.empty((num_rows, heads, width), dtype=torch.float32, device=feat.device)
     m = torch.empty((num_rows, heads), dtype=torch.float32, device=feat.device)
     l = torch.empty((num_rows, heads), dtype=torch.float32, device=feat.device)
     if num_rows > 0:
-        capi.launch_attn_aggregate_csr(indptr.contiguous(), indices.contiguous(), scores, num_rows, _padded_heads(feat, width), scale,
+        capi.launch_attn_aggregate_csr(indptr.contiguous(), indices.contiguous(), scores, num_rows, padded_last_dim(feat, width), scale,
                                        out, m, l, _raw_stream(feat.device))
     if width != head_dim:
         out = out[:, :, :head_dim].contiguous()
@@ -107,7 +102,7 @@ def attn_aggregate_grad_scores(indptr: torch.Tensor, indices: torch.Tensor, grad
     one_d = feat.dim() == 2
     if one_d:
         feat, grad_out = feat.unsqueeze(1), grad_out.unsqueeze(1)
-    if feat.dtype not in _TYPES:
+    if feat.dtype not in FEATURE_TYPES:
         feat = feat.float()
     num_rows, nnz = indptr.numel() - 1, indices.numel()
     heads, head_dim = feat.shape[1], feat.shape[2]
@@ -118,9 +113,9 @@ def attn_aggregate_grad_scores(indptr: torch.Tensor, indices: torch.Tensor, grad
     if nnz > 0 and head_dim == 0:
         out.zero_()
     elif nnz > 0:
-        width = _width(head_dim, feat.dtype)
+        width = piece_width(max(head_dim, 1), feat.dtype)
         capi.launch_attn_aggregate_grad_scores_csr(indptr.contiguous(), indices.contiguous(), num_rows,
-                                                   _padded_heads(grad_out.float(), width), _padded_heads(feat, width), scores, m, l, delta,
+                                                   padded_last_dim(grad_out.float(), width), padded_last_dim(feat, width), scores, m, l, delta,
                                                    scale, out, _raw_stream(feat.device))
     return out.view(-1) if one_d else out
 
@@ -141,7 +136,7 @@ def attn_aggregate_grad_feat(t_indptr: torch.Tensor, t_indices: torch.Tensor, t_
     one_d = grad_out.dim() == 2
     if one_d:
         grad_out = grad_out.unsqueeze(1)
-    if grad_out.dtype not in _TYPES:
+    if grad_out.dtype not in FEATURE_TYPES:
         grad_out = grad_out.float()
     nnz = t_indices.numel()
     num_rows, heads, head_dim = grad_out.shape
@@ -149,11 +144,11 @@ def attn_aggregate_grad_feat(t_indptr: torch.Tensor, t_indices: torch.Tensor, t_
     t_order = t_order.to(torch.int32).contiguous()
     scores = _scores(scores, nnz, heads)
     m, l = (t.float().contiguous().view(num_rows, heads) for t in (m, l))
-    width = _width(head_dim, grad_out.dtype)
+    width = piece_width(max(head_dim, 1), grad_out.dtype)
     out = torch.empty((num_cols, heads, width), dtype=torch.float32, device=grad_out.device)
     if num_cols > 0:
         capi.launch_attn_aggregate_grad_feat_csr(t_indptr.contiguous(), t_indices.contiguous(), t_order, num_cols,
-                                                 _padded_heads(grad_out, width), scores, m, l, scale, out, _raw_stream(grad_out.device))
+                                                 padded_last_dim(grad_out, width), scores, m, l, scale, out, _raw_stream(grad_out.device))
     if width != head_dim:
         out = out[:, :, :head_dim].contiguous()
     return out.view(num_cols, head_dim) if one_d else out

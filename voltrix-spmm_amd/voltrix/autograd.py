@@ -113,6 +113,52 @@ class _SpMMValuesFunction(torch.autograd.Function):
         return grad_feat, grad_values, None
 
 
+class CsrPattern:
+    """A CSR pattern [num_rows, num_cols] (``num_cols`` defaults to ``num_rows``) as the attention operators hold it, built once and
+    shared: the device int32 ``indptr`` / ``indices``, ``num_rows`` / ``num_cols`` / ``num_edges``, the transposed CSR ``t_indptr`` /
+    ``t_indices`` (``csr_transpose_device``) and ``t_order``, int32 [nnz]: entry ``e`` of the transpose is entry ``t_order[e]`` of the
+    CSR (``weighted.transpose_order``).  Everything is built in the constructor.  ``transposed=(t_indptr, t_indices, t_order)`` takes a
+    transpose that exists already (any integer type for the order)."""
+
+    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, num_rows: int, num_cols: int = None, transposed=None):
+        assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+        self.num_rows = num_rows
+        self.num_cols = num_rows if num_cols is None else int(num_cols)
+        self.num_edges = int(indices.numel())
+        self.indptr, self.indices = indptr.contiguous().cuda(), indices.contiguous().cuda()
+        if transposed is None:
+            from .weighted import transpose_order
+
+            t_indptr, t_indices = csr_transpose_device(self.indptr, self.indices, num_rows, self.num_cols)
+            t_order = transpose_order(self.indptr, self.indices, num_rows)
+        else:
+            t_indptr, t_indices, t_order = transposed
+            assert t_indptr.numel() == self.num_cols + 1 and t_indices.numel() == self.num_edges == t_order.numel()
+        self.t_indptr, self.t_indices, self.t_order = t_indptr, t_indices, t_order.to(torch.int32).contiguous()
+
+
+class _PatternOp:
+    """What ``SDDMM``, ``SpMMHeads``, ``GATScore``, ``GATv2Score`` and ``AttnAggregate`` share: ``Op(indptr, indices, num_rows,
+    num_cols=None, transposed=None)`` builds a ``CsrPattern`` of its own, ``Op(pattern)`` takes one that exists -- nothing is copied or
+    built again, so one graph is transposed once for all its operators.  The pattern's fields read through under their names."""
+
+    def __init__(self, indptr, indices: torch.Tensor = None, num_rows: int = None, num_cols: int = None, transposed=None):
+        if isinstance(indptr, CsrPattern):
+            assert indices is None and num_rows is None and num_cols is None and transposed is None
+            self.pattern = indptr
+        else:
+            self.pattern = CsrPattern(indptr, indices, num_rows, num_cols, transposed)
+
+    indptr = property(lambda self: self.pattern.indptr)
+    indices = property(lambda self: self.pattern.indices)
+    t_indptr = property(lambda self: self.pattern.t_indptr)
+    t_indices = property(lambda self: self.pattern.t_indices)
+    t_order = property(lambda self: self.pattern.t_order)
+    num_rows = property(lambda self: self.pattern.num_rows)
+    num_cols = property(lambda self: self.pattern.num_cols)
+    num_edges = property(lambda self: self.pattern.num_edges)
+
+
 class _SDDMMFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y, op):
@@ -145,21 +191,11 @@ class _SDDMMFunction(torch.autograd.Function):
         return grad_x, grad_y, None
 
 
-class SDDMM:
+class SDDMM(_PatternOp):
     """``s[e] = <x[row_e], y[col_e]>`` for every entry of a CSR pattern [num_rows, num_cols] (``num_cols`` defaults to ``num_rows``),
     differentiable in both operands: attention scores ``SDDMM(...)(q, k)``.  Built once per pattern: the device CSR, its transpose
-    (``csr_transpose_device``) and the transposed edge order (``weighted.transpose_order``).  Gradients come back in the operands'
-    dtypes.  Multi-head: ``x`` [num_rows, H, D], ``y`` [num_cols, H, D] -> ``s`` [nnz, H]; the backward is ``voltrix.spmm_heads``."""
-
-    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, num_rows: int, num_cols: int = None):
-        from .weighted import transpose_order
-
-        assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
-        self.num_rows = num_rows
-        self.num_cols = num_rows if num_cols is None else int(num_cols)
-        self.indptr, self.indices = indptr.contiguous().cuda(), indices.contiguous().cuda()
-        self.t_indptr, self.t_indices = csr_transpose_device(self.indptr, self.indices, num_rows, self.num_cols)
-        self.t_order = transpose_order(self.indptr, self.indices, num_rows)
+    (``csr_transpose_device``) and the transposed edge order (``weighted.transpose_order``, kept as int32) -- or ``SDDMM(pattern)`` on a
+    ``CsrPattern`` shared with the other operators of the graph.  Gradients come back in the operands' dtypes.  Multi-head: ``x`` [num_rows, H, D], ``y`` [num_cols, H, D] -> ``s`` [nnz, H]; the backward is ``voltrix.spmm_heads``."""
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         assert x.dim() in (2, 3) and x.dim() == y.dim()
@@ -191,7 +227,9 @@ class EdgeSoftmax:
     in the scores: the attention weights between ``SDDMM`` and ``SpMM(..., values=)``.  Holds the device ``indptr``; the column ids do not
     matter.  ``alpha`` is float32; the gradient comes back in the scores' dtype.  ``scores`` [nnz] or, multi-head, [nnz, H]."""
 
-    def __init__(self, indptr: torch.Tensor, num_rows: int):
+    def __init__(self, indptr, num_rows: int = None):
+        if isinstance(indptr, CsrPattern):
+            indptr, num_rows = indptr.indptr, indptr.num_rows
         assert indptr.dtype == torch.int32 and indptr.numel() == num_rows + 1
         self.num_rows = num_rows
         self.indptr = indptr.contiguous().cuda()
@@ -225,24 +263,13 @@ class _SpMMHeadsFunction(torch.autograd.Function):
         return grad_feat, grad_values, None
 
 
-class SpMMHeads:
+class SpMMHeads(_PatternOp):
     """Multi-head aggregation ``out[r, h] = sum_{e in row r} values[e, h] feat[col_e, h]`` on a CSR pattern [num_rows, num_cols]
     (``num_cols`` defaults to ``num_rows``), differentiable in ``feat`` [num_cols, H, D] and ``values`` [nnz, H]: the last step of a
     multi-head attention layer, ``SpMMHeads(...)(v, EdgeSoftmax(...)(SDDMM(...)(q, k), d ** -0.5))``.  Built once per pattern: the
-    device CSR, its transpose and the transposed edge order -- no block-format handle, and nothing is installed per call
-    (``voltrix.spmm_heads`` reads the values where it uses them).  ``out`` is float32 [num_rows, H, D]; ``feat.grad =
+    device CSR, its transpose and the transposed edge order (kept as int32), or ``SpMMHeads(pattern)`` on a shared ``CsrPattern`` -- no
+    block-format handle, and nothing is installed per call (``voltrix.spmm_heads`` reads the values where it uses them).  ``out`` is float32 [num_rows, H, D]; ``feat.grad =
     spmm_heads(csr^T, values[t_order], dC)`` and ``values.grad = sddmm(dC, feat)`` come back in the inputs' dtypes."""
-
-    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, num_rows: int, num_cols: int = None):
-        from .weighted import transpose_order
-
-        assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
-        self.num_rows = num_rows
-        self.num_cols = num_rows if num_cols is None else int(num_cols)
-        self.num_edges = int(indices.numel())
-        self.indptr, self.indices = indptr.contiguous().cuda(), indices.contiguous().cuda()
-        self.t_indptr, self.t_indices = csr_transpose_device(self.indptr, self.indices, num_rows, self.num_cols)
-        self.t_order = transpose_order(self.indptr, self.indices, num_rows)
 
     def __call__(self, feat: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
         assert feat.dim() == 3 and values.dim() == 2 and feat.shape[0] == self.num_cols
@@ -274,30 +301,14 @@ class _GATScoreFunction(torch.autograd.Function):
         return grad_el, grad_er, None, None
 
 
-class GATScore:
+class GATScore(_PatternOp):
     """GAT's edge scores ``s[e] = leaky_relu(el[row_e] + er[col_e], slope)`` on a CSR pattern [num_rows, num_cols] (``num_cols`` defaults
     to ``num_rows``), differentiable in both node scalars: the first step of ``SpMMHeads(...)(wh, EdgeSoftmax(...)(GATScore(...)(el,
     er)))``.  ``el`` [num_rows] or [num_rows, H], ``er`` [num_cols] or [num_cols, H] -> float32 [nnz] or [nnz, H].  Built once per
-    pattern: the device CSR, its transpose and the transposed edge order (kept as int32); ``transposed=(t_indptr, t_indices, t_order)``
-    takes ones that exist already (an ``SpMMHeads`` or ``SDDMM`` of the same pattern).  The backward is two segment sums
+    pattern: the device CSR, its transpose and the transposed edge order (kept as int32); ``GATScore(pattern)`` takes a ``CsrPattern``
+    shared with the other operators of the graph, ``transposed=(t_indptr, t_indices, t_order)`` a transpose that exists already.  The backward is two segment sums
     (``voltrix.gat_score.gat_score_backward``): no index op, no float atomics, the same bits on every run; gradients come back in the
     inputs' dtypes, and a side that needs none is skipped."""
-
-    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, num_rows: int, num_cols: int = None, transposed=None):
-        assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
-        self.num_rows = num_rows
-        self.num_cols = num_rows if num_cols is None else int(num_cols)
-        self.num_edges = int(indices.numel())
-        self.indptr, self.indices = indptr.contiguous().cuda(), indices.contiguous().cuda()
-        if transposed is None:
-            from .weighted import transpose_order
-
-            t_indptr, t_indices = csr_transpose_device(self.indptr, self.indices, num_rows, self.num_cols)
-            t_order = transpose_order(self.indptr, self.indices, num_rows)
-        else:
-            t_indptr, t_indices, t_order = transposed
-            assert t_indptr.numel() == self.num_cols + 1 and t_indices.numel() == self.num_edges == t_order.numel()
-        self.t_indptr, self.t_indices, self.t_order = t_indptr, t_indices, t_order.to(torch.int32).contiguous()
 
     def __call__(self, el: torch.Tensor, er: torch.Tensor, slope: float = 0.2) -> torch.Tensor:
         assert el.dim() in (1, 2) and el.dim() == er.dim() and el.shape[1:] == er.shape[1:]
@@ -336,32 +347,16 @@ class _GATv2ScoreFunction(torch.autograd.Function):
         return grad_xl, grad_xr, grad_a, None, None
 
 
-class GATv2Score:
+class GATv2Score(_PatternOp):
     """GATv2's edge scores ``s[e, h] = sum_d a[h, d] leaky_relu(xl[row_e, h, d] + xr[col_e, h, d], slope)`` on a CSR pattern [num_rows,
     num_cols] (``num_cols`` defaults to ``num_rows``), differentiable in ``xl``, ``xr`` and ``a``: the first step of
     ``SpMMHeads(...)(xr, EdgeSoftmax(...)(GATv2Score(...)(xl, xr, a)))``.  ``xl`` [num_rows, H, D], ``xr`` [num_cols, H, D], ``a`` [H, D]
     -> float32 [nnz, H]; the 2-D form ([n, D], [D] -> [nnz]) is one head.  Built once per pattern, exactly like ``GATScore``: the device
-    CSR, its transpose and the transposed edge order (kept as int32), or ``transposed=(t_indptr, t_indices, t_order)`` of an
-    ``SpMMHeads`` / ``SDDMM`` / ``GATScore`` of the same pattern.  Saves ``xl``, ``xr``, ``a`` only.  The backward is two gated row sums
+    CSR, its transpose and the transposed edge order (kept as int32), or ``GATv2Score(pattern)`` on a shared ``CsrPattern``, or
+    ``transposed=(t_indptr, t_indices, t_order)``.  Saves ``xl``, ``xr``, ``a`` only.  The backward is two gated row sums
     (``voltrix.gatv2_score.gatv2_rowsum``) and dense torch products: ``xl.grad = a G_l``, ``xr.grad = a G_r``, ``a.grad = sum xl G_l +
     sum xr G_r`` -- no index op, no float atomics, nothing of size [nnz, H, D]; gradients come back in the inputs' dtypes, and a side
     nobody needs is skipped."""
-
-    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, num_rows: int, num_cols: int = None, transposed=None):
-        assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
-        self.num_rows = num_rows
-        self.num_cols = num_rows if num_cols is None else int(num_cols)
-        self.num_edges = int(indices.numel())
-        self.indptr, self.indices = indptr.contiguous().cuda(), indices.contiguous().cuda()
-        if transposed is None:
-            from .weighted import transpose_order
-
-            t_indptr, t_indices = csr_transpose_device(self.indptr, self.indices, num_rows, self.num_cols)
-            t_order = transpose_order(self.indptr, self.indices, num_rows)
-        else:
-            t_indptr, t_indices, t_order = transposed
-            assert t_indptr.numel() == self.num_cols + 1 and t_indices.numel() == self.num_edges == t_order.numel()
-        self.t_indptr, self.t_indices, self.t_order = t_indptr, t_indices, t_order.to(torch.int32).contiguous()
 
     def __call__(self, xl: torch.Tensor, xr: torch.Tensor, a: torch.Tensor, slope: float = 0.2) -> torch.Tensor:
         assert xl.dim() in (2, 3) and xl.dim() == xr.dim() and xl.shape[1:] == xr.shape[1:] == a.shape
@@ -397,32 +392,16 @@ class _AttnAggregateFunction(torch.autograd.Function):
         return grad_feat, grad_scores, None, None
 
 
-class AttnAggregate:
+class AttnAggregate(_PatternOp):
     """``out[r, h] = sum_{e in row r} softmax(scale * scores)[e, h] feat[col_e, h]`` on a CSR pattern [num_rows, num_cols] (``num_cols``
     defaults to ``num_rows``) in one launch (``voltrix.attn_aggregate``), differentiable in ``feat`` [num_cols, H, D] and ``scores``
     [nnz, H]: ``SpMMHeads(...)(feat, EdgeSoftmax(...)(scores, scale))`` without the attention weights ever being stored.  The 2-D form
     (``feat`` [num_cols, D], ``scores`` [nnz]) is one head.  Built once per pattern, exactly like ``GATScore``: the device CSR, its
-    transpose and the transposed edge order (kept as int32), or ``transposed=(t_indptr, t_indices, t_order)`` of an ``SpMMHeads`` /
-    ``SDDMM`` / ``GATScore`` of the same pattern.  Saves ``feat``, ``scores``, ``out`` and the row statistics ``m``, ``l`` [num_rows, H].
+    transpose and the transposed edge order (kept as int32), or ``AttnAggregate(pattern)`` on a shared ``CsrPattern``, or
+    ``transposed=(t_indptr, t_indices, t_order)``.  Saves ``feat``, ``scores``, ``out`` and the row statistics ``m``, ``l`` [num_rows, H].
     The backward is ``delta = (dC * out).sum(-1)`` (dense torch), one launch split by edges for ``scores.grad`` and one on the transposed
     CSR for ``feat.grad`` (``voltrix.attn_aggregate.attn_aggregate_grad_scores`` / ``attn_aggregate_grad_feat``): no index op, no float
     atomics, no [nnz, H] tensor but ``scores.grad``; gradients come back in the inputs' dtypes, and a side nobody needs is skipped."""
-
-    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, num_rows: int, num_cols: int = None, transposed=None):
-        assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
-        self.num_rows = num_rows
-        self.num_cols = num_rows if num_cols is None else int(num_cols)
-        self.num_edges = int(indices.numel())
-        self.indptr, self.indices = indptr.contiguous().cuda(), indices.contiguous().cuda()
-        if transposed is None:
-            from .weighted import transpose_order
-
-            t_indptr, t_indices = csr_transpose_device(self.indptr, self.indices, num_rows, self.num_cols)
-            t_order = transpose_order(self.indptr, self.indices, num_rows)
-        else:
-            t_indptr, t_indices, t_order = transposed
-            assert t_indptr.numel() == self.num_cols + 1 and t_indices.numel() == self.num_edges == t_order.numel()
-        self.t_indptr, self.t_indices, self.t_order = t_indptr, t_indices, t_order.to(torch.int32).contiguous()
 
     def __call__(self, feat: torch.Tensor, scores: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
         assert feat.dim() in (2, 3) and scores.dim() == feat.dim() - 1 and feat.shape[0] == self.num_cols

@@ -577,7 +577,40 @@ def launch_cast_f32_f16_scaled(src, dst, scale, stream) -> None:
         check(rc.value, "voltrix_launch_cast_f32_f16_scaled")
 
 
-_spmm_csr_rows = None
+# ---- the CSR / attention launchers: argument types per symbol (include/voltrix_capi.h), set on the first use of a symbol -- with them
+# ---- plain ints and data_ptr() values convert in C (12 -> 4 us per call on the host)
+_P, _I, _L, _F, _RC_P = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.POINTER(ctypes.c_int)
+_ARGTYPES = {
+    "voltrix_launch_spmm_csr_rows": [_P, _P, _I, _I, _P, _I, _P, _I, _P, _RC_P],
+    "voltrix_launch_spmm_csr_rows_weighted": [_P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _RC_P],
+    "voltrix_launch_sddmm_csr": [_P, _P, _I, _L, _I, _P, _I, _P, _I, _P, _P, _RC_P],
+    "voltrix_launch_edge_softmax_csr": [_P, _I, _L, _P, _F, _P, _P, _P, _RC_P],
+    "voltrix_launch_edge_softmax_backward_csr": [_P, _I, _L, _P, _P, _F, _P, _P, _P, _RC_P],
+    "voltrix_launch_sddmm_heads_csr": [_P, _P, _I, _L, _I, _I, _P, _I, _P, _I, _P, _P, _RC_P],
+    "voltrix_launch_edge_softmax_heads_csr": [_P, _I, _L, _I, _P, _F, _P, _P, _P, _RC_P],
+    "voltrix_launch_edge_softmax_heads_backward_csr": [_P, _I, _L, _I, _P, _P, _F, _P, _P, _P, _RC_P],
+    "voltrix_launch_spmm_csr_heads": [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _RC_P],
+    "voltrix_launch_gat_score_csr": [_P, _P, _I, _L, _I, _P, _P, _F, _P, _P, _RC_P],
+    "voltrix_launch_gat_score_rowsum_csr": [_P, _P, _P, _I, _L, _I, _P, _P, _P, _F, _P, _P, _P, _RC_P],
+    "voltrix_launch_gatv2_score_csr": [_P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _F, _P, _P, _RC_P],
+    "voltrix_launch_gatv2_rowsum_csr": [_P, _P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _F, _P, _P, _RC_P],
+    "voltrix_launch_attn_aggregate_csr": [_P, _P, _P, _I, _L, _I, _I, _P, _I, _F, _P, _P, _P, _P, _RC_P],
+    "voltrix_launch_attn_aggregate_grad_scores_csr": [_P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _F, _P, _P, _RC_P],
+    "voltrix_launch_attn_aggregate_grad_feat_csr": [_P, _P, _P, _I, _L, _I, _I, _P, _I, _P, _P, _P, _F, _P, _P, _RC_P],
+    "voltrix_launch_scatter_values": [_P, _P, _P, _L, _I, _P, _RC_P],
+    "voltrix_launch_scale_rows": [_P, _P, _P, _L, _I, _I, _P, _RC_P],
+}
+_bound_fns = {}
+
+
+def _bound(name: str):
+    """The library's entry point ``name`` with its argument types set."""
+    fn = _bound_fns.get(name)
+    if fn is None:
+        fn = getattr(lib(), name)
+        fn.argtypes = _ARGTYPES[name]
+        _bound_fns[name] = fn
+    return fn
 
 
 def launch_spmm_csr_rows(indptr, indices, num_rows: int, feat, output, stream, xcd_ranges: int = 0, values=None) -> None:
@@ -586,35 +619,20 @@ def launch_spmm_csr_rows(indptr, indices, num_rows: int, feat, output, stream, x
     [num_rows, F]); see include/voltrix_capi.h."""
     import torch
 
-    global _spmm_csr_rows, _spmm_csr_rows_weighted
-    if _spmm_csr_rows is None:
-        fn = lib().voltrix_launch_spmm_csr_rows
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _spmm_csr_rows = fn
-        fn = lib().voltrix_launch_spmm_csr_rows_weighted
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _spmm_csr_rows_weighted = fn
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
     assert feat.dim() == 2 and feat.is_contiguous() and output.is_contiguous() and output.dtype == torch.float32
     assert output.shape == (num_rows, feat.shape[1])
     dtype = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[feat.dtype]
     rc = ctypes.c_int(-1)
     if values is None:
-        _spmm_csr_rows(indptr.data_ptr(), indices.data_ptr(), num_rows, feat.shape[1], feat.data_ptr(), dtype, output.data_ptr(),
-                       int(xcd_ranges), stream, rc)
+        _bound("voltrix_launch_spmm_csr_rows")(indptr.data_ptr(), indices.data_ptr(), num_rows, feat.shape[1], feat.data_ptr(), dtype,
+                                               output.data_ptr(), int(xcd_ranges), stream, rc)
         check(rc.value, "voltrix_launch_spmm_csr_rows")
         return
     assert values.dtype == torch.float32 and values.is_contiguous() and values.numel() == indices.numel() and values.is_cuda
-    _spmm_csr_rows_weighted(indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), num_rows, feat.shape[1], feat.data_ptr(), dtype,
-                            output.data_ptr(), int(xcd_ranges), stream, rc)
+    _bound("voltrix_launch_spmm_csr_rows_weighted")(indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), num_rows, feat.shape[1],
+                                                    feat.data_ptr(), dtype, output.data_ptr(), int(xcd_ranges), stream, rc)
     check(rc.value, "voltrix_launch_spmm_csr_rows_weighted")
-
-
-_spmm_csr_rows_weighted = None
-_sddmm_csr = None
-_scatter_values = None
 
 
 def launch_sddmm_csr(indptr, indices, num_rows: int, x, y, out, stream) -> None:
@@ -623,24 +641,14 @@ def launch_sddmm_csr(indptr, indices, num_rows: int, x, y, out, stream) -> None:
     F a multiple of 16 bytes of ``y``; ``out`` float32 [nnz] in CSR order; see include/voltrix_capi.h."""
     import torch
 
-    global _sddmm_csr
-    if _sddmm_csr is None:
-        fn = lib().voltrix_launch_sddmm_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _sddmm_csr = fn
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
     assert x.dim() == 2 and y.dim() == 2 and x.is_contiguous() and y.is_contiguous() and x.shape[0] == num_rows
     assert x.shape[1] == y.shape[1] and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == indices.numel()
     codes = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
     rc = ctypes.c_int(-1)
-    _sddmm_csr(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), x.shape[1], x.data_ptr(), codes[x.dtype], y.data_ptr(),
-               codes[y.dtype], out.data_ptr(), stream, rc)
+    _bound("voltrix_launch_sddmm_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), x.shape[1], x.data_ptr(),
+                                       codes[x.dtype], y.data_ptr(), codes[y.dtype], out.data_ptr(), stream, rc)
     check(rc.value, "voltrix_launch_sddmm_csr")
-
-
-_edge_softmax = None
-_edge_softmax_backward = None
 
 
 def edge_softmax_workspace_bytes(num_rows: int, nnz: int) -> int:
@@ -653,18 +661,12 @@ def launch_edge_softmax_csr(indptr, num_rows: int, scores, scale: float, out, wo
     ``out`` float32 [nnz] in CSR order, ``workspace`` uint8 of ``edge_softmax_workspace_bytes`` bytes; see include/voltrix_capi.h."""
     import torch
 
-    global _edge_softmax
-    if _edge_softmax is None:
-        fn = lib().voltrix_launch_edge_softmax_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _edge_softmax = fn
     assert indptr.dtype == torch.int32 and indptr.numel() == num_rows + 1 and indptr.is_contiguous()
     assert scores.dtype == torch.float32 and out.dtype == torch.float32 and scores.is_contiguous() and out.is_contiguous()
     assert out.numel() == scores.numel() and workspace.numel() >= edge_softmax_workspace_bytes(num_rows, scores.numel())
     rc = ctypes.c_int(-1)
-    _edge_softmax(indptr.data_ptr(), num_rows, scores.numel(), scores.data_ptr(), float(scale), out.data_ptr(), workspace.data_ptr(),
-                  stream, rc)
+    _bound("voltrix_launch_edge_softmax_csr")(indptr.data_ptr(), num_rows, scores.numel(), scores.data_ptr(), float(scale), out.data_ptr(),
+                                              workspace.data_ptr(), stream, rc)
     check(rc.value, "voltrix_launch_edge_softmax_csr")
 
 
@@ -673,28 +675,18 @@ def launch_edge_softmax_backward_csr(indptr, num_rows: int, alpha, grad_alpha, s
     CSR order; the forward's workspace size; see include/voltrix_capi.h."""
     import torch
 
-    global _edge_softmax_backward
-    if _edge_softmax_backward is None:
-        fn = lib().voltrix_launch_edge_softmax_backward_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _edge_softmax_backward = fn
     assert indptr.dtype == torch.int32 and indptr.numel() == num_rows + 1 and indptr.is_contiguous()
     for t in (alpha, grad_alpha, grad_scores):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == alpha.numel()
     assert workspace.numel() >= edge_softmax_workspace_bytes(num_rows, alpha.numel())
     rc = ctypes.c_int(-1)
-    _edge_softmax_backward(indptr.data_ptr(), num_rows, alpha.numel(), alpha.data_ptr(), grad_alpha.data_ptr(), float(scale),
-                           grad_scores.data_ptr(), workspace.data_ptr(), stream, rc)
+    _bound("voltrix_launch_edge_softmax_backward_csr")(indptr.data_ptr(), num_rows, alpha.numel(), alpha.data_ptr(), grad_alpha.data_ptr(),
+                                                       float(scale), grad_scores.data_ptr(), workspace.data_ptr(), stream, rc)
     check(rc.value, "voltrix_launch_edge_softmax_backward_csr")
 
 
 # ---- multi-head forms (csrc/capi_heads.hip): node tensors [n, H, D], edge tensors [nnz, H] with the head index fastest
 _CODES = None
-_sddmm_heads = None
-_edge_softmax_heads = None
-_edge_softmax_heads_backward = None
-_spmm_csr_heads = None
 
 
 def _dtype_code(dtype) -> int:
@@ -712,19 +704,14 @@ def launch_sddmm_heads_csr(indptr, indices, num_rows: int, x, y, out, stream) ->
     [nnz, H]; see include/voltrix_capi.h."""
     import torch
 
-    global _sddmm_heads
-    if _sddmm_heads is None:
-        fn = lib().voltrix_launch_sddmm_heads_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                       ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _sddmm_heads = fn
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
     assert x.dim() == 3 and y.dim() == 3 and x.is_contiguous() and y.is_contiguous() and x.shape[0] == num_rows
     assert x.shape[1:] == y.shape[1:] and out.dtype == torch.float32 and out.is_contiguous()
     assert out.shape == (indices.numel(), x.shape[1])
     rc = ctypes.c_int(-1)
-    _sddmm_heads(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), x.shape[1], x.shape[2], x.data_ptr(),
-                 _dtype_code(x.dtype), y.data_ptr(), _dtype_code(y.dtype), out.data_ptr(), stream, rc)
+    _bound("voltrix_launch_sddmm_heads_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), x.shape[1], x.shape[2],
+                                             x.data_ptr(), _dtype_code(x.dtype), y.data_ptr(), _dtype_code(y.dtype), out.data_ptr(), stream,
+                                             rc)
     check(rc.value, "voltrix_launch_sddmm_heads_csr")
 
 
@@ -740,20 +727,14 @@ def launch_edge_softmax_heads_csr(indptr, num_rows: int, scores, scale: float, o
     ``edge_softmax_heads_workspace_bytes`` bytes; see include/voltrix_capi.h."""
     import torch
 
-    global _edge_softmax_heads
-    if _edge_softmax_heads is None:
-        fn = lib().voltrix_launch_edge_softmax_heads_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _edge_softmax_heads = fn
     assert indptr.dtype == torch.int32 and indptr.numel() == num_rows + 1 and indptr.is_contiguous()
     assert scores.dim() == 2 and scores.dtype == torch.float32 and out.dtype == torch.float32
     assert scores.is_contiguous() and out.is_contiguous() and out.shape == scores.shape
     nnz, heads = scores.shape
     assert workspace.numel() >= edge_softmax_heads_workspace_bytes(num_rows, nnz, heads)
     rc = ctypes.c_int(-1)
-    _edge_softmax_heads(indptr.data_ptr(), num_rows, nnz, heads, scores.data_ptr(), float(scale), out.data_ptr(), workspace.data_ptr(),
-                        stream, rc)
+    _bound("voltrix_launch_edge_softmax_heads_csr")(indptr.data_ptr(), num_rows, nnz, heads, scores.data_ptr(), float(scale),
+                                                    out.data_ptr(), workspace.data_ptr(), stream, rc)
     check(rc.value, "voltrix_launch_edge_softmax_heads_csr")
 
 
@@ -761,20 +742,15 @@ def launch_edge_softmax_heads_backward_csr(indptr, num_rows: int, alpha, grad_al
     """The multi-head edge softmax's backward, all float32 [nnz, H]; the forward's workspace size; see include/voltrix_capi.h."""
     import torch
 
-    global _edge_softmax_heads_backward
-    if _edge_softmax_heads_backward is None:
-        fn = lib().voltrix_launch_edge_softmax_heads_backward_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
-                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _edge_softmax_heads_backward = fn
     assert indptr.dtype == torch.int32 and indptr.numel() == num_rows + 1 and indptr.is_contiguous()
     for t in (alpha, grad_alpha, grad_scores):
         assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous() and t.shape == alpha.shape
     nnz, heads = alpha.shape
     assert workspace.numel() >= edge_softmax_heads_workspace_bytes(num_rows, nnz, heads)
     rc = ctypes.c_int(-1)
-    _edge_softmax_heads_backward(indptr.data_ptr(), num_rows, nnz, heads, alpha.data_ptr(), grad_alpha.data_ptr(), float(scale),
-                                 grad_scores.data_ptr(), workspace.data_ptr(), stream, rc)
+    _bound("voltrix_launch_edge_softmax_heads_backward_csr")(indptr.data_ptr(), num_rows, nnz, heads, alpha.data_ptr(),
+                                                             grad_alpha.data_ptr(), float(scale), grad_scores.data_ptr(),
+                                                             workspace.data_ptr(), stream, rc)
     check(rc.value, "voltrix_launch_edge_softmax_heads_backward_csr")
 
 
@@ -784,25 +760,17 @@ def launch_spmm_csr_heads(indptr, indices, values, num_rows: int, feat, output, 
     see include/voltrix_capi.h."""
     import torch
 
-    global _spmm_csr_heads
-    if _spmm_csr_heads is None:
-        fn = lib().voltrix_launch_spmm_csr_heads
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                       ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _spmm_csr_heads = fn
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
     assert feat.dim() == 3 and feat.is_contiguous() and output.is_contiguous() and output.dtype == torch.float32
     assert output.shape == (num_rows,) + tuple(feat.shape[1:])
     assert values.dtype == torch.float32 and values.is_contiguous() and values.shape == (indices.numel(), feat.shape[1])
     rc = ctypes.c_int(-1)
-    _spmm_csr_heads(indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), num_rows, feat.shape[1], feat.shape[2], feat.data_ptr(),
-                    _dtype_code(feat.dtype), output.data_ptr(), stream, rc)
+    _bound("voltrix_launch_spmm_csr_heads")(indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), num_rows, feat.shape[1],
+                                            feat.shape[2], feat.data_ptr(), _dtype_code(feat.dtype), output.data_ptr(), stream, rc)
     check(rc.value, "voltrix_launch_spmm_csr_heads")
 
 
 # ---- GAT edge scores (csrc/capi_gat_score.hip): node scalars [n, H], edge tensors [nnz, H] with the head index fastest
-_gat_score = None
-_gat_score_rowsum = None
 
 
 def gat_score_workspace_bytes(num_rows: int, nnz: int, heads: int = 1) -> int:
@@ -816,20 +784,14 @@ def launch_gat_score_csr(indptr, indices, num_rows: int, el, er, slope: float, o
     include/voltrix_capi.h."""
     import torch
 
-    global _gat_score
-    if _gat_score is None:
-        fn = lib().voltrix_launch_gat_score_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _gat_score = fn
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
     assert indptr.is_contiguous() and indices.is_contiguous()
     for t in (el, er, out):
         assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous() and t.shape[1] == out.shape[1]
     assert el.shape[0] == num_rows and out.shape[0] == indices.numel()
     rc = ctypes.c_int(-1)
-    _gat_score(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), out.shape[1], el.data_ptr(), er.data_ptr(), float(slope),
-               out.data_ptr(), stream, rc)
+    _bound("voltrix_launch_gat_score_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), out.shape[1], el.data_ptr(),
+                                           er.data_ptr(), float(slope), out.data_ptr(), stream, rc)
     check(rc.value, "voltrix_launch_gat_score_csr")
 
 
@@ -840,13 +802,6 @@ def launch_gat_score_rowsum_csr(indptr, indices, order, num_rows: int, a, b, gra
     include/voltrix_capi.h."""
     import torch
 
-    global _gat_score_rowsum
-    if _gat_score_rowsum is None:
-        fn = lib().voltrix_launch_gat_score_rowsum_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.POINTER(ctypes.c_int)]
-        _gat_score_rowsum = fn
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
     assert indptr.is_contiguous() and indices.is_contiguous()
     nnz, heads = grad.shape
@@ -857,14 +812,13 @@ def launch_gat_score_rowsum_csr(indptr, indices, order, num_rows: int, a, b, gra
         assert order.dtype == torch.int32 and order.is_contiguous() and order.numel() == nnz
     assert workspace.numel() >= gat_score_workspace_bytes(num_rows, nnz, heads)
     rc = ctypes.c_int(-1)
-    _gat_score_rowsum(indptr.data_ptr(), indices.data_ptr(), order.data_ptr() if order is not None else None, num_rows, nnz, heads,
-                      a.data_ptr(), b.data_ptr(), grad.data_ptr(), float(slope), out.data_ptr(), workspace.data_ptr(), stream, rc)
+    _bound("voltrix_launch_gat_score_rowsum_csr")(indptr.data_ptr(), indices.data_ptr(), order.data_ptr() if order is not None else None,
+                                                  num_rows, nnz, heads, a.data_ptr(), b.data_ptr(), grad.data_ptr(), float(slope),
+                                                  out.data_ptr(), workspace.data_ptr(), stream, rc)
     check(rc.value, "voltrix_launch_gat_score_rowsum_csr")
 
 
 # ---- GATv2 edge scores (csrc/capi_gatv2_score.hip): node tensors [n, H, D], a [H, D], edge tensors [nnz, H] with the head index fastest
-_gatv2_score = None
-_gatv2_rowsum = None
 
 
 def launch_gatv2_score_csr(indptr, indices, num_rows: int, xl, xr, a, slope: float, out, stream) -> None:
@@ -873,13 +827,6 @@ def launch_gatv2_score_csr(indptr, indices, num_rows: int, xl, xr, a, slope: flo
     16 bytes; ``a`` float32 [H, D]; ``out`` float32 [nnz, H]; see include/voltrix_capi.h."""
     import torch
 
-    global _gatv2_score
-    if _gatv2_score is None:
-        fn = lib().voltrix_launch_gatv2_score_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.POINTER(ctypes.c_int)]
-        _gatv2_score = fn
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
     assert indptr.is_contiguous() and indices.is_contiguous()
     assert xl.dim() == 3 and xr.dim() == 3 and xl.is_contiguous() and xr.is_contiguous() and xl.shape[0] == num_rows
@@ -887,8 +834,9 @@ def launch_gatv2_score_csr(indptr, indices, num_rows: int, xl, xr, a, slope: flo
     assert a.dtype == torch.float32 and a.is_contiguous() and a.shape == xl.shape[1:]
     assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (indices.numel(), xl.shape[1])
     rc = ctypes.c_int(-1)
-    _gatv2_score(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), xl.shape[1], xl.shape[2], xl.data_ptr(), xr.data_ptr(),
-                 _dtype_code(xl.dtype), a.data_ptr(), float(slope), out.data_ptr(), stream, rc)
+    _bound("voltrix_launch_gatv2_score_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), xl.shape[1], xl.shape[2],
+                                             xl.data_ptr(), xr.data_ptr(), _dtype_code(xl.dtype), a.data_ptr(), float(slope),
+                                             out.data_ptr(), stream, rc)
     check(rc.value, "voltrix_launch_gatv2_score_csr")
 
 
@@ -898,13 +846,6 @@ def launch_gatv2_rowsum_csr(indptr, indices, order, num_rows: int, p, q, grad, s
     None or int32 [nnz], ``out`` float32 [num_rows, H, D] (every row written); see include/voltrix_capi.h."""
     import torch
 
-    global _gatv2_rowsum
-    if _gatv2_rowsum is None:
-        fn = lib().voltrix_launch_gatv2_rowsum_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.POINTER(ctypes.c_int)]
-        _gatv2_rowsum = fn
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
     assert indptr.is_contiguous() and indices.is_contiguous()
     assert p.dim() == 3 and q.dim() == 3 and p.is_contiguous() and q.is_contiguous() and p.shape[0] == num_rows
@@ -915,15 +856,13 @@ def launch_gatv2_rowsum_csr(indptr, indices, order, num_rows: int, p, q, grad, s
     if order is not None:
         assert order.dtype == torch.int32 and order.is_contiguous() and order.numel() == nnz
     rc = ctypes.c_int(-1)
-    _gatv2_rowsum(indptr.data_ptr(), indices.data_ptr(), order.data_ptr() if order is not None else None, num_rows, nnz, heads,
-                  p.shape[2], p.data_ptr(), q.data_ptr(), _dtype_code(p.dtype), grad.data_ptr(), float(slope), out.data_ptr(), stream, rc)
+    _bound("voltrix_launch_gatv2_rowsum_csr")(indptr.data_ptr(), indices.data_ptr(), order.data_ptr() if order is not None else None,
+                                              num_rows, nnz, heads, p.shape[2], p.data_ptr(), q.data_ptr(), _dtype_code(p.dtype),
+                                              grad.data_ptr(), float(slope), out.data_ptr(), stream, rc)
     check(rc.value, "voltrix_launch_gatv2_rowsum_csr")
 
 
 # ---- edge softmax + aggregation in one launch (csrc/capi_attn_aggregate.hip): scores [nnz, H], feat [n, H, D], row statistics [n, H]
-_attn_aggregate = None
-_attn_aggregate_grad_scores = None
-_attn_aggregate_grad_feat = None
 
 
 def launch_attn_aggregate_csr(indptr, indices, scores, num_rows: int, feat, scale: float, out, m, l, stream) -> None:
@@ -932,13 +871,6 @@ def launch_attn_aggregate_csr(indptr, indices, scores, num_rows: int, feat, scal
     multiple of 16 bytes, fp32 ``out`` [num_rows, H, D], fp32 ``m`` and ``l`` [num_rows, H]; see include/voltrix_capi.h."""
     import torch
 
-    global _attn_aggregate
-    if _attn_aggregate is None:
-        fn = lib().voltrix_launch_attn_aggregate_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                       ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.POINTER(ctypes.c_int)]
-        _attn_aggregate = fn
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
     assert indptr.is_contiguous() and indices.is_contiguous()
     assert feat.dim() == 3 and feat.is_contiguous() and out.is_contiguous() and out.dtype == torch.float32
@@ -948,8 +880,9 @@ def launch_attn_aggregate_csr(indptr, indices, scores, num_rows: int, feat, scal
     for t in (m, l):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (num_rows, heads)
     rc = ctypes.c_int(-1)
-    _attn_aggregate(indptr.data_ptr(), indices.data_ptr(), scores.data_ptr(), num_rows, indices.numel(), heads, feat.shape[2],
-                    feat.data_ptr(), _dtype_code(feat.dtype), float(scale), out.data_ptr(), m.data_ptr(), l.data_ptr(), stream, rc)
+    _bound("voltrix_launch_attn_aggregate_csr")(indptr.data_ptr(), indices.data_ptr(), scores.data_ptr(), num_rows, indices.numel(), heads,
+                                                feat.shape[2], feat.data_ptr(), _dtype_code(feat.dtype), float(scale), out.data_ptr(),
+                                                m.data_ptr(), l.data_ptr(), stream, rc)
     check(rc.value, "voltrix_launch_attn_aggregate_csr")
 
 
@@ -960,13 +893,6 @@ def launch_attn_aggregate_grad_scores_csr(indptr, indices, num_rows: int, grad_o
     ``l``, ``delta`` [num_rows, H]; see include/voltrix_capi.h."""
     import torch
 
-    global _attn_aggregate_grad_scores
-    if _attn_aggregate_grad_scores is None:
-        fn = lib().voltrix_launch_attn_aggregate_grad_scores_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
-                       ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _attn_aggregate_grad_scores = fn
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
     assert indptr.is_contiguous() and indices.is_contiguous()
     assert grad_out.dim() == 3 and feat.dim() == 3 and grad_out.is_contiguous() and feat.is_contiguous()
@@ -977,9 +903,10 @@ def launch_attn_aggregate_grad_scores_csr(indptr, indices, num_rows: int, grad_o
     for t in (m, l, delta):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (num_rows, heads)
     rc = ctypes.c_int(-1)
-    _attn_aggregate_grad_scores(indptr.data_ptr(), indices.data_ptr(), num_rows, nnz, heads, feat.shape[2], grad_out.data_ptr(),
-                                feat.data_ptr(), _dtype_code(feat.dtype), scores.data_ptr(), m.data_ptr(), l.data_ptr(), delta.data_ptr(),
-                                float(scale), out.data_ptr(), stream, rc)
+    _bound("voltrix_launch_attn_aggregate_grad_scores_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, nnz, heads, feat.shape[2],
+                                                            grad_out.data_ptr(), feat.data_ptr(), _dtype_code(feat.dtype),
+                                                            scores.data_ptr(), m.data_ptr(), l.data_ptr(), delta.data_ptr(), float(scale),
+                                                            out.data_ptr(), stream, rc)
     check(rc.value, "voltrix_launch_attn_aggregate_grad_scores_csr")
 
 
@@ -990,13 +917,6 @@ def launch_attn_aggregate_grad_feat_csr(t_indptr, t_indices, order, num_cols: in
     [num_cols, H, D]; see include/voltrix_capi.h."""
     import torch
 
-    global _attn_aggregate_grad_feat
-    if _attn_aggregate_grad_feat is None:
-        fn = lib().voltrix_launch_attn_aggregate_grad_feat_csr
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _attn_aggregate_grad_feat = fn
     assert t_indptr.dtype == torch.int32 and t_indices.dtype == torch.int32 and t_indptr.numel() == num_cols + 1
     assert t_indptr.is_contiguous() and t_indices.is_contiguous()
     nnz = t_indices.numel()
@@ -1008,9 +928,10 @@ def launch_attn_aggregate_grad_feat_csr(t_indptr, t_indices, order, num_cols: in
     for t in (m, l):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (grad_out.shape[0], heads)
     rc = ctypes.c_int(-1)
-    _attn_aggregate_grad_feat(t_indptr.data_ptr(), t_indices.data_ptr(), order.data_ptr(), num_cols, nnz, heads, grad_out.shape[2],
-                              grad_out.data_ptr(), _dtype_code(grad_out.dtype), scores.data_ptr(), m.data_ptr(), l.data_ptr(),
-                              float(scale), out.data_ptr(), stream, rc)
+    _bound("voltrix_launch_attn_aggregate_grad_feat_csr")(t_indptr.data_ptr(), t_indices.data_ptr(), order.data_ptr(), num_cols, nnz, heads,
+                                                          grad_out.shape[2], grad_out.data_ptr(), _dtype_code(grad_out.dtype),
+                                                          scores.data_ptr(), m.data_ptr(), l.data_ptr(), float(scale), out.data_ptr(),
+                                                          stream, rc)
     check(rc.value, "voltrix_launch_attn_aggregate_grad_feat_csr")
 
 
@@ -1019,21 +940,12 @@ def launch_scatter_values(values, slots, plane, stream) -> None:
     include/voltrix_capi.h."""
     import torch
 
-    global _scatter_values
-    if _scatter_values is None:
-        fn = lib().voltrix_launch_scatter_values
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
-                       ctypes.POINTER(ctypes.c_int)]
-        _scatter_values = fn
     assert values.dtype == torch.float32 and slots.dtype == torch.int64 and values.numel() == slots.numel()
     assert values.is_contiguous() and slots.is_contiguous() and plane.is_contiguous() and values.is_cuda and plane.is_cuda
     dtype = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[plane.dtype]
     rc = ctypes.c_int(-1)
-    _scatter_values(values.data_ptr(), slots.data_ptr(), plane.data_ptr(), values.numel(), dtype, stream, rc)
+    _bound("voltrix_launch_scatter_values")(values.data_ptr(), slots.data_ptr(), plane.data_ptr(), values.numel(), dtype, stream, rc)
     check(rc.value, "voltrix_launch_scatter_values")
-
-
-_scale_rows = None
 
 
 def launch_scale_rows(src, scale, dst, stream) -> None:
@@ -1041,17 +953,11 @@ def launch_scale_rows(src, scale, dst, stream) -> None:
     allowed); see include/voltrix_capi.h."""
     import torch
 
-    global _scale_rows
-    if _scale_rows is None:
-        fn = lib().voltrix_launch_scale_rows
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                       ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
-        _scale_rows = fn
     assert src.dim() == 2 and src.is_contiguous() and dst.is_contiguous() and dst.shape == src.shape and dst.dtype == src.dtype
     assert scale.dtype == torch.float32 and scale.numel() == src.shape[0] and scale.is_contiguous()
     dtype = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[src.dtype]
     rc = ctypes.c_int(-1)
-    _scale_rows(src.data_ptr(), scale.data_ptr(), dst.data_ptr(), src.shape[0], src.shape[1], dtype, stream, rc)
+    _bound("voltrix_launch_scale_rows")(src.data_ptr(), scale.data_ptr(), dst.data_ptr(), src.shape[0], src.shape[1], dtype, stream, rc)
     check(rc.value, "voltrix_launch_scale_rows")
 
 

@@ -20,23 +20,18 @@ from __future__ import annotations
 
 import torch
 
-from .sddmm import _TYPES, _padded_heads
+from .utils import FEATURE_TYPES, padded_last_dim, piece_width
 
 
 def _pair(x: torch.Tensor, y: torch.Tensor):
     """``x`` and ``y`` [n, H, D] in one type the kernels take: as they are when they share fp32 / fp16 / bf16, else both as float32."""
     assert x.is_cuda and y.is_cuda and x.dim() == y.dim() and x.dim() in (2, 3) and x.shape[1:] == y.shape[1:], (tuple(x.shape), tuple(y.shape))
-    if x.dtype != y.dtype or x.dtype not in _TYPES:
+    if x.dtype != y.dtype or x.dtype not in FEATURE_TYPES:
         x, y = x.float(), y.float()
     if x.dim() == 2:                      # the 2-D form is the H = 1 layout: the same kernel, the same bits
         x, y = x.unsqueeze(1), y.unsqueeze(1)
     assert x.shape[1] >= 1
     return x, y
-
-
-def _width(head_dim: int, dtype) -> int:
-    align = 4 if dtype == torch.float32 else 8
-    return (head_dim + align - 1) // align * align
 
 
 def gatv2_score(indptr: torch.Tensor, indices: torch.Tensor, xl: torch.Tensor, xr: torch.Tensor, a: torch.Tensor,
@@ -62,9 +57,9 @@ def gatv2_score(indptr: torch.Tensor, indices: torch.Tensor, xl: torch.Tensor, x
     if nnz > 0 and head_dim == 0:
         out.zero_()
     elif nnz > 0:
-        width = _width(head_dim, xl.dtype)
-        a = _padded_heads(a.float().reshape(1, heads, head_dim), width).view(heads, width)
-        capi.launch_gatv2_score_csr(indptr.contiguous(), indices.contiguous(), num_rows, _padded_heads(xl, width), _padded_heads(xr, width),
+        width = piece_width(head_dim, xl.dtype)
+        a = padded_last_dim(a.float().reshape(1, heads, head_dim), width).view(heads, width)
+        capi.launch_gatv2_score_csr(indptr.contiguous(), indices.contiguous(), num_rows, padded_last_dim(xl, width), padded_last_dim(xr, width),
                                     a, float(slope), out, _raw_stream(xl.device))
     return out.view(-1) if one_d else out
 
@@ -92,11 +87,11 @@ def gatv2_rowsum(indptr: torch.Tensor, indices: torch.Tensor, p: torch.Tensor, q
     if order is not None:
         assert order.is_cuda and order.numel() == nnz
         order = order.to(torch.int32).contiguous()
-    width = _width(head_dim, p.dtype)
+    width = piece_width(head_dim, p.dtype)
     out = torch.empty((num_rows, heads, width), dtype=torch.float32, device=p.device)
     if num_rows > 0 and head_dim > 0:
-        capi.launch_gatv2_rowsum_csr(indptr.contiguous(), indices.contiguous(), order, num_rows, _padded_heads(p, width),
-                                     _padded_heads(q, width), grad, float(slope), out, _raw_stream(p.device))
+        capi.launch_gatv2_rowsum_csr(indptr.contiguous(), indices.contiguous(), order, num_rows, padded_last_dim(p, width),
+                                     padded_last_dim(q, width), grad, float(slope), out, _raw_stream(p.device))
     if width != head_dim:
         out = out[:, :, :head_dim].contiguous()
     return out.view(num_rows, head_dim) if one_d else out

@@ -57,6 +57,7 @@
 #include <type_traits>
 
 #include "voltrix/edge_softmax_kernels.hpp"
+#include "voltrix/launch_geometry.hpp"
 #include "voltrix/sddmm_kernels.hpp"
 #include "voltrix/spmm_csr_kernels.hpp"
 
@@ -175,13 +176,11 @@ inline int attn_aggregate_check_shape(int num_rows, long long nnz, int heads, in
   if (num_rows < 0 || nnz < 0 || head_dim < 0 || heads < 1 || dtype < 0 || dtype > 2 || nnz > INT_MAX ||
       (long long)heads * head_dim > INT_MAX || !std::isfinite(scale))
     return kErrBadShape;
-  *v = dtype == 0 ? 4 : 8;
+  *v = piece_elems(dtype);
   if (head_dim % *v) return kErrBadShape;
   if (nnz > 0 && num_rows == 0) return kErrBadShape;
   return kOk;
 }
-
-inline bool attn_aggregate_bad_ptr(const void* p, uintptr_t mask) { return p == nullptr || ((uintptr_t)p & mask); }
 
 // dtype: 0 fp32, 1 fp16, 2 bfloat16.  head_dim % (16 / sizeof(T)) == 0.  Every element of output, m and l is written (rows without
 // entries: zeros, m = -inf, l = 0); with nnz == 0 indices, scores and input are not read.  Nothing is checked on the device: indptr
@@ -193,32 +192,24 @@ inline int launch_attn_aggregate_csr(const int* indptr, const int* indices, cons
   const int rc = attn_aggregate_check_shape(num_rows, nnz, heads, head_dim, dtype, scale, &v);
   if (rc != kOk) return rc;
   if (num_rows == 0 || head_dim == 0) return kOk;
-  if (attn_aggregate_bad_ptr(indptr, 3) || attn_aggregate_bad_ptr(output, 15) || attn_aggregate_bad_ptr(m, 3) ||
-      attn_aggregate_bad_ptr(l, 3))
+  if (bad_ptr(indptr, 3) || bad_ptr(output, 15) || bad_ptr(m, 3) ||
+      bad_ptr(l, 3))
     return kErrBadShape;
-  if (nnz > 0 && (attn_aggregate_bad_ptr(indices, 3) || attn_aggregate_bad_ptr(scores, 3) || attn_aggregate_bad_ptr(input, 15)))
+  if (nnz > 0 && (bad_ptr(indices, 3) || bad_ptr(scores, 3) || bad_ptr(input, 15)))
     return kErrBadShape;
   const int head_pieces = head_dim / v;
   const int pieces = heads * head_pieces;                // 16-byte pieces per row
-  const int slab_pieces = pieces < 64 ? pieces : 64;
-  int lanes = 1;
-  while (lanes < slab_pieces) lanes <<= 1;
-  const int slabs = (pieces + 63) / 64;
-  const int rows_per_group = 256 / lanes;
-  const long long groups = ((long long)num_rows + rows_per_group - 1) / rows_per_group;
-  const long long per_xcd = (groups + kNumXcd - 1) / kNumXcd;
-  if (per_xcd * kNumXcd > 0x7fffffffLL || slabs > 65535) return kErrBadShape;
+  const RowGroupGrid g = row_group_grid(num_rows, pieces);
+  if (!g.ok) return kErrBadShape;
   const int max_lanes = head_pieces <= 64 && (head_pieces & (head_pieces - 1)) == 0 ? head_pieces : 1;
-  const dim3 grid((unsigned)(per_xcd * kNumXcd), (unsigned)slabs);
+  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
   auto go = [&](auto tag) {
     using T = decltype(tag);
     const AttnAggregateArgs<T> a{indptr, indices, static_cast<const T*>(input), output, scores, m, l, num_rows, heads, head_pieces,
-                                 heads * head_dim, lanes, (int)per_xcd, max_lanes, scale < 0.0f ? -1.0f : 1.0f, std::fabs(scale)};
+                                 heads * head_dim, g.lanes, (int)g.per_xcd, max_lanes, scale < 0.0f ? -1.0f : 1.0f, std::fabs(scale)};
     hipLaunchKernelGGL((attn_aggregate_csr_kernel<T, 4>), grid, dim3(256), 0, stream, a);
   };
-  if (dtype == 0) go(float{});
-  else if (dtype == 1) go(_Float16{});
-  else go(bfloat16_bits{});
+  dispatch_feature_type(dtype, go);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
@@ -387,35 +378,23 @@ inline int launch_attn_aggregate_grad_scores_csr(const int* indptr, const int* i
   const int rc = attn_aggregate_check_shape(num_rows, nnz, heads, head_dim, dtype, scale, &v);
   if (rc != kOk) return rc;
   if (nnz == 0 || head_dim == 0) return kOk;
-  if (attn_aggregate_bad_ptr(indptr, 3) || attn_aggregate_bad_ptr(indices, 3) || attn_aggregate_bad_ptr(grad_out, 15) ||
-      attn_aggregate_bad_ptr(feat, 15) || attn_aggregate_bad_ptr(scores, 3) || attn_aggregate_bad_ptr(m, 3) ||
-      attn_aggregate_bad_ptr(l, 3) || attn_aggregate_bad_ptr(delta, 3) || attn_aggregate_bad_ptr(out, 3))
+  if (bad_ptr(indptr, 3) || bad_ptr(indices, 3) || bad_ptr(grad_out, 15) ||
+      bad_ptr(feat, 15) || bad_ptr(scores, 3) || bad_ptr(m, 3) ||
+      bad_ptr(l, 3) || bad_ptr(delta, 3) || bad_ptr(out, 3))
     return kErrBadShape;
   const int pieces = head_dim / v;
-  int head_lanes = 1, head_shift = 0;
-  while (head_lanes < pieces && head_lanes < 64) head_lanes <<= 1, ++head_shift;
-  const int rounds = (pieces + head_lanes - 1) / head_lanes;
-  const int slab_heads = heads < 64 / head_lanes ? heads : 64 / head_lanes;
-  int lanes = head_lanes;
-  while (lanes < slab_heads * head_lanes) lanes <<= 1;
-  const int slabs = (heads + slab_heads - 1) / slab_heads;
-  const long long chunks = (nnz + kSddmmChunkEdges - 1) / kSddmmChunkEdges;
-  const long long groups_per_wg = 256 / lanes;
-  const long long wgs = (chunks + groups_per_wg - 1) / groups_per_wg;
-  const long long per_xcd = (wgs + kNumXcd - 1) / kNumXcd;
-  if (per_xcd * kNumXcd > 0x7fffffffLL || slabs > 65535) return kErrBadShape;
+  const EdgeChunkGrid g = edge_chunk_grid(nnz, heads, pieces, kSddmmChunkEdges);
+  if (!g.ok) return kErrBadShape;
   const AttnAggregateGradScoresArgs a{indptr, indices, grad_out, feat, scores, m, l, delta, out, num_rows, (int)nnz, heads, pieces,
-                                      head_lanes, head_shift, rounds, slab_heads, lanes, wgs, per_xcd, scale,
+                                      g.head_lanes, g.head_shift, g.rounds, g.slab_heads, g.lanes, g.wgs, g.per_xcd, scale,
                                       scale < 0.0f ? -1.0f : 1.0f, std::fabs(scale)};
-  const dim3 grid((unsigned)(per_xcd * kNumXcd), (unsigned)slabs);
+  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
   auto go = [&](auto ytag) {
     using Y = decltype(ytag);
-    if (rounds == 1) hipLaunchKernelGGL((attn_aggregate_grad_scores_kernel<Y, 1>), grid, dim3(256), 0, stream, a);
+    if (g.rounds == 1) hipLaunchKernelGGL((attn_aggregate_grad_scores_kernel<Y, 1>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((attn_aggregate_grad_scores_kernel<Y, 0>), grid, dim3(256), 0, stream, a);
   };
-  if (dtype == 0) go(float{});
-  else if (dtype == 1) go(_Float16{});
-  else go(bfloat16_bits{});
+  dispatch_feature_type(dtype, go);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
@@ -509,31 +488,23 @@ inline int launch_attn_aggregate_grad_feat_csr(const int* t_indptr, const int* t
   const int rc = attn_aggregate_check_shape(num_rows, nnz, heads, head_dim, dtype, scale, &v);
   if (rc != kOk) return rc;
   if (num_rows == 0 || head_dim == 0) return kOk;
-  if (attn_aggregate_bad_ptr(t_indptr, 3) || attn_aggregate_bad_ptr(out, 15)) return kErrBadShape;
-  if (nnz > 0 && (attn_aggregate_bad_ptr(t_indices, 3) || attn_aggregate_bad_ptr(order, 3) || attn_aggregate_bad_ptr(grad_out, 15) ||
-                  attn_aggregate_bad_ptr(scores, 3) || attn_aggregate_bad_ptr(m, 3) || attn_aggregate_bad_ptr(l, 3)))
+  if (bad_ptr(t_indptr, 3) || bad_ptr(out, 15)) return kErrBadShape;
+  if (nnz > 0 && (bad_ptr(t_indices, 3) || bad_ptr(order, 3) || bad_ptr(grad_out, 15) ||
+                  bad_ptr(scores, 3) || bad_ptr(m, 3) || bad_ptr(l, 3)))
     return kErrBadShape;
   const int head_pieces = head_dim / v;
   const int pieces = heads * head_pieces;
-  const int slab_pieces = pieces < 64 ? pieces : 64;
-  int lanes = 1;
-  while (lanes < slab_pieces) lanes <<= 1;
-  const int slabs = (pieces + 63) / 64;
-  const int rows_per_group = 256 / lanes;
-  const long long groups = ((long long)num_rows + rows_per_group - 1) / rows_per_group;
-  const long long per_xcd = (groups + kNumXcd - 1) / kNumXcd;
-  if (per_xcd * kNumXcd > 0x7fffffffLL || slabs > 65535) return kErrBadShape;
-  const dim3 grid((unsigned)(per_xcd * kNumXcd), (unsigned)slabs);
+  const RowGroupGrid g = row_group_grid(num_rows, pieces);
+  if (!g.ok) return kErrBadShape;
+  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
   auto go = [&](auto tag) {
     using T = decltype(tag);
     const AttnAggregateGradFeatArgs<T> a{t_indptr, t_indices, order, static_cast<const T*>(grad_out), out, scores, m, l, num_rows,
-                                         heads, head_pieces, heads * head_dim, lanes, (int)per_xcd, scale < 0.0f ? -1.0f : 1.0f,
+                                         heads, head_pieces, heads * head_dim, g.lanes, (int)g.per_xcd, scale < 0.0f ? -1.0f : 1.0f,
                                          std::fabs(scale)};
     hipLaunchKernelGGL((attn_aggregate_grad_feat_kernel<T, 4>), grid, dim3(256), 0, stream, a);
   };
-  if (dtype == 0) go(float{});
-  else if (dtype == 1) go(_Float16{});
-  else go(bfloat16_bits{});
+  dispatch_feature_type(dtype, go);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

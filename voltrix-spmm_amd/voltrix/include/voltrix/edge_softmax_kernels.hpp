@@ -47,6 +47,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "voltrix/launch_geometry.hpp"
 #include "voltrix/spmm_kernels.hpp"
 
 namespace voltrix {
@@ -430,8 +431,7 @@ inline int edge_softmax_args(const int* indptr, int num_rows, long long nnz, con
   if (num_rows < 0 || nnz < 0 || nnz > INT_MAX || !std::isfinite(scale)) return kErrBadShape;
   args->chunks = 0;
   if (nnz == 0) return kOk;
-  if (num_rows == 0 || indptr == nullptr || in0 == nullptr || in1 == nullptr || out == nullptr || workspace == nullptr ||
-      ((uintptr_t)indptr & 3) || ((uintptr_t)in0 & 3) || ((uintptr_t)in1 & 3) || ((uintptr_t)out & 3) || ((uintptr_t)workspace & 15))
+  if (num_rows == 0 || bad_ptr(indptr, 3) || bad_ptr(in0, 3) || bad_ptr(in1, 3) || bad_ptr(out, 3) || bad_ptr(workspace, 15))
     return kErrBadShape;
   const long long chunks = edge_softmax_chunks(nnz);
   char* ws = static_cast<char*>(workspace);

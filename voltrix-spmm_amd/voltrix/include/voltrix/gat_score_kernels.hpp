@@ -60,6 +60,7 @@
 #include <cstdint>
 
 #include "voltrix/edge_softmax_kernels.hpp"
+#include "voltrix/launch_geometry.hpp"
 
 namespace voltrix {
 
@@ -371,8 +372,6 @@ static __global__ __launch_bounds__(kGatScoreThreads) void gat_score_rowsum_merg
   if (lane == 0) args.out[(long long)r * args.heads + head] = v;
 }
 
-inline bool gs_misaligned(const void* p, uintptr_t mask) { return p == nullptr || ((uintptr_t)p & mask) != 0; }
-
 // Checks shared by both launches, on the host and before any HIP call.
 inline int gat_score_check(int num_rows, long long nnz, int heads, float slope) {
   if (heads < 1 || heads > kGatScoreMaxHeads || num_rows < 0 || nnz < 0 || nnz > INT_MAX || !std::isfinite(slope)) return kErrBadShape;
@@ -387,7 +386,7 @@ inline int launch_gat_score_csr(const int* indptr, const int* indices, int num_r
                                 const float* er, float slope, float* out, hipStream_t stream) {
   const int rc = gat_score_check(num_rows, nnz, heads, slope);
   if (rc != kOk || nnz == 0) return rc;
-  if (gs_misaligned(indptr, 3) || gs_misaligned(indices, 3) || gs_misaligned(el, 3) || gs_misaligned(er, 3) || gs_misaligned(out, 3))
+  if (bad_ptr(indptr, 3) || bad_ptr(indices, 3) || bad_ptr(el, 3) || bad_ptr(er, 3) || bad_ptr(out, 3))
     return kErrBadShape;
   const GatScoreArgs a{indptr, indices, el, er, out, num_rows, (int)nnz, heads, slope};
   const dim3 grid((unsigned)edge_softmax_chunks(nnz)), block(kGatScoreThreads);
@@ -407,9 +406,9 @@ inline int launch_gat_score_rowsum_csr(const int* indptr, const int* indices, co
                                        hipStream_t stream) {
   const int rc = gat_score_check(num_rows, nnz, heads, slope);
   if (rc != kOk || num_rows == 0) return rc;
-  if (gs_misaligned(out, 3)) return kErrBadShape;
-  if (nnz > 0 && (gs_misaligned(indptr, 3) || gs_misaligned(indices, 3) || gs_misaligned(a, 3) || gs_misaligned(b, 3) ||
-                  gs_misaligned(g, 3) || gs_misaligned(workspace, 15) || ((uintptr_t)order & 3)))
+  if (bad_ptr(out, 3)) return kErrBadShape;
+  if (nnz > 0 && (bad_ptr(indptr, 3) || bad_ptr(indices, 3) || bad_ptr(a, 3) || bad_ptr(b, 3) ||
+                  bad_ptr(g, 3) || bad_ptr(workspace, 15) || misaligned(order, 3)))
     return kErrBadShape;
   const long long chunks = edge_softmax_chunks(nnz);
   const long long chunks8 = (chunks + kNumXcd - 1) / kNumXcd * kNumXcd;

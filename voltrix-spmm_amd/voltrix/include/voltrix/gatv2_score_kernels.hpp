@@ -214,37 +214,24 @@ inline int launch_gatv2_score_csr(const int* indptr, const int* indices, int num
   if (num_rows < 0 || nnz < 0 || head_dim < 0 || heads < 1 || nnz > INT_MAX || (long long)heads * head_dim > INT_MAX)
     return kErrBadShape;
   if (dtype < 0 || dtype > 2 || !std::isfinite(slope)) return kErrBadShape;
-  const int v = dtype == 0 ? 4 : 8;
+  const int v = piece_elems(dtype);
   if (head_dim % v) return kErrBadShape;
   if (nnz == 0 || head_dim == 0) return kOk;
-  if (num_rows == 0 || indptr == nullptr || indices == nullptr || xl == nullptr || xr == nullptr || a == nullptr || out == nullptr ||
-      ((uintptr_t)indptr & 3) || ((uintptr_t)indices & 3) || ((uintptr_t)xl & 15) || ((uintptr_t)xr & 15) || ((uintptr_t)a & 15) ||
-      ((uintptr_t)out & 3))
+  if (num_rows == 0 || bad_ptr(indptr, 3) || bad_ptr(indices, 3) || bad_ptr(xl, 15) || bad_ptr(xr, 15) || bad_ptr(a, 15) ||
+      bad_ptr(out, 3))
     return kErrBadShape;
   const int pieces = head_dim / v;
-  int head_lanes = 1, head_shift = 0;
-  while (head_lanes < pieces && head_lanes < 64) head_lanes <<= 1, ++head_shift;
-  const int rounds = (pieces + head_lanes - 1) / head_lanes;
-  const int slab_heads = heads < 64 / head_lanes ? heads : 64 / head_lanes;
-  int lanes = head_lanes;
-  while (lanes < slab_heads * head_lanes) lanes <<= 1;
-  const int slabs = (heads + slab_heads - 1) / slab_heads;
-  const long long chunks = (nnz + kSddmmChunkEdges - 1) / kSddmmChunkEdges;
-  const long long groups_per_wg = 256 / lanes;
-  const long long wgs = (chunks + groups_per_wg - 1) / groups_per_wg;
-  const long long per_xcd = (wgs + kNumXcd - 1) / kNumXcd;
-  if (per_xcd * kNumXcd > 0x7fffffffLL || slabs > 65535) return kErrBadShape;
-  const Gatv2ScoreArgs args{indptr, indices, xl, xr, a, out, num_rows, (int)nnz, heads, pieces, head_lanes, head_shift, rounds,
-                            slab_heads, lanes, slope, wgs, per_xcd};
-  const dim3 grid((unsigned)(per_xcd * kNumXcd), (unsigned)slabs);
+  const EdgeChunkGrid grid_of = edge_chunk_grid(nnz, heads, pieces, kSddmmChunkEdges);
+  if (!grid_of.ok) return kErrBadShape;
+  const Gatv2ScoreArgs args{indptr, indices, xl, xr, a, out, num_rows, (int)nnz, heads, pieces, grid_of.head_lanes, grid_of.head_shift,
+                            grid_of.rounds, grid_of.slab_heads, grid_of.lanes, slope, grid_of.wgs, grid_of.per_xcd};
+  const dim3 grid((unsigned)(grid_of.per_xcd * kNumXcd), (unsigned)grid_of.slabs);
   auto go = [&](auto tag) {
     using T = decltype(tag);
-    if (rounds == 1) hipLaunchKernelGGL((gatv2_score_csr_kernel<T, 1>), grid, dim3(256), 0, stream, args);
+    if (grid_of.rounds == 1) hipLaunchKernelGGL((gatv2_score_csr_kernel<T, 1>), grid, dim3(256), 0, stream, args);
     else hipLaunchKernelGGL((gatv2_score_csr_kernel<T, 0>), grid, dim3(256), 0, stream, args);
   };
-  if (dtype == 0) go(float{});
-  else if (dtype == 1) go(_Float16{});
-  else go(bfloat16_bits{});
+  dispatch_feature_type(dtype, go);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
@@ -327,34 +314,25 @@ inline int launch_gatv2_rowsum_csr(const int* indptr, const int* indices, const 
   if (num_rows < 0 || nnz < 0 || head_dim < 0 || heads < 1 || nnz > INT_MAX || (long long)heads * head_dim > INT_MAX)
     return kErrBadShape;
   if (dtype < 0 || dtype > 2 || !std::isfinite(slope)) return kErrBadShape;
-  const int v = dtype == 0 ? 4 : 8;
+  const int v = piece_elems(dtype);
   if (head_dim % v) return kErrBadShape;
   if (nnz > 0 && num_rows == 0) return kErrBadShape;
   if (num_rows == 0 || head_dim == 0) return kOk;
-  if (indptr == nullptr || p == nullptr || out == nullptr || ((uintptr_t)indptr & 3) || ((uintptr_t)p & 15) || ((uintptr_t)out & 15))
-    return kErrBadShape;
+  if (bad_ptr(indptr, 3) || bad_ptr(p, 15) || bad_ptr(out, 15)) return kErrBadShape;
   if (nnz > 0 && (indices == nullptr || q == nullptr || g == nullptr)) return kErrBadShape;
-  if (((uintptr_t)indices & 3) || ((uintptr_t)order & 3) || ((uintptr_t)q & 15) || ((uintptr_t)g & 3)) return kErrBadShape;
+  if (misaligned(indices, 3) || misaligned(order, 3) || misaligned(q, 15) || misaligned(g, 3)) return kErrBadShape;
   const int head_pieces = head_dim / v;
   const int pieces = heads * head_pieces;                // 16-byte pieces per row
-  const int slab_pieces = pieces < 64 ? pieces : 64;
-  int lanes = 1;
-  while (lanes < slab_pieces) lanes <<= 1;
-  const int slabs = (pieces + 63) / 64;
-  const int rows_per_group = 256 / lanes;
-  const long long groups = ((long long)num_rows + rows_per_group - 1) / rows_per_group;
-  const long long per_xcd = (groups + kNumXcd - 1) / kNumXcd;
-  if (per_xcd * kNumXcd > 0x7fffffffLL || slabs > 65535) return kErrBadShape;
-  const dim3 grid((unsigned)(per_xcd * kNumXcd), (unsigned)slabs);
+  const RowGroupGrid grid_of = row_group_grid(num_rows, pieces);
+  if (!grid_of.ok) return kErrBadShape;
+  const dim3 grid((unsigned)(grid_of.per_xcd * kNumXcd), (unsigned)grid_of.slabs);
   auto go = [&](auto tag) {
     using T = decltype(tag);
-    const Gatv2RowsumArgs<T> args{indptr,   indices, order,       static_cast<const T*>(p), static_cast<const T*>(q), g,           out,
-                                  num_rows, heads,   head_pieces, heads * head_dim,         lanes,                    (int)per_xcd, slope};
+    const Gatv2RowsumArgs<T> args{indptr, indices, order, static_cast<const T*>(p), static_cast<const T*>(q), g, out, num_rows, heads,
+                                  head_pieces, heads * head_dim, grid_of.lanes, (int)grid_of.per_xcd, slope};
     hipLaunchKernelGGL((gatv2_rowsum_csr_kernel<T, 4>), grid, dim3(256), 0, stream, args);
   };
-  if (dtype == 0) go(float{});
-  else if (dtype == 1) go(_Float16{});
-  else go(bfloat16_bits{});
+  dispatch_feature_type(dtype, go);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

@@ -176,42 +176,25 @@ inline int launch_sddmm_heads_csr(const int* indptr, const int* indices, int num
                                   const void* x, int x_dtype, const void* y, int y_dtype, float* out, hipStream_t stream) {
   if (num_rows < 0 || nnz < 0 || head_dim < 0 || heads < 1 || nnz > INT_MAX || (long long)heads * head_dim > INT_MAX)
     return kErrBadShape;
-  const bool pair_ok = (x_dtype == 0 && (y_dtype == 0 || y_dtype == 1 || y_dtype == 2)) || (x_dtype == 1 && y_dtype == 1) ||
-                       (x_dtype == 2 && y_dtype == 2);
-  if (!pair_ok) return kErrBadShape;
-  const int v = y_dtype == 0 ? 4 : 8;
+  if (!sddmm_pair_ok(x_dtype, y_dtype)) return kErrBadShape;
+  const int v = piece_elems(y_dtype);
   if (head_dim % v) return kErrBadShape;
   if (nnz == 0 || head_dim == 0) return kOk;
-  if (num_rows == 0 || indptr == nullptr || indices == nullptr || x == nullptr || y == nullptr || out == nullptr ||
-      ((uintptr_t)indptr & 3) || ((uintptr_t)indices & 3) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)out & 3))
+  if (num_rows == 0 || bad_ptr(indptr, 3) || bad_ptr(indices, 3) || bad_ptr(x, 15) || bad_ptr(y, 15) || bad_ptr(out, 3))
     return kErrBadShape;
   const int pieces = head_dim / v;
-  int head_lanes = 1, head_shift = 0;
-  while (head_lanes < pieces && head_lanes < 64) head_lanes <<= 1, ++head_shift;
-  const int rounds = (pieces + head_lanes - 1) / head_lanes;
-  const int slab_heads = heads < 64 / head_lanes ? heads : 64 / head_lanes;
-  int lanes = head_lanes;
-  while (lanes < slab_heads * head_lanes) lanes <<= 1;
-  const int slabs = (heads + slab_heads - 1) / slab_heads;
-  const long long chunks = (nnz + kSddmmChunkEdges - 1) / kSddmmChunkEdges;
-  const long long groups_per_wg = 256 / lanes;
-  const long long wgs = (chunks + groups_per_wg - 1) / groups_per_wg;
-  const long long per_xcd = (wgs + kNumXcd - 1) / kNumXcd;
-  if (per_xcd * kNumXcd > 0x7fffffffLL || slabs > 65535) return kErrBadShape;
-  const SddmmHeadsArgs a{indptr, indices, x, y, out, num_rows, (int)nnz, heads, pieces, head_lanes, head_shift, rounds, slab_heads,
-                         lanes, wgs, per_xcd};
-  const dim3 grid((unsigned)(per_xcd * kNumXcd), (unsigned)slabs);
+  const EdgeChunkGrid g = edge_chunk_grid(nnz, heads, pieces, kSddmmChunkEdges);
+  if (!g.ok) return kErrBadShape;
+  const SddmmHeadsArgs a{indptr, indices, x, y, out, num_rows, (int)nnz, heads, pieces, g.head_lanes, g.head_shift, g.rounds,
+                         g.slab_heads, g.lanes, g.wgs, g.per_xcd};
+  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
   auto go = [&](auto xtag, auto ytag) {
     using X = decltype(xtag);
     using Y = decltype(ytag);
-    if (rounds == 1) hipLaunchKernelGGL((sddmm_heads_csr_kernel<X, Y, 1>), grid, dim3(256), 0, stream, a);
+    if (g.rounds == 1) hipLaunchKernelGGL((sddmm_heads_csr_kernel<X, Y, 1>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((sddmm_heads_csr_kernel<X, Y, 0>), grid, dim3(256), 0, stream, a);
   };
-  if (x_dtype == 0 && y_dtype == 0) go(float{}, float{});
-  else if (x_dtype == 0 && y_dtype == 1) go(float{}, _Float16{});
-  else if (x_dtype == 0) go(float{}, bfloat16_bits{});
-  else if (x_dtype == 1) go(_Float16{}, _Float16{});
-  else go(bfloat16_bits{}, bfloat16_bits{});
+  dispatch_sddmm_pair(x_dtype, y_dtype, go);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

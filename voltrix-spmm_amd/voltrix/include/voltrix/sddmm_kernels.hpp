@@ -28,6 +28,7 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "voltrix/launch_geometry.hpp"
 #include "voltrix/spmm_kernels.hpp"
 
 namespace voltrix {
@@ -205,39 +206,25 @@ static __global__ __launch_bounds__(256) void sddmm_csr_kernel(const SddmmArgs a
 inline int launch_sddmm_csr(const int* indptr, const int* indices, int num_rows, long long nnz, int embedding_dim, const void* x,
                             int x_dtype, const void* y, int y_dtype, float* out, hipStream_t stream) {
   if (num_rows < 0 || nnz < 0 || embedding_dim < 0 || nnz > INT_MAX) return kErrBadShape;
-  const bool pair_ok = (x_dtype == 0 && (y_dtype == 0 || y_dtype == 1 || y_dtype == 2)) || (x_dtype == 1 && y_dtype == 1) ||
-                       (x_dtype == 2 && y_dtype == 2);
-  if (!pair_ok) return kErrBadShape;
-  const int v = y_dtype == 0 ? 4 : 8;
+  if (!sddmm_pair_ok(x_dtype, y_dtype)) return kErrBadShape;
+  const int v = piece_elems(y_dtype);
   if (embedding_dim % v) return kErrBadShape;
   if (nnz == 0 || embedding_dim == 0) return kOk;
-  if (num_rows == 0 || indptr == nullptr || indices == nullptr || x == nullptr || y == nullptr || out == nullptr ||
-      ((uintptr_t)indptr & 3) || ((uintptr_t)indices & 3) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)out & 3))
+  if (num_rows == 0 || bad_ptr(indptr, 3) || bad_ptr(indices, 3) || bad_ptr(x, 15) || bad_ptr(y, 15) || bad_ptr(out, 3))
     return kErrBadShape;
   const int pieces = embedding_dim / v;
-  const int slab = pieces < 64 ? pieces : 64;
-  int lanes = 1;
-  while (lanes < slab) lanes <<= 1;
-  const int rounds = (pieces + lanes - 1) / lanes;
-  const long long chunks = (nnz + kSddmmChunkEdges - 1) / kSddmmChunkEdges;
-  const long long groups_per_wg = 256 / lanes;
-  const long long wgs = (chunks + groups_per_wg - 1) / groups_per_wg;
-  const long long per_xcd = (wgs + kNumXcd - 1) / kNumXcd;
-  if (per_xcd * kNumXcd > 0x7fffffffLL) return kErrBadShape;
-  const SddmmArgs a{indptr, indices, x, y, out, num_rows, (int)nnz, embedding_dim, pieces, lanes, rounds, wgs, per_xcd};
-  const dim3 grid((unsigned)(per_xcd * kNumXcd));
+  const EdgeChunkGrid g = edge_chunk_grid(nnz, 1, pieces, kSddmmChunkEdges);      // one head: one slab, lanes == head_lanes
+  if (!g.ok) return kErrBadShape;
+  const SddmmArgs a{indptr, indices, x, y, out, num_rows, (int)nnz, embedding_dim, pieces, g.lanes, g.rounds, g.wgs, g.per_xcd};
+  const dim3 grid((unsigned)(g.per_xcd * kNumXcd));
   auto go = [&](auto xtag, auto ytag) {
     using X = decltype(xtag);
     using Y = decltype(ytag);
-    if (rounds == 1) hipLaunchKernelGGL((sddmm_csr_kernel<X, Y, 1>), grid, dim3(256), 0, stream, a);
-    else if (rounds == 2) hipLaunchKernelGGL((sddmm_csr_kernel<X, Y, 2>), grid, dim3(256), 0, stream, a);
+    if (g.rounds == 1) hipLaunchKernelGGL((sddmm_csr_kernel<X, Y, 1>), grid, dim3(256), 0, stream, a);
+    else if (g.rounds == 2) hipLaunchKernelGGL((sddmm_csr_kernel<X, Y, 2>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((sddmm_csr_kernel<X, Y, 0>), grid, dim3(256), 0, stream, a);
   };
-  if (x_dtype == 0 && y_dtype == 0) go(float{}, float{});
-  else if (x_dtype == 0 && y_dtype == 1) go(float{}, _Float16{});
-  else if (x_dtype == 0) go(float{}, bfloat16_bits{});
-  else if (x_dtype == 1) go(_Float16{}, _Float16{});
-  else go(bfloat16_bits{}, bfloat16_bits{});
+  dispatch_sddmm_pair(x_dtype, y_dtype, go);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

@@ -25,6 +25,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "voltrix/launch_geometry.hpp"
 #include "voltrix/spmm_csr_kernels.hpp"
 
 namespace voltrix {
@@ -103,32 +104,22 @@ static __global__ __launch_bounds__(256) void spmm_csr_heads_kernel(const CsrHea
 inline int launch_spmm_csr_heads(const int* indptr, const int* indices, const float* values, int num_rows, int heads, int head_dim,
                                  const void* input, int dtype, float* output, hipStream_t stream) {
   if (num_rows < 0 || head_dim < 0 || heads < 1 || dtype < 0 || dtype > 2 || (long long)heads * head_dim > INT_MAX) return kErrBadShape;
-  const int v = dtype == 0 ? 4 : 8;
+  const int v = piece_elems(dtype);
   if (head_dim % v) return kErrBadShape;
   if (num_rows == 0 || head_dim == 0) return kOk;
-  if (indptr == nullptr || indices == nullptr || values == nullptr || input == nullptr || output == nullptr || ((uintptr_t)indptr & 3) ||
-      ((uintptr_t)indices & 3) || ((uintptr_t)values & 3) || ((uintptr_t)input & 15) || ((uintptr_t)output & 15))
-    return kErrBadShape;
+  if (bad_ptr(indptr, 3) || bad_ptr(indices, 3) || bad_ptr(values, 3) || bad_ptr(input, 15) || bad_ptr(output, 15)) return kErrBadShape;
   const int head_pieces = head_dim / v;
   const int pieces = heads * head_pieces;                // 16-byte pieces per row
-  const int slab_pieces = pieces < 64 ? pieces : 64;
-  int lanes = 1;
-  while (lanes < slab_pieces) lanes <<= 1;
-  const int slabs = (pieces + 63) / 64;
-  const int rows_per_group = 256 / lanes;
-  const long long groups = ((long long)num_rows + rows_per_group - 1) / rows_per_group;
-  const long long per_xcd = (groups + kNumXcd - 1) / kNumXcd;
-  if (per_xcd * kNumXcd > 0x7fffffffLL || slabs > 65535) return kErrBadShape;
-  const dim3 grid((unsigned)(per_xcd * kNumXcd), (unsigned)slabs);
+  const RowGroupGrid g = row_group_grid(num_rows, pieces);
+  if (!g.ok) return kErrBadShape;
+  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
   auto go = [&](auto tag) {
     using T = decltype(tag);
     const CsrHeadsArgs<T> a{indptr, indices, static_cast<const T*>(input), output, values, num_rows, heads, head_pieces,
-                            heads * head_dim, lanes, (int)per_xcd};
+                            heads * head_dim, g.lanes, (int)g.per_xcd};
     hipLaunchKernelGGL((spmm_csr_heads_kernel<T, 4>), grid, dim3(256), 0, stream, a);
   };
-  if (dtype == 0) go(float{});
-  else if (dtype == 1) go(_Float16{});
-  else go(bfloat16_bits{});
+  dispatch_feature_type(dtype, go);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

@@ -27,6 +27,7 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "voltrix/launch_geometry.hpp"
 #include "voltrix/spmm_kernels.hpp"
 
 namespace voltrix {
@@ -150,10 +151,8 @@ inline int launch_spmm_csr_rows(const int* indptr, const int* indices, int num_r
                                 float* output, hipStream_t stream, int xcd_ranges = 0, const float* values = nullptr) {
   if (num_rows < 0 || embedding_dim < 0 || dtype < 0 || dtype > 2) return kErrBadShape;
   if (num_rows == 0 || embedding_dim == 0) return kOk;
-  const int v = dtype == 0 ? 4 : 8;
-  if (embedding_dim % v || indptr == nullptr || input == nullptr || output == nullptr || ((uintptr_t)input & 15) ||
-      ((uintptr_t)output & 15))
-    return kErrBadShape;
+  const int v = piece_elems(dtype);
+  if (embedding_dim % v || indptr == nullptr || bad_ptr(input, 15) || bad_ptr(output, 15)) return kErrBadShape;
   const int pieces = embedding_dim / v;                  // 16-byte pieces per row
   const int slab_pieces = pieces < 64 ? pieces : 64;
   int lanes = 1;
@@ -173,9 +172,7 @@ inline int launch_spmm_csr_rows(const int* indptr, const int* indices, int num_r
     else
       hipLaunchKernelGGL((spmm_csr_rows_kernel<T, 4, false>), grid, dim3(256), 0, stream, a);
   };
-  if (dtype == 0) go(float{});
-  else if (dtype == 1) go(_Float16{});
-  else go(bfloat16_bits{});
+  dispatch_feature_type(dtype, go);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

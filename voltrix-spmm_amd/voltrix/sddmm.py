@@ -13,19 +13,10 @@ from __future__ import annotations
 
 import torch
 
-from .utils import aligned16
+from .utils import FEATURE_TYPES, padded_last_dim, piece_width
 
 _PAIRS = {(torch.float32, torch.float16), (torch.float32, torch.bfloat16), (torch.float16, torch.float16),
           (torch.bfloat16, torch.bfloat16), (torch.float32, torch.float32)}
-_TYPES = (torch.float32, torch.float16, torch.bfloat16)
-
-
-def _padded(t: torch.Tensor, width: int) -> torch.Tensor:
-    """``t`` contiguous, 16-byte aligned, its rows padded with zeros to ``width`` columns."""
-    t = t.contiguous()
-    if width != t.shape[1]:
-        t = torch.nn.functional.pad(t, (0, width - t.shape[1]))
-    return aligned16(t)
 
 
 def sddmm(indptr: torch.Tensor, indices: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
@@ -46,7 +37,7 @@ def sddmm(indptr: torch.Tensor, indices: torch.Tensor, x: torch.Tensor, y: torch
     num_rows = indptr.numel() - 1
     assert x.shape[0] == num_rows, (tuple(x.shape), num_rows)
     if (x.dtype, y.dtype) not in _PAIRS:
-        y = y if y.dtype in _TYPES else y.float()
+        y = y if y.dtype in FEATURE_TYPES else y.float()
         x = x.float()
     nnz = indices.numel()
     out = torch.empty(nnz, dtype=torch.float32, device=x.device)
@@ -55,19 +46,10 @@ def sddmm(indptr: torch.Tensor, indices: torch.Tensor, x: torch.Tensor, y: torch
         return out
     if num_feats == 0:
         return out.zero_()
-    align = 4 if (x.dtype, y.dtype) == (torch.float32, torch.float32) else 8
-    width = (num_feats + align - 1) // align * align
-    capi.launch_sddmm_csr(indptr.contiguous(), indices.contiguous(), num_rows, _padded(x, width), _padded(y, width), out,
+    width = piece_width(num_feats, (x.dtype, y.dtype))
+    capi.launch_sddmm_csr(indptr.contiguous(), indices.contiguous(), num_rows, padded_last_dim(x, width), padded_last_dim(y, width), out,
                           _raw_stream(x.device))
     return out
-
-
-def _padded_heads(t: torch.Tensor, width: int) -> torch.Tensor:
-    """``t`` [n, H, D] contiguous, 16-byte aligned, every head padded with zeros to ``width`` columns."""
-    t = t.contiguous()
-    if width != t.shape[2]:
-        t = torch.nn.functional.pad(t, (0, width - t.shape[2]))
-    return aligned16(t)
 
 
 def _sddmm_heads(indptr: torch.Tensor, indices: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
@@ -79,7 +61,7 @@ def _sddmm_heads(indptr: torch.Tensor, indices: torch.Tensor, x: torch.Tensor, y
     num_rows = indptr.numel() - 1
     assert x.shape[0] == num_rows, (tuple(x.shape), num_rows)
     if (x.dtype, y.dtype) not in _PAIRS:
-        y = y if y.dtype in _TYPES else y.float()
+        y = y if y.dtype in FEATURE_TYPES else y.float()
         x = x.float()
     nnz, heads, head_dim = indices.numel(), x.shape[1], x.shape[2]
     assert heads >= 1
@@ -88,9 +70,8 @@ def _sddmm_heads(indptr: torch.Tensor, indices: torch.Tensor, x: torch.Tensor, y
         return out
     if head_dim == 0:
         return out.zero_()
-    align = 4 if (x.dtype, y.dtype) == (torch.float32, torch.float32) else 8
-    width = (head_dim + align - 1) // align * align
-    capi.launch_sddmm_heads_csr(indptr.contiguous(), indices.contiguous(), num_rows, _padded_heads(x, width), _padded_heads(y, width),
+    width = piece_width(head_dim, (x.dtype, y.dtype))
+    capi.launch_sddmm_heads_csr(indptr.contiguous(), indices.contiguous(), num_rows, padded_last_dim(x, width), padded_last_dim(y, width),
                                 out, _raw_stream(x.device))
     return out
 
@@ -110,7 +91,7 @@ def spmm_heads(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor
     assert indptr.is_cuda and indices.is_cuda and indptr.dtype == torch.int32 and indices.dtype == torch.int32
     assert feat.is_cuda and values.is_cuda and feat.dim() == 3 and values.dim() == 2, (tuple(feat.shape), tuple(values.shape))
     assert indptr.numel() == num_rows + 1 and values.shape == (indices.numel(), feat.shape[1]), (tuple(values.shape), tuple(feat.shape))
-    if feat.dtype not in _TYPES:
+    if feat.dtype not in FEATURE_TYPES:
         feat = feat.float()
     heads, head_dim = feat.shape[1], feat.shape[2]
     assert heads >= 1
@@ -119,11 +100,10 @@ def spmm_heads(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor
     if heads == 1:      # one head is the single-head layout: its kernel, measured faster at H = 1, the same bits
         return csr_values_product(indptr.contiguous(), indices.contiguous(), values.reshape(-1), num_rows,
                                   feat.reshape(feat.shape[0], head_dim)).view(num_rows, 1, head_dim)
-    align = 4 if feat.dtype == torch.float32 else 8
-    width = (head_dim + align - 1) // align * align
+    width = piece_width(head_dim, feat.dtype)
     output = torch.empty((num_rows, heads, width), dtype=torch.float32, device=feat.device)
     capi.launch_spmm_csr_heads(indptr.contiguous(), indices.contiguous(), values.float().contiguous(), num_rows,
-                               _padded_heads(feat, width), output, _raw_stream(feat.device))
+                               padded_last_dim(feat, width), output, _raw_stream(feat.device))
     return output if width == head_dim else output[:, :, :head_dim].contiguous()
 
 
@@ -134,14 +114,13 @@ def csr_values_product(indptr: torch.Tensor, indices: torch.Tensor, values: torc
     from . import capi
     from .jit_kernels.spmm import _raw_stream
 
-    if feat.dtype not in _TYPES:
+    if feat.dtype not in FEATURE_TYPES:
         feat = feat.float()
     num_feats = feat.shape[1]
     if indices.numel() == 0 or num_feats == 0 or num_rows == 0:
         return torch.zeros(num_rows, num_feats, dtype=torch.float32, device=feat.device)
-    align = 4 if feat.dtype == torch.float32 else 8
-    width = (num_feats + align - 1) // align * align
+    width = piece_width(num_feats, feat.dtype)
     output = torch.empty((num_rows, width), dtype=torch.float32, device=feat.device)
-    capi.launch_spmm_csr_rows(indptr, indices, num_rows, _padded(feat, width), output, _raw_stream(feat.device), 1,
+    capi.launch_spmm_csr_rows(indptr, indices, num_rows, padded_last_dim(feat, width), output, _raw_stream(feat.device), 1,
                               values=values.float().contiguous())
     return output if width == num_feats else output[:, :num_feats].contiguous()

@@ -17,7 +17,7 @@ from ..jit_kernels import (
 )
 from .. import capi, hybrid, sidecar
 from ..project import CSR_PATH_FLAG, FP32_MODE_FLAG, PREPROCESS_FLAG
-from ..utils import aligned16
+from ..utils import aligned16, padded_last_dim, piece_width
 
 BLK_H = 16
 BLK_W = 8
@@ -329,14 +329,10 @@ def _spmm_csr(csr, feat: torch.Tensor) -> torch.Tensor:
     """``csr(ones) @ feat`` with the CSR row-gather kernel: fp32 / fp16 / bf16 rows as they are (no cast pass), fp32 result."""
     from ..jit_kernels.spmm import _raw_stream
 
-    feat = feat.contiguous()
     num_feats = feat.shape[1]
-    align = 4 if feat.dtype == torch.float32 else 8
-    padded = (num_feats + align - 1) // align * align
-    if padded != num_feats:
-        feat = torch.nn.functional.pad(feat, (0, padded - num_feats))
+    padded = piece_width(num_feats, feat.dtype)
     output = torch.empty((csr.num_rows, padded), dtype=torch.float32, device=feat.device)
-    capi.launch_spmm_csr_rows(csr.indptr, csr.indices, csr.num_rows, aligned16(feat), output, _raw_stream(feat.device), 1)
+    capi.launch_spmm_csr_rows(csr.indptr, csr.indices, csr.num_rows, padded_last_dim(feat, padded), output, _raw_stream(feat.device), 1)
     return output if padded == num_feats else output[:, :num_feats].contiguous()
 
 

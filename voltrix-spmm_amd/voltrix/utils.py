@@ -26,6 +26,24 @@ def aligned16(t: torch.Tensor) -> torch.Tensor:
     return t.clone() if t.data_ptr() % 16 else t
 
 
+FEATURE_TYPES = (torch.float32, torch.float16, torch.bfloat16)      # what the CSR / attention kernels read as it is
+
+
+def piece_width(dim: int, dtype_or_pair) -> int:
+    """``dim`` rounded up to whole 16-byte pieces of a row: 4 elements for fp32 (for an operand pair: when both are), else 8."""
+    align = 4 if dtype_or_pair in (torch.float32, (torch.float32, torch.float32)) else 8
+    return (dim + align - 1) // align * align
+
+
+def padded_last_dim(t: torch.Tensor, width: int) -> torch.Tensor:
+    """``t`` contiguous, its last dimension padded with zeros to ``width``, 16-byte aligned (``aligned16``): ``t`` itself when it is all
+    that already."""
+    t = t.contiguous()
+    if width != t.shape[-1]:
+        t = torch.nn.functional.pad(t, (0, width - t.shape[-1]))
+    return aligned16(t)
+
+
 def relative_error(value: torch.Tensor, real: torch.Tensor, exclude_zeros: bool = True) -> float:
     value = value.double().flatten()
     real = real.double().flatten()

@@ -21,7 +21,7 @@ import dataclasses
 import torch
 
 from .jit_kernels import csr_fused_preprocess_kernel, spmm_kernel
-from .utils import aligned16
+from .utils import padded_last_dim, piece_width
 
 
 # A value plane is 512 B per TC block in fp32 (the master the 16-bit planes are rounded from) and 256 B in a 16-bit type.  Above
@@ -385,14 +385,11 @@ def _spmm_weighted_csr(handle: WeightedHandle, feat: torch.Tensor) -> torch.Tens
     from .jit_kernels.spmm import _raw_stream
 
     indptr, indices, values, _ = handle.csr
-    feat = feat.contiguous()
     num_feats = feat.shape[1]
-    align = 4 if feat.dtype == torch.float32 else 8
-    padded = (num_feats + align - 1) // align * align
-    if padded != num_feats:
-        feat = torch.nn.functional.pad(feat, (0, padded - num_feats))
+    padded = piece_width(num_feats, feat.dtype)
     output = torch.empty((handle.num_nodes, padded), dtype=torch.float32, device=feat.device)
-    capi.launch_spmm_csr_rows(indptr, indices, handle.num_nodes, aligned16(feat), output, _raw_stream(feat.device), 1, values=values)
+    capi.launch_spmm_csr_rows(indptr, indices, handle.num_nodes, padded_last_dim(feat, padded), output, _raw_stream(feat.device), 1,
+                              values=values)
     return output if padded == num_feats else output[:, :num_feats].contiguous()
 
 
@@ -480,13 +477,9 @@ def _spmm_separable(handle: WeightedHandle, feat: torch.Tensor, prescaled: bool 
     from .spmm.spmm import spmm
 
     assert feat.is_cuda and feat.dim() == 2 and feat.shape[0] == handle.col_scale.numel()
-    feat = feat.contiguous()
     num_feats = feat.shape[1]
-    align = 4 if feat.dtype == torch.float32 else 8
-    padded = (num_feats + align - 1) // align * align
-    if padded != num_feats:
-        feat = torch.nn.functional.pad(feat, (0, padded - num_feats))
-    feat = aligned16(feat)
+    padded = piece_width(num_feats, feat.dtype)
+    feat = padded_last_dim(feat, padded)
     stream = _raw_stream(feat.device)
     scaled = feat
     if not prescaled:
@@ -507,12 +500,8 @@ def scale_rows_of(feat: torch.Tensor, scale: torch.Tensor, in_place: bool = Fals
 
     assert feat.is_cuda and feat.dim() == 2 and scale.numel() == feat.shape[0] and scale.dtype == torch.float32
     num_feats = feat.shape[1]
-    align = 4 if feat.dtype == torch.float32 else 8
-    padded = (num_feats + align - 1) // align * align
-    src = feat.contiguous()
-    if padded != num_feats:
-        src = torch.nn.functional.pad(src, (0, padded - num_feats))
-    src = aligned16(src)
+    padded = piece_width(num_feats, feat.dtype)
+    src = padded_last_dim(feat, padded)
     dst = src if (in_place or src is not feat) else torch.empty_like(src)
     capi.launch_scale_rows(src, scale.contiguous(), dst, _raw_stream(feat.device))
     return dst if padded == num_feats else dst[:, :num_feats].contiguous()
