@@ -21,7 +21,12 @@ With a trailing argument ``fused`` the multi-head and the ``v2`` layers replace 
 ``voltrix.autograd.AttnAggregate``: one launch forward, the attention weights [nnz, H] are never stored and their gradient never exists.
 Without ``fused`` every run is unchanged.
 
-    python examples/gat_train.py [workload] [hidden] [epochs] [heads] [v2] [fused]   # synthetic stand-in graph, random features and labels
+With a trailing token ``attn_drop=P`` the attention weights are dropped with probability ``P`` while training (GAT's own recipe uses
+0.6) and left alone in evaluation.  The keep mask is one bit per edge and head (``voltrix.dropout_mask``, a fresh seed per layer and
+step from torch's generator); with ``fused`` it goes into ``AttnAggregate`` (nothing of size [nnz, H] but the scores exists), without
+it ``voltrix.apply_dropout_mask`` multiplies the stored ``alpha``.  Without the token every run is unchanged.
+
+    python examples/gat_train.py [workload] [hidden] [epochs] [heads] [v2] [fused] [attn_drop=P]   # synthetic graph, random features and labels
 """
 import os
 import sys
@@ -50,11 +55,11 @@ class Graph:
     the multi-head aggregation (no handle); every operator but the block-format ``SpMM`` shares one ``CsrPattern``.  ``rows`` / ``cols``
     (int64 row and column id of every edge) are built when something asks for them; the training run never does."""
 
-    def __init__(self, indptr, indices, n, hash_tag="example_gat", heads=1, v2=False, fused=False):
+    def __init__(self, indptr, indices, n, hash_tag="example_gat", heads=1, v2=False, fused=False, attn_drop=0.0):
         from voltrix.autograd import AttnAggregate, CsrPattern, EdgeSoftmax, GATScore, GATv2Score, SpMM, SpMMHeads
 
         assert not fused or v2 or heads > 1, "fused: the multi-head and the v2 layers"
-        self.n, self.heads, self.v2 = n, heads, v2
+        self.n, self.heads, self.v2, self.attn_drop = n, heads, v2, float(attn_drop)
         self._indptr, self._indices = indptr, indices
         self._rows = self._cols = None
         pattern = CsrPattern(indptr, indices, n)      # the device CSR and its transpose, once for every operator below
@@ -66,11 +71,25 @@ class Graph:
             self.aggregate = SpMM(indptr, indices, n, values=torch.ones(indices.numel(), device="cuda"), hash_tag=hash_tag)
         self.fused = AttnAggregate(pattern) if fused else None      # softmax and aggregation in one operator
 
-    def attend(self, feat, s):
-        """``aggregate(feat, softmax(s))``: scores [nnz, H], out [n, H, out_feats]; one operator with ``fused``."""
+    def drop(self, alpha, training):
+        """Attention dropout on stored weights ([nnz] or [nnz, H]): a packed keep mask, applied in torch."""
+        if not training or self.attn_drop == 0.0:
+            return alpha
+        import voltrix
+
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        mask = voltrix.dropout_mask(alpha.shape[0], 1 if alpha.dim() == 1 else alpha.shape[1], self.attn_drop, seed, device=alpha.device)
+        one, kept = torch.tensor(1.0), torch.tensor(1.0 - self.attn_drop)      # float32, the quotient AttnAggregate uses
+        return voltrix.apply_dropout_mask(alpha, mask, float(one / kept))
+
+    def attend(self, feat, s, training=False):
+        """``aggregate(feat, softmax(s))``: scores [nnz, H], out [n, H, out_feats]; one operator with ``fused``.  ``training``: with
+        attention dropout when the graph was built with ``attn_drop``."""
         if self.fused is not None:
+            if training and self.attn_drop > 0.0:
+                return self.fused(feat, s, dropout_p=self.attn_drop, training=True)
             return self.fused(feat, s)
-        return self.aggregate(feat, self.softmax(s))
+        return self.aggregate(feat, self.drop(self.softmax(s), training))
 
     @property
     def rows(self):
@@ -98,7 +117,7 @@ class GATLayer(torch.nn.Module):
         g = self.graph
         wh = self.w(x)
         s = g.score(wh @ self.a_l, wh @ self.a_r, self.slope)
-        alpha = g.softmax(s)
+        alpha = g.drop(g.softmax(s), self.training)
         return g.aggregate(wh.half(), values=alpha)
 
 
@@ -116,7 +135,7 @@ class GATHeadsLayer(torch.nn.Module):
         g = self.graph
         wh = self.w(x).view(g.n, g.heads, self.out_feats)
         s = g.score((wh * self.a_l).sum(-1), (wh * self.a_r).sum(-1), self.slope)
-        out = g.attend(wh.half(), s)                          # scores, weights [nnz, H]; out [n, H, out_feats]
+        out = g.attend(wh.half(), s, self.training)           # scores, weights [nnz, H]; out [n, H, out_feats]
         return out.flatten(1) if self.concat else out.mean(1)
 
 
@@ -135,7 +154,7 @@ class GATv2HeadsLayer(torch.nn.Module):
         xl = self.wl(x).view(g.n, g.heads, self.out_feats).half()
         xr = self.wr(x).view(g.n, g.heads, self.out_feats).half()
         s = g.score(xl, xr, self.a, self.slope)               # [nnz, H] from fp16 rows; the gradients come back in fp16
-        out = g.attend(xr, s)                                 # out [n, H, out_feats]
+        out = g.attend(xr, s, self.training)                  # out [n, H, out_feats]
         return out.flatten(1) if self.concat else out.mean(1)
 
 
@@ -167,13 +186,17 @@ def main():
     epochs = int(sys.argv[3]) if len(sys.argv) > 3 else 10
     heads = int(sys.argv[4]) if len(sys.argv) > 4 else 1
     flags = sys.argv[5:]
+    attn_drop = 0.0
+    if flags and flags[-1].startswith("attn_drop="):
+        attn_drop = float(flags.pop()[len("attn_drop="):])
+        assert 0.0 <= attn_drop < 1.0, attn_drop
     assert flags in ([], ["v2"], ["fused"], ["v2", "fused"]), flags
     v2, fused = "v2" in flags, "fused" in flags
     indptr, indices, _ = synth_graphs.generate(workload, device="cuda")
     n = indptr.numel() - 1
     indptr, indices = with_self_loops(indptr, indices, n)
     t0 = time.perf_counter()
-    graph = Graph(indptr, indices, n, hash_tag=f"example_gat/{workload}", heads=heads, v2=v2, fused=fused)
+    graph = Graph(indptr, indices, n, hash_tag=f"example_gat/{workload}", heads=heads, v2=v2, fused=fused, attn_drop=attn_drop)
     torch.cuda.synchronize()
     print(f"{workload}: N={n} nnz={indices.numel()} (self loops added); operators built in {time.perf_counter() - t0:.2f} s")
     torch.manual_seed(0)
@@ -183,6 +206,7 @@ def main():
     model = GAT(graph, in_feats, hidden, classes).cuda()
     opt = torch.optim.Adam(model.parameters(), lr=1e-2)
     times = []
+    model.train()
     for epoch in range(epochs):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -196,7 +220,11 @@ def main():
             print(f"epoch {epoch}: loss {float(loss):.4f}, {times[-1]:.2f} ms")
     steady = sorted(times[2:])[len(times[2:]) // 2] if len(times) > 2 else times[-1]
     print(f"steady epoch (forward + backward + Adam, full graph): {steady:.2f} ms -- two attention layers, hidden {hidden}"
-          + (f", {heads} heads" if heads > 1 else "") + (", GATv2" if v2 else "") + (", fused" if fused else "") + f"; peak memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+          + (f", {heads} heads" if heads > 1 else "") + (", GATv2" if v2 else "") + (", fused" if fused else "") + (f", attn_drop {attn_drop}" if attn_drop else "") + f"; peak memory {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB")
+    if attn_drop:
+        model.eval()                         # evaluation: no dropout, the same operators
+        with torch.no_grad():
+            print(f"evaluation loss (attention dropout off): {float(torch.nn.functional.cross_entropy(model(x), y)):.4f}")
 
 
 if __name__ == "__main__":

@@ -622,6 +622,44 @@ void voltrix_launch_attn_aggregate_grad_feat_csr(void* t_indptr, void* t_indices
                                                  int head_dim, void* grad_out, int dtype, void* scores, void* m, void* l, float scale,
                                                  void* grad_feat, void* stream, int* return_code);
 
+/* Attention dropout (dropout_mask_kernels.hpp; attn_aggregate_kernels.hpp with a mask).
+ * The keep mask is device int32[nnz, W], W = ceil(heads / 32), in CSR edge order: bit (h & 31) of word (h >> 5) of edge e set means
+ * (e, h) is kept; bits past heads are zero and never read.  voltrix_launch_dropout_mask writes every word: (e, h) is kept iff
+ * x >= threshold with x = word (h & 3) of Philox4x32-10(counter = (e, h >> 2, offset & 0xffffffff, offset >> 32), key = (seed &
+ * 0xffffffff, seed >> 32)), multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds.  threshold =
+ * min(2^32 - 1, floor(p * 2^32)) for a drop probability p: the kept probability is 1 - threshold / 2^32 and threshold 0 keeps all.  A
+ * bit depends on (seed, offset, e, h) only -- not on nnz, heads or the launch.  One thread per word, one 4-byte store each, no LDS, no
+ * workspace, no atomics, no host synchronisation.
+ * VOLTRIX_ERR_BAD_SHAPE on the host before any HIP call: heads < 1, nnz < 0, nnz > INT_MAX, mask null or not 4-byte aligned with
+ * nnz > 0; VOLTRIX_OK without a launch for nnz == 0. */
+void voltrix_launch_dropout_mask(int64_t nnz, int heads, uint32_t threshold, uint64_t seed, uint64_t offset, void* mask, void* stream,
+                                 int* return_code);
+
+/* voltrix_launch_attn_aggregate_csr and its two gradients with a keep mask: k[e, h] = keep_scale where the bit is set, 0 elsewhere.
+ *   out[r, h, :]        = sum_{e in row r} alpha[e, h] * k[e, h] * feat[indices[e], h, :]
+ *   grad_scores[e, h]   = scale * alpha[e, h] * (k[e, h] * <grad_out[row_e, h], feat[indices[e], h]> - delta[row_e, h])
+ *   grad_feat[c, h, :]  = sum_{e in row c of the transpose} alpha[order[e], h] * k[order[e], h] * grad_out[t_indices[e], h, :]
+ * alpha, m and l are those of the call without a mask (same bits): dropout acts after the normalisation, and delta is the dense product
+ * with the dropped out.  A dropped entry is a predicate, not a product with 0: its 16-byte pieces of feat (grad_out for grad_feat) are
+ * not loaded, so a NaN or inf there reaches nothing, and its dot in grad_scores is +0.  A row or head without a kept entry gives zeros.
+ * With every bit set and keep_scale = 1 all five results have the bits of the calls without a mask.  |out - ref| <= (2 (deg + 3) + 1)
+ * 2^-23 sum_e alpha_e k_e |feat_e| + 2^-23 sum_e k_e |feat_e| / l + 2^-126 with deg the row's full degree.  Lane maps, grids and the
+ * order of the sums are those of the calls without a mask; one more broadcast 4-byte load per entry; no LDS, no workspace, no atomics.
+ * The arguments, checks and alignments of the calls without a mask, and: keep_scale non-finite or negative is VOLTRIX_ERR_BAD_SHAPE
+ * (checked with scale, before "nothing to do"); mask null or not 4-byte aligned is VOLTRIX_ERR_BAD_SHAPE when nnz > 0 and the call has
+ * something to do.  mask = device int32[nnz, ceil(heads / 32)] in CSR order for all three (grad_feat reads it at order[e]). */
+void voltrix_launch_attn_aggregate_dropout_csr(void* indptr, void* indices, void* scores, int num_rows, int64_t nnz, int heads,
+                                               int head_dim, void* feat, int dtype, float scale, void* out, void* m, void* l, void* mask,
+                                               float keep_scale, void* stream, int* return_code);
+void voltrix_launch_attn_aggregate_dropout_grad_scores_csr(void* indptr, void* indices, int num_rows, int64_t nnz, int heads,
+                                                           int head_dim, void* grad_out, void* feat, int dtype, void* scores, void* m,
+                                                           void* l, void* delta, float scale, void* grad_scores, void* mask,
+                                                           float keep_scale, void* stream, int* return_code);
+void voltrix_launch_attn_aggregate_dropout_grad_feat_csr(void* t_indptr, void* t_indices, void* order, int num_cols, int64_t nnz,
+                                                         int heads, int head_dim, void* grad_out, int dtype, void* scores, void* m,
+                                                         void* l, float scale, void* grad_feat, void* mask, float keep_scale,
+                                                         void* stream, int* return_code);
+
 /* Rows of a dense row-major matrix times a per-row factor: dst[i, :] = T(float(src[i, :]) * scale[i]); dst may be src.
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,

@@ -22,6 +22,11 @@ and zero gradients; an empty row gives zeros; a NaN or ``+inf`` score stays in i
 entries that are not ``-inf``.  Numerics: DESIGN.md 3.17; ``out[:, h]``, ``d_s[:, h]``, ``d_feat[:, h]`` of an ``H``-head call have the
 bits of the 2-D call on the contiguous slices.  Known limit: the forward and ``d_feat`` walk a hub row with one wave, like
 ``voltrix.spmm_heads``.
+
+Attention dropout: ``mask=`` (int32 [nnz, ceil(H / 32)] keep bits, ``voltrix.dropout_mask``) and ``keep_scale=`` on all
+three functions.  ``out = sum_e alpha_e k_e feat_e`` with ``k = keep_scale`` where the bit is set and 0 elsewhere; ``m`` and ``l`` stay
+those of the undropped softmax, ``delta = (dC * out).sum(-1)`` holds with the dropped ``out``, ``d_s = scale * alpha * (k * dot - delta)``
+and ``d_feat`` weighs by ``alpha * k``.  A dropped entry's row is not read.  ``mask=None`` is the call without dropout, untouched.
 """
 from __future__ import annotations
 
@@ -44,8 +49,17 @@ def _finite(scale) -> float:
     return scale
 
 
+def _mask(mask, keep_scale, nnz: int, heads: int, device):
+    """``(mask, keep_scale)`` validated and layout-repaired; ``(None, 1.0)`` without a mask."""
+    if mask is None:
+        return None, 1.0
+    from .dropout import check_keep_scale, check_mask
+
+    return check_mask(mask, nnz, heads, device), check_keep_scale(keep_scale)
+
+
 def attn_aggregate(indptr: torch.Tensor, indices: torch.Tensor, scores: torch.Tensor, feat: torch.Tensor, num_rows: int,
-                   scale: float = 1.0, return_stats: bool = False):
+                   scale: float = 1.0, return_stats: bool = False, mask: torch.Tensor = None, keep_scale: float = 1.0):
     """``sum_{e in row r} softmax(scale * scores)[e, h] * feat[indices[e], h, :]`` -> float32 [num_rows, H, D], every element written, on
     the current stream; with ``return_stats`` also ``m`` and ``l``, float32 [num_rows, H]: the row maximum of ``sign(scale) * scores``
     (``-inf`` for an empty row) and the sum of ``exp(|scale| * (sign(scale) * scores - m))``.
@@ -54,7 +68,11 @@ def attn_aggregate(indptr: torch.Tensor, indices: torch.Tensor, scores: torch.Te
     in CSR order, head index fastest (cast to float32); ``feat`` [num_cols, H, D] fp32 / fp16 / bf16 as it is (other types as fp32);
     ``scale``: a finite float, negative allowed.  The 2-D form ``scores`` [nnz], ``feat`` [num_cols, D] -> [num_rows, D] (``m``, ``l``
     [num_rows]) is the ``H = 1`` layout through the same kernel.  A head width that is not a multiple of 16 bytes is padded with zeros
-    per head; an operand that is contiguous and 16-byte aligned is never copied."""
+    per head; an operand that is contiguous and 16-byte aligned is never copied.
+
+    ``mask`` (int32 [nnz, ceil(H / 32)] keep bits) and ``keep_scale`` (finite, >= 0): attention dropout -- a kept entry weighs
+    ``alpha * keep_scale``, a dropped one nothing and its row of ``feat`` is not read; ``m`` and ``l`` are those of the call without a
+    mask.  A wrong dtype, shape or device of the mask is a ``ValueError``."""
     from . import capi
     from .jit_kernels.spmm import _raw_stream
 
@@ -72,13 +90,18 @@ def attn_aggregate(indptr: torch.Tensor, indices: torch.Tensor, scores: torch.Te
     heads, head_dim = feat.shape[1], feat.shape[2]
     assert heads >= 1
     scores = _scores(scores, indices.numel(), heads)
+    mask, keep_scale = _mask(mask, keep_scale, indices.numel(), heads, feat.device)
     width = piece_width(max(head_dim, 1), feat.dtype)
     out = torch.empty((num_rows, heads, width), dtype=torch.float32, device=feat.device)
     m = torch.empty((num_rows, heads), dtype=torch.float32, device=feat.device)
     l = torch.empty((num_rows, heads), dtype=torch.float32, device=feat.device)
     if num_rows > 0:
-        capi.launch_attn_aggregate_csr(indptr.contiguous(), indices.contiguous(), scores, num_rows, padded_last_dim(feat, width), scale,
-                                       out, m, l, _raw_stream(feat.device))
+        if mask is None:
+            capi.launch_attn_aggregate_csr(indptr.contiguous(), indices.contiguous(), scores, num_rows, padded_last_dim(feat, width), scale,
+                                           out, m, l, _raw_stream(feat.device))
+        else:
+            capi.launch_attn_aggregate_csr(indptr.contiguous(), indices.contiguous(), scores, num_rows, padded_last_dim(feat, width), scale,
+                                           out, m, l, _raw_stream(feat.device), mask, keep_scale)
     if width != head_dim:
         out = out[:, :, :head_dim].contiguous()
     if one_d:
@@ -88,11 +111,12 @@ def attn_aggregate(indptr: torch.Tensor, indices: torch.Tensor, scores: torch.Te
 
 def attn_aggregate_grad_scores(indptr: torch.Tensor, indices: torch.Tensor, grad_out: torch.Tensor, feat: torch.Tensor,
                                scores: torch.Tensor, m: torch.Tensor, l: torch.Tensor, delta: torch.Tensor,
-                               scale: float = 1.0) -> torch.Tensor:
+                               scale: float = 1.0, mask: torch.Tensor = None, keep_scale: float = 1.0) -> torch.Tensor:
     """The gradient of ``attn_aggregate`` for its scores: ``scale * alpha[e, h] * (<grad_out[row_e, h], feat[indices[e], h]> -
     delta[row_e, h])`` -> float32 [nnz, H] (2-D form: [nnz]), with ``alpha`` recomputed from ``scores`` and the forward's ``m``, ``l``.
     ``delta`` [num_rows, H] is ``(grad_out * out).sum(-1)`` of the forward's ``out``.  ``grad_out`` [num_rows, H, D] (cast to float32),
-    ``feat`` as in the forward.  One launch split by edges; a row or head with ``l == 0`` gets zeros."""
+    ``feat`` as in the forward.  One launch split by edges; a row or head with ``l == 0`` gets zeros.  With ``mask`` / ``keep_scale`` of
+    the forward: ``scale * alpha * (k * dot - delta)``, a dropped entry's dot is +0 and its row of ``feat`` is not read."""
     from . import capi
     from .jit_kernels.spmm import _raw_stream
 
@@ -109,24 +133,29 @@ def attn_aggregate_grad_scores(indptr: torch.Tensor, indices: torch.Tensor, grad
     assert grad_out.shape == (num_rows, heads, head_dim), (tuple(grad_out.shape), num_rows, heads, head_dim)
     scores = _scores(scores, nnz, heads)
     m, l, delta = (t.float().contiguous().view(num_rows, heads) for t in (m, l, delta))
+    mask, keep_scale = _mask(mask, keep_scale, nnz, heads, feat.device)
     out = torch.empty((nnz, heads), dtype=torch.float32, device=feat.device)
     if nnz > 0 and head_dim == 0:
         out.zero_()
     elif nnz > 0:
         width = piece_width(max(head_dim, 1), feat.dtype)
+        extra = () if mask is None else (mask, keep_scale)
         capi.launch_attn_aggregate_grad_scores_csr(indptr.contiguous(), indices.contiguous(), num_rows,
                                                    padded_last_dim(grad_out.float(), width), padded_last_dim(feat, width), scores, m, l, delta,
-                                                   scale, out, _raw_stream(feat.device))
+                                                   scale, out, _raw_stream(feat.device), *extra)
     return out.view(-1) if one_d else out
 
 
 def attn_aggregate_grad_feat(t_indptr: torch.Tensor, t_indices: torch.Tensor, t_order: torch.Tensor, grad_out: torch.Tensor,
-                             scores: torch.Tensor, m: torch.Tensor, l: torch.Tensor, num_cols: int, scale: float = 1.0) -> torch.Tensor:
+                             scores: torch.Tensor, m: torch.Tensor, l: torch.Tensor, num_cols: int, scale: float = 1.0,
+                             mask: torch.Tensor = None, keep_scale: float = 1.0) -> torch.Tensor:
     """The gradient of ``attn_aggregate`` for ``feat``: ``sum_{e in column c} alpha[t_order[e], h] * grad_out[row_e, h, :]`` -> float32
     [num_cols, H, D] (2-D form: [num_cols, D]), every row written.  ``t_indptr`` / ``t_indices``: the transposed device CSR
     (``voltrix.autograd.csr_transpose_device``); ``t_order``: device [nnz], the entry of the CSR that entry ``e`` of the transpose is
     (``weighted.transpose_order``; kept as int32).  ``scores`` stays in CSR order and ``grad_out`` [num_rows, H, D] (fp32 / fp16 / bf16 as
-    it is) is never permuted; ``m``, ``l``: the forward's.  A row per lane group: a hub column serialises its wave."""
+    it is) is never permuted; ``m``, ``l``: the forward's.  A row per lane group: a hub column serialises its wave.  With ``mask`` /
+    ``keep_scale`` of the forward (the mask stays in CSR order and is read at ``t_order[e]``) the weight is ``alpha * k`` and a dropped
+    entry's row of ``grad_out`` is not read."""
     from . import capi
     from .jit_kernels.spmm import _raw_stream
 
@@ -144,11 +173,14 @@ def attn_aggregate_grad_feat(t_indptr: torch.Tensor, t_indices: torch.Tensor, t_
     t_order = t_order.to(torch.int32).contiguous()
     scores = _scores(scores, nnz, heads)
     m, l = (t.float().contiguous().view(num_rows, heads) for t in (m, l))
+    mask, keep_scale = _mask(mask, keep_scale, nnz, heads, grad_out.device)
     width = piece_width(max(head_dim, 1), grad_out.dtype)
     out = torch.empty((num_cols, heads, width), dtype=torch.float32, device=grad_out.device)
     if num_cols > 0:
+        extra = () if mask is None else (mask, keep_scale)
         capi.launch_attn_aggregate_grad_feat_csr(t_indptr.contiguous(), t_indices.contiguous(), t_order, num_cols,
-                                                 padded_last_dim(grad_out, width), scores, m, l, scale, out, _raw_stream(grad_out.device))
+                                                 padded_last_dim(grad_out, width), scores, m, l, scale, out, _raw_stream(grad_out.device),
+                                                 *extra)
     if width != head_dim:
         out = out[:, :, :head_dim].contiguous()
     return out.view(num_cols, head_dim) if one_d else out

@@ -366,12 +366,17 @@ class GATv2Score(_PatternOp):
 
 class _AttnAggregateFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feat, scores, op, scale):
+    def forward(ctx, feat, scores, op, scale, mask=None, keep_scale=1.0):
         from .attn_aggregate import attn_aggregate
 
-        out, m, l = attn_aggregate(op.indptr, op.indices, scores, feat, op.num_rows, scale, return_stats=True)
-        ctx.op, ctx.scale = op, scale
-        ctx.save_for_backward(feat, scores, out, m, l)      # never alpha
+        ctx.op, ctx.scale, ctx.keep_scale, ctx.dropout = op, scale, keep_scale, mask is not None
+        if mask is None:
+            out, m, l = attn_aggregate(op.indptr, op.indices, scores, feat, op.num_rows, scale, return_stats=True)
+            ctx.save_for_backward(feat, scores, out, m, l)      # never alpha
+            return out
+        out, m, l = attn_aggregate(op.indptr, op.indices, scores, feat, op.num_rows, scale, return_stats=True, mask=mask,
+                                   keep_scale=keep_scale)
+        ctx.save_for_backward(feat, scores, out, m, l, mask)    # one bit per edge and head: never alpha, never a float mask
         return out
 
     @staticmethod
@@ -379,17 +384,18 @@ class _AttnAggregateFunction(torch.autograd.Function):
         from .attn_aggregate import attn_aggregate_grad_feat, attn_aggregate_grad_scores
 
         op = ctx.op
-        feat, scores, out, m, l = (t.detach() for t in ctx.saved_tensors)
+        feat, scores, out, m, l = (t.detach() for t in ctx.saved_tensors[:5])
+        drop = {"mask": ctx.saved_tensors[5], "keep_scale": ctx.keep_scale} if ctx.dropout else {}
         grad_out = grad_out.float().contiguous()
         grad_feat = grad_scores = None
         if ctx.needs_input_grad[0]:           # the transposed CSR, alpha recomputed through its edge order; dC is not permuted
             grad_feat = attn_aggregate_grad_feat(op.t_indptr, op.t_indices, op.t_order, grad_out, scores, m, l, op.num_cols,
-                                                 ctx.scale).to(feat.dtype)
-        if ctx.needs_input_grad[1]:           # the softmax backward's row sum is the dense product <dC, out>
+                                                 ctx.scale, **drop).to(feat.dtype)
+        if ctx.needs_input_grad[1]:           # the softmax backward's row sum is the dense product <dC, out> (the dropped out)
             delta = (grad_out * out).sum(-1)
             grad_scores = attn_aggregate_grad_scores(op.indptr, op.indices, grad_out, feat, scores, m, l, delta,
-                                                     ctx.scale).to(scores.dtype)
-        return grad_feat, grad_scores, None, None
+                                                     ctx.scale, **drop).to(scores.dtype)
+        return (grad_feat, grad_scores, None, None, None, None) if ctx.dropout else (grad_feat, grad_scores, None, None)
 
 
 class AttnAggregate(_PatternOp):
@@ -401,12 +407,35 @@ class AttnAggregate(_PatternOp):
     ``transposed=(t_indptr, t_indices, t_order)``.  Saves ``feat``, ``scores``, ``out`` and the row statistics ``m``, ``l`` [num_rows, H].
     The backward is ``delta = (dC * out).sum(-1)`` (dense torch), one launch split by edges for ``scores.grad`` and one on the transposed
     CSR for ``feat.grad`` (``voltrix.attn_aggregate.attn_aggregate_grad_scores`` / ``attn_aggregate_grad_feat``): no index op, no float
-    atomics, no [nnz, H] tensor but ``scores.grad``; gradients come back in the inputs' dtypes, and a side nobody needs is skipped."""
+    atomics, no [nnz, H] tensor but ``scores.grad``; gradients come back in the inputs' dtypes, and a side nobody needs is skipped.
 
-    def __call__(self, feat: torch.Tensor, scores: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    Attention dropout: ``op(feat, scores, scale, dropout_p=p, training=True, seed=None, offset=0, mask=None)`` drops
+    attention weights after the normalisation, ``out = sum_e alpha_e k_e feat_e`` with ``k_e = float32(1) / float32(1 - p)`` for a kept
+    entry and 0 for a dropped one.  The keep mask is one bit per edge and head (``voltrix.dropout_mask(nnz, H, p, seed, offset)``, or the
+    caller's ``mask=`` int32 [nnz, ceil(H / 32)]); it is all the backward saves besides ``feat, scores, out, m, l``.  ``seed=None`` draws
+    a 63-bit seed from torch's default CPU generator on the host (no device synchronisation), so ``torch.manual_seed`` reproduces a run.
+    Under graph capture pass ``mask=``: a seed drawn during capture is a host value baked into the graph, and every replay would drop
+    the same entries -- generate the mask outside the graph (into the same buffer) and capture only its use.  With ``dropout_p == 0`` or
+    ``training=False`` and no ``mask`` the call is the one without dropout: nothing is allocated, the same bits."""
+
+    def __call__(self, feat: torch.Tensor, scores: torch.Tensor, scale: float = 1.0, dropout_p: float = 0.0, training: bool = True,
+                 seed: int = None, offset: int = 0, mask: torch.Tensor = None) -> torch.Tensor:
         assert feat.dim() in (2, 3) and scores.dim() == feat.dim() - 1 and feat.shape[0] == self.num_cols
         assert scores.shape[0] == self.num_edges and scores.shape[1:] == feat.shape[1:-1], (tuple(scores.shape), tuple(feat.shape))
-        return _AttnAggregateFunction.apply(feat, scores, self, float(scale))
+        dropout_p = float(dropout_p)
+        if not 0.0 <= dropout_p < 1.0:
+            raise ValueError(f"AttnAggregate: dropout_p must satisfy 0 <= p < 1, got {dropout_p}")
+        if mask is None and (dropout_p == 0.0 or not training):
+            return _AttnAggregateFunction.apply(feat, scores, self, float(scale))
+        heads = 1 if feat.dim() == 2 else feat.shape[1]
+        if mask is None:
+            from .dropout import dropout_mask
+
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())      # the default CPU generator: no sync
+            mask = dropout_mask(self.num_edges, heads, dropout_p, seed, offset, device=feat.device)
+        keep_scale = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(1.0 - dropout_p, dtype=torch.float32))
+        return _AttnAggregateFunction.apply(feat, scores, self, float(scale), mask, keep_scale)
 
 
 class SpMM:

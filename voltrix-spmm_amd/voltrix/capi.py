@@ -88,6 +88,10 @@ SYMBOLS = (
     "voltrix_launch_attn_aggregate_csr",
     "voltrix_launch_attn_aggregate_grad_scores_csr",
     "voltrix_launch_attn_aggregate_grad_feat_csr",
+    "voltrix_launch_dropout_mask",
+    "voltrix_launch_attn_aggregate_dropout_csr",
+    "voltrix_launch_attn_aggregate_dropout_grad_scores_csr",
+    "voltrix_launch_attn_aggregate_dropout_grad_feat_csr",
     "voltrix_csr_preprocess_workspace_bytes",
     "voltrix_launch_csr_window_count",
     "voltrix_launch_csr_fill",
@@ -580,6 +584,7 @@ def launch_cast_f32_f16_scaled(src, dst, scale, stream) -> None:
 # ---- the CSR / attention launchers: argument types per symbol (include/voltrix_capi.h), set on the first use of a symbol -- with them
 # ---- plain ints and data_ptr() values convert in C (12 -> 4 us per call on the host)
 _P, _I, _L, _F, _RC_P = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.POINTER(ctypes.c_int)
+_U32, _U64 = ctypes.c_uint32, ctypes.c_uint64
 _ARGTYPES = {
     "voltrix_launch_spmm_csr_rows": [_P, _P, _I, _I, _P, _I, _P, _I, _P, _RC_P],
     "voltrix_launch_spmm_csr_rows_weighted": [_P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _RC_P],
@@ -597,6 +602,11 @@ _ARGTYPES = {
     "voltrix_launch_attn_aggregate_csr": [_P, _P, _P, _I, _L, _I, _I, _P, _I, _F, _P, _P, _P, _P, _RC_P],
     "voltrix_launch_attn_aggregate_grad_scores_csr": [_P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _F, _P, _P, _RC_P],
     "voltrix_launch_attn_aggregate_grad_feat_csr": [_P, _P, _P, _I, _L, _I, _I, _P, _I, _P, _P, _P, _F, _P, _P, _RC_P],
+    "voltrix_launch_dropout_mask": [_L, _I, _U32, _U64, _U64, _P, _P, _RC_P],
+    "voltrix_launch_attn_aggregate_dropout_csr": [_P, _P, _P, _I, _L, _I, _I, _P, _I, _F, _P, _P, _P, _P, _F, _P, _RC_P],
+    "voltrix_launch_attn_aggregate_dropout_grad_scores_csr": [_P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _F, _P, _P, _F, _P,
+                                                              _RC_P],
+    "voltrix_launch_attn_aggregate_dropout_grad_feat_csr": [_P, _P, _P, _I, _L, _I, _I, _P, _I, _P, _P, _P, _F, _P, _P, _F, _P, _RC_P],
     "voltrix_launch_scatter_values": [_P, _P, _P, _L, _I, _P, _RC_P],
     "voltrix_launch_scale_rows": [_P, _P, _P, _L, _I, _I, _P, _RC_P],
 }
@@ -865,10 +875,31 @@ def launch_gatv2_rowsum_csr(indptr, indices, order, num_rows: int, p, q, grad, s
 # ---- edge softmax + aggregation in one launch (csrc/capi_attn_aggregate.hip): scores [nnz, H], feat [n, H, D], row statistics [n, H]
 
 
-def launch_attn_aggregate_csr(indptr, indices, scores, num_rows: int, feat, scale: float, out, m, l, stream) -> None:
+def _check_keep_mask(mask, nnz: int, heads: int) -> None:
+    import torch
+
+    assert mask.dtype == torch.int32 and mask.is_contiguous() and mask.is_cuda and mask.shape == (nnz, (heads + 31) // 32), \
+        (mask.dtype, tuple(mask.shape), nnz, heads)
+
+
+def launch_dropout_mask(nnz: int, heads: int, threshold: int, seed: int, offset: int, mask, stream) -> None:
+    """``mask`` int32 [nnz, ceil(heads / 32)]: bit ``h & 31`` of word ``h >> 5`` of edge ``e`` set iff word ``h & 3`` of
+    ``Philox4x32-10((e, h >> 2, offset lo, offset hi), (seed lo, seed hi))`` is ``>= threshold`` (voltrix/dropout_mask_kernels.hpp);
+    see include/voltrix_capi.h."""
+    _check_keep_mask(mask, nnz, heads)
+    assert 0 <= threshold < 2 ** 32 and 0 <= seed < 2 ** 64 and 0 <= offset < 2 ** 64
+    rc = ctypes.c_int(-1)
+    _bound("voltrix_launch_dropout_mask")(nnz, heads, threshold, seed, offset, mask.data_ptr(), stream, rc)
+    check(rc.value, "voltrix_launch_dropout_mask")
+
+
+def launch_attn_aggregate_csr(indptr, indices, scores, num_rows: int, feat, scale: float, out, m, l, stream, mask=None,
+                              keep_scale: float = 1.0) -> None:
     """``out[r, h] = sum_{e in row r} softmax(scale * scores)[e, h] * feat[indices[e], h]`` with the row statistics ``m``, ``l``
     (voltrix/attn_aggregate_kernels.hpp): device int32 CSR, ``scores`` float32 [nnz, H], fp32 / fp16 / bf16 ``feat`` [*, H, D] with D a
-    multiple of 16 bytes, fp32 ``out`` [num_rows, H, D], fp32 ``m`` and ``l`` [num_rows, H]; see include/voltrix_capi.h."""
+    multiple of 16 bytes, fp32 ``out`` [num_rows, H, D], fp32 ``m`` and ``l`` [num_rows, H]; with ``mask`` (int32 [nnz, ceil(H / 32)] keep
+    bits) the kept entries weigh ``alpha * keep_scale`` and the others nothing (``voltrix_launch_attn_aggregate_dropout_csr``); see
+    include/voltrix_capi.h."""
     import torch
 
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
@@ -880,6 +911,14 @@ def launch_attn_aggregate_csr(indptr, indices, scores, num_rows: int, feat, scal
     for t in (m, l):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (num_rows, heads)
     rc = ctypes.c_int(-1)
+    if mask is not None:
+        _check_keep_mask(mask, indices.numel(), heads)
+        _bound("voltrix_launch_attn_aggregate_dropout_csr")(indptr.data_ptr(), indices.data_ptr(), scores.data_ptr(), num_rows,
+                                                            indices.numel(), heads, feat.shape[2], feat.data_ptr(),
+                                                            _dtype_code(feat.dtype), float(scale), out.data_ptr(), m.data_ptr(),
+                                                            l.data_ptr(), mask.data_ptr(), float(keep_scale), stream, rc)
+        check(rc.value, "voltrix_launch_attn_aggregate_dropout_csr")
+        return
     _bound("voltrix_launch_attn_aggregate_csr")(indptr.data_ptr(), indices.data_ptr(), scores.data_ptr(), num_rows, indices.numel(), heads,
                                                 feat.shape[2], feat.data_ptr(), _dtype_code(feat.dtype), float(scale), out.data_ptr(),
                                                 m.data_ptr(), l.data_ptr(), stream, rc)
@@ -887,10 +926,11 @@ def launch_attn_aggregate_csr(indptr, indices, scores, num_rows: int, feat, scal
 
 
 def launch_attn_aggregate_grad_scores_csr(indptr, indices, num_rows: int, grad_out, feat, scores, m, l, delta, scale: float, out,
-                                          stream) -> None:
+                                          stream, mask=None, keep_scale: float = 1.0) -> None:
     """``out[e, h] = scale * alpha[e, h] * (<grad_out[row_e, h], feat[indices[e], h]> - delta[row_e, h])`` with ``alpha`` recomputed from
     ``scores``, ``m``, ``l``: fp32 ``grad_out`` [num_rows, H, D], ``feat`` [*, H, D], fp32 ``scores`` and ``out`` [nnz, H], fp32 ``m``,
-    ``l``, ``delta`` [num_rows, H]; see include/voltrix_capi.h."""
+    ``l``, ``delta`` [num_rows, H]; with ``mask`` the dot product is times ``keep_scale`` for a kept entry and +0 for a dropped one; see
+    include/voltrix_capi.h."""
     import torch
 
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
@@ -903,6 +943,15 @@ def launch_attn_aggregate_grad_scores_csr(indptr, indices, num_rows: int, grad_o
     for t in (m, l, delta):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (num_rows, heads)
     rc = ctypes.c_int(-1)
+    if mask is not None:
+        _check_keep_mask(mask, nnz, heads)
+        _bound("voltrix_launch_attn_aggregate_dropout_grad_scores_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, nnz, heads,
+                                                                        feat.shape[2], grad_out.data_ptr(), feat.data_ptr(),
+                                                                        _dtype_code(feat.dtype), scores.data_ptr(), m.data_ptr(),
+                                                                        l.data_ptr(), delta.data_ptr(), float(scale), out.data_ptr(),
+                                                                        mask.data_ptr(), float(keep_scale), stream, rc)
+        check(rc.value, "voltrix_launch_attn_aggregate_dropout_grad_scores_csr")
+        return
     _bound("voltrix_launch_attn_aggregate_grad_scores_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, nnz, heads, feat.shape[2],
                                                             grad_out.data_ptr(), feat.data_ptr(), _dtype_code(feat.dtype),
                                                             scores.data_ptr(), m.data_ptr(), l.data_ptr(), delta.data_ptr(), float(scale),
@@ -911,10 +960,11 @@ def launch_attn_aggregate_grad_scores_csr(indptr, indices, num_rows: int, grad_o
 
 
 def launch_attn_aggregate_grad_feat_csr(t_indptr, t_indices, order, num_cols: int, grad_out, scores, m, l, scale: float, out,
-                                        stream) -> None:
+                                        stream, mask=None, keep_scale: float = 1.0) -> None:
     """``out[c, h] = sum_{e in row c of the transposed CSR} alpha[order[e], h] * grad_out[t_indices[e], h]`` with ``alpha`` recomputed
     from ``scores`` (CSR order), ``m``, ``l``: int32 ``order`` [nnz], fp32 / fp16 / bf16 ``grad_out`` [num_rows, H, D], fp32 ``out``
-    [num_cols, H, D]; see include/voltrix_capi.h."""
+    [num_cols, H, D]; with ``mask`` (CSR order, read at ``order[e]``) the weight is ``alpha * keep_scale`` for a kept entry and a dropped
+    one adds nothing; see include/voltrix_capi.h."""
     import torch
 
     assert t_indptr.dtype == torch.int32 and t_indices.dtype == torch.int32 and t_indptr.numel() == num_cols + 1
@@ -928,6 +978,15 @@ def launch_attn_aggregate_grad_feat_csr(t_indptr, t_indices, order, num_cols: in
     for t in (m, l):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (grad_out.shape[0], heads)
     rc = ctypes.c_int(-1)
+    if mask is not None:
+        _check_keep_mask(mask, nnz, heads)
+        _bound("voltrix_launch_attn_aggregate_dropout_grad_feat_csr")(t_indptr.data_ptr(), t_indices.data_ptr(), order.data_ptr(),
+                                                                      num_cols, nnz, heads, grad_out.shape[2], grad_out.data_ptr(),
+                                                                      _dtype_code(grad_out.dtype), scores.data_ptr(), m.data_ptr(),
+                                                                      l.data_ptr(), float(scale), out.data_ptr(), mask.data_ptr(),
+                                                                      float(keep_scale), stream, rc)
+        check(rc.value, "voltrix_launch_attn_aggregate_dropout_grad_feat_csr")
+        return
     _bound("voltrix_launch_attn_aggregate_grad_feat_csr")(t_indptr.data_ptr(), t_indices.data_ptr(), order.data_ptr(), num_cols, nnz, heads,
                                                           grad_out.shape[2], grad_out.data_ptr(), _dtype_code(grad_out.dtype),
                                                           scores.data_ptr(), m.data_ptr(), l.data_ptr(), float(scale), out.data_ptr(),

@@ -45,6 +45,16 @@
 // contiguous slices, so out[:, h], m[:, h], l[:, h], d_s[:, h] and d_feat[:, h] have its bits.  No LDS, no scratch, no float atomics,
 // no workspace, no host synchronisation; offsets e H + h and row H D are 64-bit.
 //
+// Attention dropout (DROP = true, the trailing template argument of the three kernels).  k[e, h] = keep_scale where bit
+// h & 31 of word h >> 5 of mask[e] is set, 0 elsewhere (dropout_mask_kernels.hpp).  Dropout acts on alpha, after the normalisation: m and
+// l are computed over every entry exactly as without a mask; out = sum_e alpha_e k_e feat_e, so sum_e alpha_e k_e <dC_r, feat_e> =
+// <dC_r, out_r> = delta still; d_s = scale alpha (k dot - delta); d_feat weighs by alpha k with the mask read at order[e].  A dropped
+// entry is a predicate on the bit, not a product with 0: the lane's 16 bytes are not loaded and nothing is accumulated, so a NaN there
+// reaches nothing, and the bytes the gathers request fall with the kept fraction (what that does to time: DESIGN.md 3.19).  The
+// batch's ids, mask words and scores are loaded unconditionally and first; only the 16-byte gathers are predicated, issued back to back.
+// With every bit set and keep_scale = 1 the bits are those of DROP = false (w * 1.0f is exact).  The launchers that instantiate
+// DROP = true live in attn_aggregate_dropout.hpp, so a translation unit that includes this header alone emits the kernels it always did.
+//
 // Known limit.  The forward and d_feat keep the weakness of spmm_csr_heads_kernel: a wave walks a whole hub row (for d_feat, a hub
 // column), and the forward walks it twice.  The hub-row split is the follow-up for all row-per-group kernels together.
 #pragma once
@@ -92,9 +102,21 @@ struct AttnAggregateArgs {
   int max_lanes;        // lanes of a head that share pass 1: head_pieces when it is a power of two <= 64, else 1
   float sign;           // +1 / -1 = sign of scale
   float a;              // |scale|
+  const uint32_t* mask; // DROP: [nnz, mask_words] keep bits in CSR order (dropout_mask_kernels.hpp)
+  int mask_words;       // DROP: ceil(H / 32)
+  float keep_scale;     // DROP: the factor of a kept entry
 };
 
-template <typename T, int UNROLL>
+// Keeps the load of `id` where the source puts it: the compiler would otherwise sink an id that only a predicated gather uses into
+// the predicated block, and every gather would wait for its own id instead of the batch's ids being fetched together.  No instruction.
+__device__ __forceinline__ void aa_pin(int& id) { asm volatile("" : "+v"(id)); }
+
+// bit `bit` of a mask word
+__device__ __forceinline__ bool aa_kept(const uint32_t word, const int bit) { return ((word >> bit) & 1u) != 0u; }
+
+// DROP: attention dropout.  m and l are those of the undropped softmax; a kept entry accumulates with the weight
+// w keep_scale, a dropped entry's piece of feat is neither loaded nor accumulated.
+template <typename T, int UNROLL, bool DROP = false>
 static __global__ __launch_bounds__(256) void attn_aggregate_csr_kernel(const AttnAggregateArgs<T> a) {
 #pragma clang fp contract(off)
   constexpr int V = 16 / (int)sizeof(T);
@@ -127,37 +149,86 @@ static __global__ __launch_bounds__(256) void attn_aggregate_csr_kernel(const At
   int e = begin;
   const T* const base = a.input + col0;
   const long long F = a.F;
+  [[maybe_unused]] const uint32_t* mk = nullptr;                       // DROP: this lane's word of every edge and its bit in it
+  [[maybe_unused]] long long W = 0;
+  [[maybe_unused]] int bit = 0;
+  if constexpr (DROP) {
+    mk = a.mask + (head >> 5);
+    W = a.mask_words;
+    bit = head & 31;
+  }
   // full batches of UNROLL edges, then one more batch for the tail with clamped ids (spmm_csr_heads_kernel: every load issued before
   // the first is consumed)
   for (; e + UNROLL <= end; e += UNROLL) {
     uint4_t raw[UNROLL];
     float s[UNROLL];
+    [[maybe_unused]] bool keep[UNROLL];
+    if constexpr (DROP) {      // the batch's column ids, mask words and scores first, unconditionally; then the predicated gathers
+      int col[UNROLL];
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[e + u] * F);
-      s[u] = sc[(long long)(e + u) * H];
+      for (int u = 0; u < UNROLL; ++u) {
+        col[u] = a.indices[e + u];
+        keep[u] = aa_kept(mk[(long long)(e + u) * W], bit);
+        s[u] = sc[(long long)(e + u) * H];
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) aa_pin(col[u]);
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u)
+        if (keep[u]) raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)col[u] * F);   // a dropped entry's raw is never read
+    } else {
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[e + u] * F);
+        s[u] = sc[(long long)(e + u) * H];
+      }
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
       const float w = aa_weight(s[u], m, 1.0f, a.sign, a.a);
-      csr_accumulate_scaled<T>(acc, raw[u], w);
+      if constexpr (DROP) {
+        if (keep[u]) csr_accumulate_scaled<T>(acc, raw[u], w * a.keep_scale);
+      } else {
+        csr_accumulate_scaled<T>(acc, raw[u], w);
+      }
       l += w;
     }
   }
   if (e < end) {
     uint4_t raw[UNROLL];
     float s[UNROLL];
+    [[maybe_unused]] bool keep[UNROLL];
+    if constexpr (DROP) {
+      int col[UNROLL];
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int ee = e + u < end ? e + u : end - 1;
-      raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
-      s[u] = sc[(long long)ee * H];
+      for (int u = 0; u < UNROLL; ++u) {
+        const int ee = e + u < end ? e + u : end - 1;
+        col[u] = a.indices[ee];
+        keep[u] = aa_kept(mk[(long long)ee * W], bit) && e + u < end;
+        s[u] = sc[(long long)ee * H];
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) aa_pin(col[u]);
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u)
+        if (keep[u]) raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)col[u] * F);   // a dropped entry's raw is never read
+    } else {
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const int ee = e + u < end ? e + u : end - 1;
+        raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
+        s[u] = sc[(long long)ee * H];
+      }
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
       if (e + u < end) {
         const float w = aa_weight(s[u], m, 1.0f, a.sign, a.a);
-        csr_accumulate_scaled<T>(acc, raw[u], w);
+        if constexpr (DROP) {
+          if (keep[u]) csr_accumulate_scaled<T>(acc, raw[u], w * a.keep_scale);
+        } else {
+          csr_accumulate_scaled<T>(acc, raw[u], w);
+        }
         l += w;
       }
   }
@@ -182,20 +253,25 @@ inline int attn_aggregate_check_shape(int num_rows, long long nnz, int heads, in
   return kOk;
 }
 
+// the factor of a kept entry: finite and not negative (checked with the shape, before "nothing to do")
+inline bool attn_aggregate_bad_keep_scale(float keep_scale) { return !std::isfinite(keep_scale) || keep_scale < 0.0f; }
+
 // dtype: 0 fp32, 1 fp16, 2 bfloat16.  head_dim % (16 / sizeof(T)) == 0.  Every element of output, m and l is written (rows without
 // entries: zeros, m = -inf, l = 0); with nnz == 0 indices, scores and input are not read.  Nothing is checked on the device: indptr
 // must be a valid CSR of num_rows rows ending at nnz, and every index a row of `input`.
-inline int launch_attn_aggregate_csr(const int* indptr, const int* indices, const float* scores, int num_rows, long long nnz, int heads,
-                                     int head_dim, const void* input, int dtype, float scale, float* output, float* m, float* l,
-                                     hipStream_t stream) {
+template <bool DROP>
+inline int launch_attn_aggregate_csr_impl(const int* indptr, const int* indices, const float* scores, int num_rows, long long nnz,
+                                          int heads, int head_dim, const void* input, int dtype, float scale, float* output, float* m,
+                                          float* l, const void* mask, float keep_scale, hipStream_t stream) {
   int v = 0;
   const int rc = attn_aggregate_check_shape(num_rows, nnz, heads, head_dim, dtype, scale, &v);
   if (rc != kOk) return rc;
+  if (DROP && attn_aggregate_bad_keep_scale(keep_scale)) return kErrBadShape;
   if (num_rows == 0 || head_dim == 0) return kOk;
   if (bad_ptr(indptr, 3) || bad_ptr(output, 15) || bad_ptr(m, 3) ||
       bad_ptr(l, 3))
     return kErrBadShape;
-  if (nnz > 0 && (bad_ptr(indices, 3) || bad_ptr(scores, 3) || bad_ptr(input, 15)))
+  if (nnz > 0 && (bad_ptr(indices, 3) || bad_ptr(scores, 3) || bad_ptr(input, 15) || (DROP && bad_ptr(mask, 3))))
     return kErrBadShape;
   const int head_pieces = head_dim / v;
   const int pieces = heads * head_pieces;                // 16-byte pieces per row
@@ -206,11 +282,19 @@ inline int launch_attn_aggregate_csr(const int* indptr, const int* indices, cons
   auto go = [&](auto tag) {
     using T = decltype(tag);
     const AttnAggregateArgs<T> a{indptr, indices, static_cast<const T*>(input), output, scores, m, l, num_rows, heads, head_pieces,
-                                 heads * head_dim, g.lanes, (int)g.per_xcd, max_lanes, scale < 0.0f ? -1.0f : 1.0f, std::fabs(scale)};
-    hipLaunchKernelGGL((attn_aggregate_csr_kernel<T, 4>), grid, dim3(256), 0, stream, a);
+                                 heads * head_dim, g.lanes, (int)g.per_xcd, max_lanes, scale < 0.0f ? -1.0f : 1.0f, std::fabs(scale),
+                                 static_cast<const uint32_t*>(mask), (heads + 31) / 32, keep_scale};
+    hipLaunchKernelGGL((attn_aggregate_csr_kernel<T, 4, DROP>), grid, dim3(256), 0, stream, a);
   };
   dispatch_feature_type(dtype, go);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+inline int launch_attn_aggregate_csr(const int* indptr, const int* indices, const float* scores, int num_rows, long long nnz, int heads,
+                                     int head_dim, const void* input, int dtype, float scale, float* output, float* m, float* l,
+                                     hipStream_t stream) {
+  return launch_attn_aggregate_csr_impl<false>(indptr, indices, scores, num_rows, nnz, heads, head_dim, input, dtype, scale, output, m, l,
+                                               nullptr, 1.0f, stream);
 }
 
 struct AttnAggregateGradScoresArgs {
@@ -237,10 +321,14 @@ struct AttnAggregateGradScoresArgs {
   float scale;
   float sign;            // +1 / -1 = sign of scale
   float a;               // |scale|
+  const uint32_t* mask;  // DROP: [nnz, mask_words] keep bits
+  int mask_words;        // DROP: ceil(H / 32)
+  float keep_scale;      // DROP: the factor of a kept entry
 };
 
 // Y: float / _Float16 / bfloat16_bits.  R = 1: one piece per lane, dC held in registers; 0: any number, dC loaded per edge.
-template <typename Y, int R>
+// DROP: d_s = scale (alpha (k dot - delta)); a dropped entry's row of feat is not read and its dot is +0.
+template <typename Y, int R, bool DROP = false>
 static __global__ __launch_bounds__(256) void attn_aggregate_grad_scores_kernel(const AttnAggregateGradScoresArgs a) {
 #pragma clang fp contract(off)
   using X = float;
@@ -300,6 +388,14 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_scores_kernel(
     float acc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) acc[u] = 0.0f;
+    [[maybe_unused]] bool keep[U];                    // DROP: the bit of (edge, this lane's head); the lanes of a head agree
+    if constexpr (DROP) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int ee = e + u < e_end ? e + u : e_end - 1;
+        keep[u] = live && aa_kept(a.mask[(long long)ee * a.mask_words + (head >> 5)], head & 31);
+      }
+    }
     if constexpr (R == 1) {
       const bool mine = live && head_lane < a.head_pieces;
       const long long k0 = head0 + (long long)head_lane * V;
@@ -310,7 +406,11 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_scores_kernel(
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         yr[u] = uint4_t{0u, 0u, 0u, 0u};
-        if (mine) yr[u] = *reinterpret_cast<const uint4_t*>(y + (long long)cols[u] * F + k0);
+        if constexpr (DROP) {
+          if (mine && keep[u]) yr[u] = *reinterpret_cast<const uint4_t*>(y + (long long)cols[u] * F + k0);
+        } else {
+          if (mine) yr[u] = *reinterpret_cast<const uint4_t*>(y + (long long)cols[u] * F + k0);
+        }
       }
 #pragma unroll
       for (int u = 0; u < U; ++u)
@@ -335,6 +435,12 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_scores_kernel(
         uint4_t yr[U], xr[U][XW];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
+          if constexpr (DROP) {
+            yr[u] = uint4_t{0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int w = 0; w < XW; ++w) xr[u][w] = uint4_t{0u, 0u, 0u, 0u};
+            if (!keep[u]) continue;
+          }
           yr[u] = *reinterpret_cast<const uint4_t*>(y + (long long)cols[u] * F + k0);
 #pragma unroll
           for (int w = 0; w < XW; ++w) xr[u][w] = reinterpret_cast<const uint4_t*>(x + (long long)rows[u] * F + k0)[w];
@@ -362,7 +468,8 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_scores_kernel(
           const long long eh = (long long)(e + u) * a.heads + head;
           const long long rh = (long long)rows[u] * a.heads + head;
           const float alpha = aa_weight(a.scores[eh], a.m[rh], aa_inv(a.l[rh]), a.sign, a.a);
-          a.out[eh] = a.scale * (alpha * (acc[u] - a.delta[rh]));
+          if constexpr (DROP) a.out[eh] = a.scale * (alpha * ((keep[u] ? a.keep_scale * acc[u] : 0.0f) - a.delta[rh]));
+          else a.out[eh] = a.scale * (alpha * (acc[u] - a.delta[rh]));
         }
     }
   }
@@ -370,32 +477,43 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_scores_kernel(
 
 // d_s[e, h] = scale alpha[e, h] (<grad_out[row_e, h], feat[indices[e], h]> - delta[row_e, h]) with alpha recomputed from scores, m, l.
 // grad_out fp32 [num_rows, H, D]; feat dtype 0 fp32 / 1 fp16 / 2 bfloat16.  Every element of out[nnz, heads] is written.
-inline int launch_attn_aggregate_grad_scores_csr(const int* indptr, const int* indices, int num_rows, long long nnz, int heads,
-                                                 int head_dim, const float* grad_out, const void* feat, int dtype, const float* scores,
-                                                 const float* m, const float* l, const float* delta, float scale, float* out,
-                                                 hipStream_t stream) {
+template <bool DROP>
+inline int launch_attn_aggregate_grad_scores_csr_impl(const int* indptr, const int* indices, int num_rows, long long nnz, int heads,
+                                                      int head_dim, const float* grad_out, const void* feat, int dtype,
+                                                      const float* scores, const float* m, const float* l, const float* delta,
+                                                      float scale, float* out, const void* mask, float keep_scale, hipStream_t stream) {
   int v = 0;
   const int rc = attn_aggregate_check_shape(num_rows, nnz, heads, head_dim, dtype, scale, &v);
   if (rc != kOk) return rc;
+  if (DROP && attn_aggregate_bad_keep_scale(keep_scale)) return kErrBadShape;
   if (nnz == 0 || head_dim == 0) return kOk;
   if (bad_ptr(indptr, 3) || bad_ptr(indices, 3) || bad_ptr(grad_out, 15) ||
       bad_ptr(feat, 15) || bad_ptr(scores, 3) || bad_ptr(m, 3) ||
-      bad_ptr(l, 3) || bad_ptr(delta, 3) || bad_ptr(out, 3))
+      bad_ptr(l, 3) || bad_ptr(delta, 3) || bad_ptr(out, 3) || (DROP && bad_ptr(mask, 3)))
     return kErrBadShape;
   const int pieces = head_dim / v;
   const EdgeChunkGrid g = edge_chunk_grid(nnz, heads, pieces, kSddmmChunkEdges);
   if (!g.ok) return kErrBadShape;
   const AttnAggregateGradScoresArgs a{indptr, indices, grad_out, feat, scores, m, l, delta, out, num_rows, (int)nnz, heads, pieces,
                                       g.head_lanes, g.head_shift, g.rounds, g.slab_heads, g.lanes, g.wgs, g.per_xcd, scale,
-                                      scale < 0.0f ? -1.0f : 1.0f, std::fabs(scale)};
+                                      scale < 0.0f ? -1.0f : 1.0f, std::fabs(scale), static_cast<const uint32_t*>(mask),
+                                      (heads + 31) / 32, keep_scale};
   const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
   auto go = [&](auto ytag) {
     using Y = decltype(ytag);
-    if (g.rounds == 1) hipLaunchKernelGGL((attn_aggregate_grad_scores_kernel<Y, 1>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((attn_aggregate_grad_scores_kernel<Y, 0>), grid, dim3(256), 0, stream, a);
+    if (g.rounds == 1) hipLaunchKernelGGL((attn_aggregate_grad_scores_kernel<Y, 1, DROP>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((attn_aggregate_grad_scores_kernel<Y, 0, DROP>), grid, dim3(256), 0, stream, a);
   };
   dispatch_feature_type(dtype, go);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+inline int launch_attn_aggregate_grad_scores_csr(const int* indptr, const int* indices, int num_rows, long long nnz, int heads,
+                                                 int head_dim, const float* grad_out, const void* feat, int dtype, const float* scores,
+                                                 const float* m, const float* l, const float* delta, float scale, float* out,
+                                                 hipStream_t stream) {
+  return launch_attn_aggregate_grad_scores_csr_impl<false>(indptr, indices, num_rows, nnz, heads, head_dim, grad_out, feat, dtype, scores,
+                                                           m, l, delta, scale, out, nullptr, 1.0f, stream);
 }
 
 template <typename T>
@@ -416,9 +534,13 @@ struct AttnAggregateGradFeatArgs {
   int groups_per_xcd;   // ceil(row groups / 8)
   float sign;
   float a;
+  const uint32_t* mask; // DROP: [nnz, mask_words] keep bits in CSR order: read at order[e]
+  int mask_words;       // DROP: ceil(H / 32)
+  float keep_scale;     // DROP: the factor of a kept entry
 };
 
-template <typename T, int UNROLL>
+// DROP: the weight is alpha keep_scale for a kept entry; a dropped entry's piece of dC is neither loaded nor accumulated.
+template <typename T, int UNROLL, bool DROP = false>
 static __global__ __launch_bounds__(256) void attn_aggregate_grad_feat_kernel(const AttnAggregateGradFeatArgs<T> a) {
 #pragma clang fp contract(off)
   constexpr int V = 16 / (int)sizeof(T);
@@ -443,35 +565,108 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_feat_kernel(co
   const int end = a.indptr[row + 1];
   const T* const base = a.input + col0;
   const long long F = a.F;
+  [[maybe_unused]] const uint32_t* mk = nullptr;
+  [[maybe_unused]] long long W = 0;
+  [[maybe_unused]] int bit = 0;
+  if constexpr (DROP) {
+    mk = a.mask + (head >> 5);
+    W = a.mask_words;
+    bit = head & 31;
+  }
   for (; e + UNROLL <= end; e += UNROLL) {
     uint4_t raw[UNROLL];
     float s[UNROLL], m[UNROLL], l[UNROLL];
+    [[maybe_unused]] bool keep[UNROLL];
+    if constexpr (DROP) {      // every id, then every word that hangs on one, then the four predicated gathers back to back
+      int ri[UNROLL];
+      long long r[UNROLL], o[UNROLL];
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const long long r = a.indices[e + u];
-      raw[u] = *reinterpret_cast<const uint4_t*>(base + r * F);
-      s[u] = sc[(long long)a.order[e + u] * H];
-      m[u] = mh[r * H];
-      l[u] = lh[r * H];
+      for (int u = 0; u < UNROLL; ++u) {
+        ri[u] = a.indices[e + u];
+        o[u] = a.order[e + u];
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        aa_pin(ri[u]);
+        r[u] = ri[u];
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        keep[u] = aa_kept(mk[o[u] * W], bit);
+        s[u] = sc[o[u] * H];
+        m[u] = mh[r[u] * H];
+        l[u] = lh[r[u] * H];
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u)
+        if (keep[u]) raw[u] = *reinterpret_cast<const uint4_t*>(base + r[u] * F);   // a dropped entry's raw is never read
+    } else {
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const long long r = a.indices[e + u];
+        raw[u] = *reinterpret_cast<const uint4_t*>(base + r * F);
+        s[u] = sc[(long long)a.order[e + u] * H];
+        m[u] = mh[r * H];
+        l[u] = lh[r * H];
+      }
     }
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) csr_accumulate_scaled<T>(acc, raw[u], aa_weight(s[u], m[u], aa_inv(l[u]), a.sign, a.a));
+    for (int u = 0; u < UNROLL; ++u) {
+      if constexpr (DROP) {
+        if (keep[u]) csr_accumulate_scaled<T>(acc, raw[u], aa_weight(s[u], m[u], aa_inv(l[u]), a.sign, a.a) * a.keep_scale);
+      } else {
+        csr_accumulate_scaled<T>(acc, raw[u], aa_weight(s[u], m[u], aa_inv(l[u]), a.sign, a.a));
+      }
+    }
   }
   if (e < end) {
     uint4_t raw[UNROLL];
     float s[UNROLL], m[UNROLL], l[UNROLL];
+    [[maybe_unused]] bool keep[UNROLL];
+    if constexpr (DROP) {
+      int ri[UNROLL];
+      long long r[UNROLL], o[UNROLL];
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int ee = e + u < end ? e + u : end - 1;
-      const long long r = a.indices[ee];
-      raw[u] = *reinterpret_cast<const uint4_t*>(base + r * F);
-      s[u] = sc[(long long)a.order[ee] * H];
-      m[u] = mh[r * H];
-      l[u] = lh[r * H];
+      for (int u = 0; u < UNROLL; ++u) {
+        const int ee = e + u < end ? e + u : end - 1;
+        ri[u] = a.indices[ee];
+        o[u] = a.order[ee];
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        aa_pin(ri[u]);
+        r[u] = ri[u];
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        keep[u] = aa_kept(mk[o[u] * W], bit) && e + u < end;
+        s[u] = sc[o[u] * H];
+        m[u] = mh[r[u] * H];
+        l[u] = lh[r[u] * H];
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u)
+        if (keep[u]) raw[u] = *reinterpret_cast<const uint4_t*>(base + r[u] * F);   // a dropped entry's raw is never read
+    } else {
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const int ee = e + u < end ? e + u : end - 1;
+        const long long r = a.indices[ee];
+        raw[u] = *reinterpret_cast<const uint4_t*>(base + r * F);
+        s[u] = sc[(long long)a.order[ee] * H];
+        m[u] = mh[r * H];
+        l[u] = lh[r * H];
+      }
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
-      if (e + u < end) csr_accumulate_scaled<T>(acc, raw[u], aa_weight(s[u], m[u], aa_inv(l[u]), a.sign, a.a));
+      if (e + u < end) {
+        if constexpr (DROP) {
+          if (keep[u]) csr_accumulate_scaled<T>(acc, raw[u], aa_weight(s[u], m[u], aa_inv(l[u]), a.sign, a.a) * a.keep_scale);
+        } else {
+          csr_accumulate_scaled<T>(acc, raw[u], aa_weight(s[u], m[u], aa_inv(l[u]), a.sign, a.a));
+        }
+      }
   }
   float4_t* out = reinterpret_cast<float4_t*>(a.output + row * F + col0);
 #pragma unroll
@@ -481,16 +676,19 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_feat_kernel(co
 // d_feat[c, h, :] = sum_{e in row c of the transposed CSR} alpha[order[e], h] grad_out[t_indices[e], h, :], alpha recomputed from
 // scores (CSR order), m and l.  grad_out dtype 0 fp32 / 1 fp16 / 2 bfloat16.  Every row of out is written (rows without entries:
 // zeros); with nnz == 0 nothing but t_indptr is read.
-inline int launch_attn_aggregate_grad_feat_csr(const int* t_indptr, const int* t_indices, const int* order, int num_rows, long long nnz,
-                                               int heads, int head_dim, const void* grad_out, int dtype, const float* scores,
-                                               const float* m, const float* l, float scale, float* out, hipStream_t stream) {
+template <bool DROP>
+inline int launch_attn_aggregate_grad_feat_csr_impl(const int* t_indptr, const int* t_indices, const int* order, int num_rows,
+                                                    long long nnz, int heads, int head_dim, const void* grad_out, int dtype,
+                                                    const float* scores, const float* m, const float* l, float scale, float* out,
+                                                    const void* mask, float keep_scale, hipStream_t stream) {
   int v = 0;
   const int rc = attn_aggregate_check_shape(num_rows, nnz, heads, head_dim, dtype, scale, &v);
   if (rc != kOk) return rc;
+  if (DROP && attn_aggregate_bad_keep_scale(keep_scale)) return kErrBadShape;
   if (num_rows == 0 || head_dim == 0) return kOk;
   if (bad_ptr(t_indptr, 3) || bad_ptr(out, 15)) return kErrBadShape;
   if (nnz > 0 && (bad_ptr(t_indices, 3) || bad_ptr(order, 3) || bad_ptr(grad_out, 15) ||
-                  bad_ptr(scores, 3) || bad_ptr(m, 3) || bad_ptr(l, 3)))
+                  bad_ptr(scores, 3) || bad_ptr(m, 3) || bad_ptr(l, 3) || (DROP && bad_ptr(mask, 3))))
     return kErrBadShape;
   const int head_pieces = head_dim / v;
   const int pieces = heads * head_pieces;
@@ -501,11 +699,18 @@ inline int launch_attn_aggregate_grad_feat_csr(const int* t_indptr, const int* t
     using T = decltype(tag);
     const AttnAggregateGradFeatArgs<T> a{t_indptr, t_indices, order, static_cast<const T*>(grad_out), out, scores, m, l, num_rows,
                                          heads, head_pieces, heads * head_dim, g.lanes, (int)g.per_xcd, scale < 0.0f ? -1.0f : 1.0f,
-                                         std::fabs(scale)};
-    hipLaunchKernelGGL((attn_aggregate_grad_feat_kernel<T, 4>), grid, dim3(256), 0, stream, a);
+                                         std::fabs(scale), static_cast<const uint32_t*>(mask), (heads + 31) / 32, keep_scale};
+    hipLaunchKernelGGL((attn_aggregate_grad_feat_kernel<T, 4, DROP>), grid, dim3(256), 0, stream, a);
   };
   dispatch_feature_type(dtype, go);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
+}
+
+inline int launch_attn_aggregate_grad_feat_csr(const int* t_indptr, const int* t_indices, const int* order, int num_rows, long long nnz,
+                                               int heads, int head_dim, const void* grad_out, int dtype, const float* scores,
+                                               const float* m, const float* l, float scale, float* out, hipStream_t stream) {
+  return launch_attn_aggregate_grad_feat_csr_impl<false>(t_indptr, t_indices, order, num_rows, nnz, heads, head_dim, grad_out, dtype,
+                                                         scores, m, l, scale, out, nullptr, 1.0f, stream);
 }
 
 }  // namespace voltrix
