@@ -628,8 +628,9 @@ void voltrix_launch_attn_aggregate_grad_feat_csr(void* t_indptr, void* t_indices
  * x >= threshold with x = word (h & 3) of Philox4x32-10(counter = (e, h >> 2, offset & 0xffffffff, offset >> 32), key = (seed &
  * 0xffffffff, seed >> 32)), multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds.  threshold =
  * min(2^32 - 1, floor(p * 2^32)) for a drop probability p: the kept probability is 1 - threshold / 2^32 and threshold 0 keeps all.  A
- * bit depends on (seed, offset, e, h) only -- not on nnz, heads or the launch.  One thread per word, one 4-byte store each, no LDS, no
- * workspace, no atomics, no host synchronisation.
+ * bit depends on (seed, offset, e, h) only -- not on nnz, heads or the launch.  One thread per word (at most 2^24 - 1 workgroups: past
+ * 2^32 - 256 words a thread writes more than one), one 4-byte store each, no LDS, no workspace, no atomics, no host synchronisation.
+ * Every nnz <= INT_MAX works with every heads (nnz = 2^31 - 1 with 33 heads is tested on the device).
  * VOLTRIX_ERR_BAD_SHAPE on the host before any HIP call: heads < 1, nnz < 0, nnz > INT_MAX, mask null or not 4-byte aligned with
  * nnz > 0; VOLTRIX_OK without a launch for nnz == 0. */
 void voltrix_launch_dropout_mask(int64_t nnz, int heads, uint32_t threshold, uint64_t seed, uint64_t offset, void* mask, void* stream,

@@ -159,7 +159,7 @@ static __global__ __launch_bounds__(256) void attn_aggregate_csr_kernel(const At
   }
   // full batches of UNROLL edges, then one more batch for the tail with clamped ids (spmm_csr_heads_kernel: every load issued before
   // the first is consumed)
-  for (; e + UNROLL <= end; e += UNROLL) {
+  for (; end - e >= UNROLL; e += UNROLL) {
     uint4_t raw[UNROLL];
     float s[UNROLL];
     [[maybe_unused]] bool keep[UNROLL];
@@ -202,9 +202,9 @@ static __global__ __launch_bounds__(256) void attn_aggregate_csr_kernel(const At
       int col[UNROLL];
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
-        const int ee = e + u < end ? e + u : end - 1;
+        const int ee = u < end - e ? e + u : end - 1;
         col[u] = a.indices[ee];
-        keep[u] = aa_kept(mk[(long long)ee * W], bit) && e + u < end;
+        keep[u] = aa_kept(mk[(long long)ee * W], bit) && u < end - e;
         s[u] = sc[(long long)ee * H];
       }
 #pragma unroll
@@ -215,14 +215,14 @@ static __global__ __launch_bounds__(256) void attn_aggregate_csr_kernel(const At
     } else {
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
-        const int ee = e + u < end ? e + u : end - 1;
+        const int ee = u < end - e ? e + u : end - 1;
         raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
         s[u] = sc[(long long)ee * H];
       }
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
-      if (e + u < end) {
+      if (u < end - e) {
         const float w = aa_weight(s[u], m, 1.0f, a.sign, a.a);
         if constexpr (DROP) {
           if (keep[u]) csr_accumulate_scaled<T>(acc, raw[u], w * a.keep_scale);
@@ -377,7 +377,8 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_scores_kernel(
   for (int i = 0; i < V; ++i) xc[i] = 0.0f;
   int cur_row = -1;
 
-  for (int e = e_begin; e < e_end; e += U) {
+  for (int i = 0; i < e_end - e_begin; i += U) {     // counted: e + U may pass INT_MAX in the last chunk
+    const int e = e_begin + i;
     int rows[U], cols[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -573,7 +574,7 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_feat_kernel(co
     W = a.mask_words;
     bit = head & 31;
   }
-  for (; e + UNROLL <= end; e += UNROLL) {
+  for (; end - e >= UNROLL; e += UNROLL) {
     uint4_t raw[UNROLL];
     float s[UNROLL], m[UNROLL], l[UNROLL];
     [[maybe_unused]] bool keep[UNROLL];
@@ -628,7 +629,7 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_feat_kernel(co
       long long r[UNROLL], o[UNROLL];
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
-        const int ee = e + u < end ? e + u : end - 1;
+        const int ee = u < end - e ? e + u : end - 1;
         ri[u] = a.indices[ee];
         o[u] = a.order[ee];
       }
@@ -639,7 +640,7 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_feat_kernel(co
       }
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
-        keep[u] = aa_kept(mk[o[u] * W], bit) && e + u < end;
+        keep[u] = aa_kept(mk[o[u] * W], bit) && u < end - e;
         s[u] = sc[o[u] * H];
         m[u] = mh[r[u] * H];
         l[u] = lh[r[u] * H];
@@ -650,7 +651,7 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_feat_kernel(co
     } else {
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
-        const int ee = e + u < end ? e + u : end - 1;
+        const int ee = u < end - e ? e + u : end - 1;
         const long long r = a.indices[ee];
         raw[u] = *reinterpret_cast<const uint4_t*>(base + r * F);
         s[u] = sc[(long long)a.order[ee] * H];
@@ -660,7 +661,7 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_feat_kernel(co
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
-      if (e + u < end) {
+      if (u < end - e) {
         if constexpr (DROP) {
           if (keep[u]) csr_accumulate_scaled<T>(acc, raw[u], aa_weight(s[u], m[u], aa_inv(l[u]), a.sign, a.a) * a.keep_scale);
         } else {

@@ -72,12 +72,18 @@ struct DropoutMaskArgs {
   uint32_t off0, off1; // offset
 };
 
+// The runtime refuses a grid of 2^32 threads or more in one dimension (nnz = 2^31 - 1 with two words per edge is 2^24 blocks of 256: a
+// launch error, found by tests/test_gpu_large_offsets.py).  The grid is capped below that and a thread strides over the words: one word
+// per thread for every total below 2^32 - 256, as before.
+constexpr long long kDropoutMaskMaxBlocks = 0xffffff;
+
 static __global__ __launch_bounds__(256) void dropout_mask_kernel(const DropoutMaskArgs a) {
-  const long long i = (long long)blockIdx.x * 256 + (int)threadIdx.x;
-  if (i >= a.total) return;
-  const long long edge = a.words == 1 ? i : i / a.words;      // one word per edge for H <= 32: no 64-bit division on that path
-  const int word = (int)(i - edge * a.words);
-  a.mask[i] = dropout_mask_word((uint32_t)edge, word, a.heads, a.threshold, a.k0, a.k1, a.off0, a.off1);
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + (int)threadIdx.x; i < a.total; i += stride) {
+    const long long edge = a.words == 1 ? i : i / a.words;    // one word per edge for H <= 32: no 64-bit division on that path
+    const int word = (int)(i - edge * a.words);
+    a.mask[i] = dropout_mask_word((uint32_t)edge, word, a.heads, a.threshold, a.k0, a.k1, a.off0, a.off1);
+  }
 }
 
 // Every word of mask [nnz, ceil(heads / 32)] is written.  nnz == 0: kOk without a launch.
@@ -88,8 +94,8 @@ inline int launch_dropout_mask(long long nnz, int heads, uint32_t threshold, uin
   if (bad_ptr(mask, 3)) return kErrBadShape;
   const int words = (int)(((long long)heads + 31) / 32);
   const long long total = nnz * words;
-  const long long blocks = (total + 255) / 256;
-  if (blocks > 0x7fffffffLL) return kErrBadShape;
+  const long long all_blocks = (total + 255) / 256;
+  const long long blocks = all_blocks < kDropoutMaskMaxBlocks ? all_blocks : kDropoutMaskMaxBlocks;
   const DropoutMaskArgs a{static_cast<uint32_t*>(mask), total, heads, words, threshold, (uint32_t)seed, (uint32_t)(seed >> 32),
                           (uint32_t)offset, (uint32_t)(offset >> 32)};
   hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);

@@ -133,7 +133,8 @@ static __global__ __launch_bounds__(256) void gatv2_score_csr_kernel(const Gatv2
   }
   int cur_row = -1;
 
-  for (int e = e_begin; e < e_end; e += U) {
+  for (int i = 0; i < e_end - e_begin; i += U) {     // counted: e + U may pass INT_MAX in the last chunk
+    const int e = e_begin + i;
     int rows[U], cols[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -284,13 +285,13 @@ static __global__ __launch_bounds__(256) void gatv2_rowsum_csr_kernel(const Gatv
     float gv[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
-      const int ee = !decltype(tail)::value || e + u < end ? e + u : end - 1;
+      const int ee = !decltype(tail)::value || u < end - e ? e + u : end - 1;
       raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
       gv[u] = gh[(long long)(a.order != nullptr ? a.order[ee] : ee) * H];
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
-      if (!decltype(tail)::value || e + u < end) {
+      if (!decltype(tail)::value || u < end - e) {
         float qv[V];
         sddmm_to_float<T, 1>({raw[u]}, qv);
         const float gs = slope * gv[u];                                // one rounded product per edge
@@ -298,7 +299,7 @@ static __global__ __launch_bounds__(256) void gatv2_rowsum_csr_kernel(const Gatv
         for (int i = 0; i < V; ++i) acc[i] += (pv[i] + qv[i] > 0.0f) ? gv[u] : gs;
       }
   };
-  for (; e + UNROLL <= end; e += UNROLL) batch(std::false_type{});
+  for (; end - e >= UNROLL; e += UNROLL) batch(std::false_type{});
   if (e < end) batch(std::true_type{});
   float4_t* out = reinterpret_cast<float4_t*>(a.out + row * F + col0);
 #pragma unroll

@@ -95,7 +95,8 @@ static __global__ __launch_bounds__(256) void sddmm_heads_csr_kernel(const Sddmm
   for (int i = 0; i < V; ++i) xc[i] = 0.0f;
   int cur_row = -1;
 
-  for (int e = e_begin; e < e_end; e += U) {
+  for (int i = 0; i < e_end - e_begin; i += U) {     // counted: e + U may pass INT_MAX in the last chunk
+    const int e = e_begin + i;
     int rows[U], cols[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {

@@ -69,7 +69,7 @@ static __global__ __launch_bounds__(256) void spmm_csr_heads_kernel(const CsrHea
   const long long F = a.F;
   // full batches of UNROLL edges, then one more batch for the tail with clamped ids (spmm_csr_rows_kernel: every load issued before the
   // first is consumed)
-  for (; e + UNROLL <= end; e += UNROLL) {
+  for (; end - e >= UNROLL; e += UNROLL) {
     uint4_t raw[UNROLL];
     float v[UNROLL];
 #pragma unroll
@@ -85,13 +85,13 @@ static __global__ __launch_bounds__(256) void spmm_csr_heads_kernel(const CsrHea
     float v[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
-      const int ee = e + u < end ? e + u : end - 1;
+      const int ee = u < end - e ? e + u : end - 1;
       raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
       v[u] = vals[(long long)ee * H];
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
-      if (e + u < end) csr_accumulate_scaled<T>(acc, raw[u], v[u]);
+      if (u < end - e) csr_accumulate_scaled<T>(acc, raw[u], v[u]);
   }
   float4_t* out = reinterpret_cast<float4_t*>(a.output + row * F + col0);
 #pragma unroll

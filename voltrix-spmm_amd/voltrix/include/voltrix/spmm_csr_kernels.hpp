@@ -109,7 +109,7 @@ static __global__ __launch_bounds__(256) void spmm_csr_rows_kernel(const CsrArgs
   // the first is consumed; the slots past the row's end are skipped when adding): at mean degree 5 a row is one or two batches with all
   // their loads in flight -- a scalar tail loop ran most rows of these graphs one load at a time; a tail whose LOADS were predicated
   // serialised them (ppi-like x 128: 0.150 ms against 0.091; profiles/r06/experiment_csr_mapping.log)
-  for (; e + UNROLL <= end; e += UNROLL) {
+  for (; end - e >= UNROLL; e += UNROLL) {
     uint4_t raw[UNROLL];
     float v[UNROLL];
 #pragma unroll
@@ -128,13 +128,13 @@ static __global__ __launch_bounds__(256) void spmm_csr_rows_kernel(const CsrArgs
     float v[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
-      const int ee = e + u < end ? e + u : end - 1;
+      const int ee = u < end - e ? e + u : end - 1;
       raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
       if constexpr (WEIGHTED) v[u] = a.values[ee];
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
-      if (e + u < end) {
+      if (u < end - e) {
         if constexpr (WEIGHTED) csr_accumulate_scaled<T>(acc, raw[u], v[u]);
         else csr_accumulate<T>(acc, raw[u]);
       }
