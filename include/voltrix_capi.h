@@ -25,7 +25,15 @@
  *   - *return_code is ALWAYS written: 0 on success, a voltrix_rc value otherwise (the reference plumbs
  *     __return_code but never sets it; on errors it throws through ctypes or exit(1)s,
  *     spmm_kernels.cuh:28-45);
- *   - nothing is printed (the reference's preprocess printf's, bmat_kernels.cuh:309-310).
+ *   - nothing is printed (the reference's preprocess printf's, bmat_kernels.cuh:309-310);
+ *   - memory the caller did not define (DESIGN.md section 3.21 has a row per buffer): no `workspace`, `fill_workspace`, `partials`,
+ *     header, status, table or output argument NEED BE INITIALISED.  The library writes -- by a kernel or by a hipMemsetAsync on
+ *     `stream` -- every byte of a scratch buffer before it reads it and every element of every output it documents as written, and
+ *     nothing in a scratch buffer survives a call, except that a phase-2 call reads what its own phase 1 left in the SAME workspace,
+ *     untouched in between.  A buffer last used by another call, another graph or another operator serves as well as a fresh one.
+ *     The exceptions, each stated again where it applies, are inputs by nature: `output` of the atomic forms (atomic_out = 1,
+ *     accumulate = 2: the CALLER ZERO-FILLS it) and of accumulate = 1 / combine passes with accumulate != 0 (it holds the other
+ *     addend), and `level` / `rank` of the breadth-first search (the caller sets them to -1 before the first component).
  */
 #ifndef VOLTRIX_CAPI_H_
 #define VOLTRIX_CAPI_H_
@@ -108,7 +116,8 @@ void voltrix_launch_spmm_f16_tile(void* blk_offsets, void* hspa_packed, void* hi
  * keeps the same 10 mantissa bits; fp32's exponent range is preserved) into `workspace`, the product runs on
  * v_mfma_f32_16x16x32_f16 with the default tile and the epilogue undoes the scale (exact).  What voltrix.spmm does for a
  * float32 `feat`.  workspace: voltrix_spmm_f32_workspace_bytes(input_rows, embedding_dim) bytes, device, 16-byte aligned,
- * owned by the caller (input_rows = rows of `input`: num_nodes for a square adjacency).  embedding_dim % 8 == 0.
+ * owned by the caller (input_rows = rows of `input`: num_nodes for a square adjacency), need not be initialised and holds nothing
+ * a later call depends on.  embedding_dim % 8 == 0.
  * voltrix_launch_spmm itself keeps exact fp32 products (3.6x slower on the reddit-like headline graph). */
 int64_t voltrix_spmm_f32_workspace_bytes(int64_t input_rows, int embedding_dim);
 void voltrix_launch_spmm_f32_as_f16(void* blk_offsets, void* hspa_packed, void* hind, int num_nodes, int num_edges,
@@ -135,7 +144,8 @@ void voltrix_launch_spmm_bf16_tile(void* blk_offsets, void* hspa_packed, void* h
  *               units listed by length run in step and share gathered rows through L2.  slot < 0: the unit is the
  *               whole window (stride 1) and its result goes to output; slot >= 0: the unit's [16][embedding_dim] float32
  *               tile goes to partials + slot * 16 * embedding_dim, and voltrix_launch_combine_partials sums the tiles
- *               of each cut window in unit order (deterministic) into output.  unit_ptr int32[9]: XCD x owns units
+ *               of each cut window in unit order (deterministic) into output (partials need not be initialised: every unit with a
+ *               slot stores its whole tile, and only the slots of cut windows are read).  unit_ptr int32[9]: XCD x owns units
  *               [unit_ptr[x], unit_ptr[x+1]); max_units_per_xcd = the largest of those eight counts.  Every stage of
  *               every window must belong to exactly one unit.
  *   units_per_wave  1, or 2 with a unit table and fs <= 128 (several column slabs: fs = 128, slab-major order): every wave runs two consecutive units of the
@@ -171,11 +181,12 @@ void voltrix_launch_combine_partials(void* cuts, int num_cuts, void* partials, v
  *   phase 1  voltrix_launch_unit_table_count: header int32[8] (device) = {num_units U, num_cuts C, num_slots, max units per
  *            XCD, max_stages L, top (longest unit), 0, 0}.  max_stages <= 0: L = max(8, floor(1.5 x median stages per window)),
  *            on handles of fewer than 1024 windows at most max(8, ceil(all stages / 1024)) (unit_table.hpp).
- *            workspace: voltrix_unit_table_workspace_bytes(num_nodes) bytes, device, 16-byte aligned.
+ *            workspace: voltrix_unit_table_workspace_bytes(num_nodes) bytes, device, 16-byte aligned; it and the header need not be
+ *            initialised (the launch clears the histogram and the statistics itself and writes every other array before reading it).
  *   (caller reads the header; allocates units int32[U][4], unit_ptr int32[9], cuts int32[C][4], partials
  *    float[num_slots * 16 * embedding_dim] and voltrix_unit_table_fill_workspace_bytes(U) bytes of fill workspace)
  *   phase 2  voltrix_launch_unit_table_fill: writes units, unit_ptr, cuts (every element); same workspace, untouched since
- *            phase 1; num_units / num_cuts / top as read from the header.
+ *            phase 1; num_units / num_cuts / top as read from the header.  The fill workspace need not be initialised.
  * xcd_ptr: NULL, or device int32[9] = first window of every XCD's range (xcd_ptr[0] = 0, xcd_ptr[8] = ceil(num_nodes / 16),
  * non-decreasing; the same array in both phases): ranges of equal WORK instead of equal window counts, for graphs whose
  * stages per row vary along the rows (communities); a two-level host passes 32 x the panel kernel's xcd_ptr so that both
@@ -200,10 +211,12 @@ void voltrix_launch_unit_table_fill(void* blk_offsets, int num_nodes, void* xcd_
  *     voltrix_launch_stream_table_count: header int32[8] (device) = {num_units U, cut windows C, partial-tile slots, bound on
  *       the number of runs, run_cost, cut_stages, 0, 0}.  run_cost <= 0: clamp((stages + windows) / 9216, 6, 48) (six runs per
  *       wave slot of the chip); cut_stages <= 0: max(run_cost, the unit table's default L).  run_cost <= 128.
- *       workspace: voltrix_stream_table_workspace_bytes(num_nodes) bytes, device, 16-byte aligned.
+ *       workspace: voltrix_stream_table_workspace_bytes(num_nodes) bytes, device, 16-byte aligned; it, the header and the fill
+ *       workspace of phase 2 need not be initialised.
  *     (caller reads the header; allocates units int32[U][8], cuts int32[C][4], runs int32[bound][4], run_ptr int32[9],
  *      header2 int32[4], partials float[slots * 16 * embedding_dim], voltrix_stream_table_fill_workspace_bytes(U) bytes)
- *     voltrix_launch_stream_table_fill: writes them all; header2 = {runs R, max runs per XCD, oversized, 0} (the launch's
+ *     voltrix_launch_stream_table_fill: writes them all (every record of runs up to `bound`: the ones past R are zero);
+ *       header2 = {runs R, max runs per XCD, oversized, 0} (the launch's
  *       max_runs_per_xcd); same workspace, untouched since phase 1; run_cost as read from the header: 2 .. 128, anything else is
  *       refused (kErrBadShape) -- a larger value would make runs of more than 64 units, which the kernel (one lane per unit of a
  *       run) cannot walk; `oversized` != 0 reports such a run should one ever be built: do not launch with that table.
@@ -233,7 +246,7 @@ void voltrix_launch_spmm_stream_bf16(void* hspa_packed, void* hind, int num_node
 /* "Balance" schedule for a handle: order_out int32[W] (device) lists the windows of every XCD range, inside chunks of
  * `chunk` (1..4096) consecutive windows, by descending TC-block count, so that co-resident waves sweep their sorted
  * columns at a similar pace and share gathered rows through L2.  Depends on blk_offsets only; results of the SpMM are
- * bit-identical with or without it. */
+ * bit-identical with or without it.  Every element of order_out is written. */
 void voltrix_launch_window_order(void* blk_offsets, int num_nodes, int chunk, void* order_out, void* stream,
                                  int* return_code);
 
@@ -283,7 +296,8 @@ void voltrix_launch_spmm_panel_bf16(void* panel_ptr, void* panel_cols, void* pan
  * community carries 5-20 x the k-steps of the median panel).  parts int32 [num_parts][4] = {panel, first k-step inside the
  * panel, k-steps, slot} replaces panel_order: launch position -> a piece of at most a bounded number of k-steps.  slot < 0:
  * the panel is whole and its tile goes to `output` per `accumulate`, exactly as above.  slot >= 0: the panel is cut; every
- * piece STORES its tile to partials[slot] (float32 [slots][16 waves row_blocks][embedding_dim], per-call scratch) and
+ * piece STORES its tile to partials[slot] (float32 [slots][16 waves row_blocks][embedding_dim], per-call scratch that need not be
+ * initialised) and
  * voltrix_launch_combine_panel_partials -- on the same stream, after this launch (and, for accumulate == 2, after the window
  * kernel has been joined) -- adds the pieces to `output` in slot order: a fixed order, whatever the pieces' timing.
  * xcd_ptr / max_parts_per_xcd as above, over part positions (NULL / 0: ranges of ceil(num_parts / 8)).
@@ -310,7 +324,8 @@ void voltrix_launch_combine_panel_partials(void* cuts, int num_cuts, void* parti
  * ceil(TC blocks / 4)), n = ceil(num_nodes / 16); _of_panels: work of panel p = round(kstep_cost_x10 / 10 x its k-steps) +
  * the stages of its panel_rows / 16 windows in resid_blk_offsets (the Python host passes 66: a k-step costs a CU about 6.6
  * residual stages), and window_xcd_ptr int32[9] (or NULL) <- the same ranges in windows, for the residual's unit table.
- * One workgroup each; stream-ordered, no host read. */
+ * One workgroup each; stream-ordered, no host read.  All nine elements of xcd_ptr (and of window_xcd_ptr) are written, nothing of
+ * them is read. */
 void voltrix_launch_xcd_ranges_of_work(void* work, int num_items, int align, void* xcd_ptr, void* stream, int* return_code);
 void voltrix_launch_xcd_ranges_of_windows(void* blk_offsets, int num_nodes, int align, void* xcd_ptr, void* stream,
                                           int* return_code);
@@ -322,7 +337,9 @@ void voltrix_launch_xcd_ranges_of_panels(void* panel_ptr, void* resid_blk_offset
  * between): parts int32[pieces][4], part_xcd_ptr int32[9], cuts int32[max(1, cut panels)][4] as described above -- panels
  * of more than `cap` k-steps in ceil(k-steps / cap) contiguous pieces of nearly equal length; per XCD range (panel_xcd_ptr in
  * panel units, or NULL = ceil(num_panels / 8) panels each) longest first, ties by (panel, piece).  workspace: 16-byte aligned,
- * voltrix_panel_parts_workspace_bytes(num_panels) bytes. */
+ * voltrix_panel_parts_workspace_bytes(num_panels) bytes; it and the header need not be initialised (the count call writes all of both).
+ * Every element of parts and part_xcd_ptr and one row of cuts per cut panel are written; without a cut panel the one row of cuts is
+ * neither written nor read. */
 int64_t voltrix_panel_parts_workspace_bytes(int num_panels);
 void voltrix_launch_panel_parts_count(void* panel_ptr, int num_panels, int cap, void* panel_xcd_ptr, void* workspace,
                                       void* header, void* stream, int* return_code);
@@ -358,8 +375,8 @@ void voltrix_launch_spmm_fused_bf16(void* panel_ptr, void* panel_cols, void* pan
 /* Builder of the stage records above (fused_plan.hpp): block-format handle of the RESIDUAL matrix (the handle of
  * resid_node_pointer / resid_edge_list from the plan builder below, through voltrix_launch_csr_window_count / _fill) ->
  * (wave_ptr, records), in two phases because the caller owns every buffer:
- *   phase 1  voltrix_launch_fused_records_count: wave_ptr int32 [4 NP + 1] (NP = ceil(num_nodes / 512)); workspace:
- *            voltrix_fused_records_workspace_bytes(num_nodes) bytes, device, 16-byte aligned
+ *   phase 1  voltrix_launch_fused_records_count: wave_ptr int32 [4 NP + 1] (NP = ceil(num_nodes / 512)), every element written;
+ *            workspace: voltrix_fused_records_workspace_bytes(num_nodes) bytes, device, 16-byte aligned, need not be initialised
  *   (caller reads R = wave_ptr[4 NP] and allocates records uint32 [(R + 1) * 64], 16-byte aligned)
  *   phase 2  voltrix_launch_fused_records_fill: every word of records is written (the padding record is zero).
  * Once the records exist the residual handle is no longer needed by voltrix_launch_spmm_fused_*. */
@@ -375,7 +392,8 @@ void voltrix_launch_fused_records_fill(void* blk_offsets, void* hspa_packed, voi
 /* Builder of the panel plan (panel_plan.hpp): CSR on the DEVICE (rows sorted, duplicate-free, ids in [0, num_cols),
  * num_cols <= 2^22) -> residual CSR + plan, in two phases because the caller owns every buffer:
  *   phase 1  voltrix_launch_panel_plan_count: panel_ptr int32[NP+1], resid_node_pointer int32[num_nodes+1], status[1];
- *            workspace: voltrix_panel_plan_workspace_bytes(...) bytes, device, 16-byte aligned
+ *            workspace: voltrix_panel_plan_workspace_bytes(...) bytes, device, 16-byte aligned, need not be initialised (the launch
+ *            clears all of it); every element of the three outputs is written
  *   (caller reads S = panel_ptr[NP], E_r = resid_node_pointer[num_nodes] and status[0] -- the number of input
  *    violations, must be 0 -- and allocates resid_edge_list int32[E_r], panel_cols int32[32 (S + 2)],
  *    panel_bits uint32[(S + 1) * waves * 64])
@@ -395,7 +413,7 @@ void voltrix_launch_panel_plan_fill(void* node_pointer, void* edge_list, int num
  * positions (xcd_ptr int32[9] on the device, or NULL: ceil(num_panels / 8) each), groups of `group` consecutive panels (neighbours share their band columns: side by side
  * they share gathered rows through L2), the groups with the most k-steps first (ties by index), natural order inside a
  * group; group = 1: plain longest-first (what the Python host uses: groups of 4 gained 3 % on the bare kernel pair, nothing
- * through the operator).  Speed only. */
+ * through the operator).  Speed only.  Every element of order_out is written (a permutation inside every range). */
 void voltrix_launch_panel_order(void* panel_ptr, int num_panels, int group, void* xcd_ptr, void* order_out, void* stream,
                                 int* return_code);
 
@@ -413,7 +431,9 @@ void voltrix_launch_cast_f32_f16(void* src, void* dst, int64_t count, void* stre
  * per call, e = exponent(max |src|) - 14, so fp32 magnitudes beyond fp16's range neither overflow nor flush while the
  * 10-bit mantissa (= the reference's TF32 rounding, spmm_kernels.cuh:1671) is kept.  scale: device float[2], 8-byte
  * aligned; scale[0] <- 2^e, to be passed as `out_scale` of voltrix_launch_spmm_f16_tile (multiplied into every output
- * element in the epilogue; exact).  No host sync.  Inf / NaN in src: scale 1, they propagate as in fp32. */
+ * element in the epilogue; exact).  No host sync.  Inf / NaN in src: scale 1, they propagate as in fp32.  Neither dst nor scale
+ * need be initialised: scale[1] is scratch (the bits of max |src|), the head of dst briefly holds one word per workgroup of the
+ * reduction -- both are written before they are read -- and the conversion then writes every element of dst. */
 void voltrix_launch_cast_f32_f16_scaled(void* src, void* dst, int64_t count, void* scale, void* stream,
                                         int* return_code);
 
@@ -466,7 +486,8 @@ void voltrix_launch_sddmm_csr(void* indptr, void* indices, int num_rows, int64_t
  * 1 / (the row's entries that are not -inf) to each of them.  Accuracy, with deg_r the row's entries and ref the exact softmax:
  * |alpha - ref| <= ref * 2 (deg_r + |z_e - m_r| + 2) 2^-23 + 2^-126.  Deterministic: no float atomics, sums in an order fixed by
  * the pattern, the same bits on every launch.  Three kernel launches on `stream`, no host synchronisation; workspace: device, 16-byte
- * aligned, voltrix_edge_softmax_workspace_bytes(num_rows, nnz) bytes (a function of nnz alone), reused by the backward.
+ * aligned, voltrix_edge_softmax_workspace_bytes(num_rows, nnz) bytes (a function of nnz alone), reused by the backward; it need not
+ * be initialised and carries nothing from one call to the next (every call writes the chunk rows and partials it reads).
  * VOLTRIX_ERR_BAD_SHAPE: negative sizes, nnz > INT_MAX, a non-finite scale, a null or misaligned pointer; VOLTRIX_OK without a launch
  * for nnz == 0.  No reference counterpart (the reference is forward-only and has no edge values).
  * Alignment: indptr, scores and out 4 bytes suffice (the backward's alpha, grad_alpha and grad_scores likewise): a thread moves its 8
@@ -543,7 +564,8 @@ void voltrix_launch_gat_score_csr(void* indptr, void* indices, int num_rows, int
  * out[:, h] of a call with `heads` heads has the bits of the single-head call on the contiguous slices a[:, h], b[:, h], grad[:, h].  A
  * NaN in grad[e, h] reaches only the one sum that holds it.  Three launches (zero fill, chunk sums, merge of the rows that cross a chunk
  * of 2048 edges), split by edges so a hub row costs what its edges cost; no host synchronisation.  workspace: device, 16-byte aligned,
- * voltrix_gat_score_workspace_bytes(num_rows, nnz, heads) bytes -- a function of (nnz, heads) alone, a multiple of 16, 0 for nnz == 0.
+ * voltrix_gat_score_workspace_bytes(num_rows, nnz, heads) bytes -- a function of (nnz, heads) alone, a multiple of 16, 0 for nnz == 0;
+ * it need not be initialised (partials are read only for rows that cross a chunk boundary, and those are written by the same call).
  * The checks of voltrix_launch_gat_score_csr -- 4 bytes suffice for indptr, indices, order, a, b, grad and out (one float at a time);
  * workspace 16 bytes, required --; nnz == 0 zero-fills out (num_rows > 0 then needs a valid out) and is VOLTRIX_OK. */
 int64_t voltrix_gat_score_workspace_bytes(int num_rows, int64_t nnz, int heads);
@@ -665,7 +687,8 @@ void voltrix_launch_attn_aggregate_dropout_grad_feat_csr(void* t_indptr, void* t
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,
  * C's rows times r after -- the normalised adjacencies of GCN / mean aggregation); the reference has no edge values at all
- * (spmm_kernels.cuh:1632-1644: bits -> 1.0).  Alignment: src and dst 16 bytes (16 bytes per lane; anything else is
+ * (spmm_kernels.cuh:1632-1644: bits -> 1.0).  Every element of dst is written.
+ * Alignment: src and dst 16 bytes (16 bytes per lane; anything else is
  * VOLTRIX_ERR_BAD_SHAPE on the host, before any launch), scale 4 bytes. */
 void voltrix_launch_scale_rows(void* src, void* scale, void* dst, int64_t rows, int num_feats, int dtype, void* stream,
                                int* return_code);
@@ -674,7 +697,9 @@ void voltrix_launch_scale_rows(void* src, void* scale, void* dst, int64_t rows, 
  * preprocess, the O(TCb*E) rescan or the 512-byte/TC-block fp32 `hspa` intermediate.  Two phases because the
  * caller owns every buffer and T is data dependent:
  *   phase 1  voltrix_launch_csr_window_count: block_partition[W], pointer1[W+1], status[1] (device int32)
- *            workspace: voltrix_csr_preprocess_workspace_bytes(num_nodes, num_cols, num_edges, path) bytes, device, 16-B aligned
+ *            workspace: voltrix_csr_preprocess_workspace_bytes(num_nodes, num_cols, num_edges, path) bytes, device, 16-B aligned,
+ *            need not be initialised (the launch clears the four queue counters on the paths that queue windows; keys, queues and
+ *            range groups are written for exactly the windows they are later read for); every element of all three outputs is written
  *   (caller reads T = pointer1[W] and status[0], allocates hspa_packed uint32[4T] and hind int32[8T])
  *   phase 2  voltrix_launch_csr_fill: writes hspa_packed and hind (every word), same workspace, same num_cols.
  * num_cols = the column universe: every id in edge_list lies in [0, num_cols) (square adjacency: num_nodes; a row shard
@@ -705,9 +730,12 @@ void voltrix_launch_csr_fill(void* node_pointer, void* edge_list, int num_nodes,
  *       duplicates kept; entries with a column id outside [0, num_cols) left out) -- the search walks row u of A and row u of
  *       A^T, and the backward pass of the SpMM multiplies with it (voltrix/autograd.py).  Row ids expanded per entry, one
  *       stable radix sort by column, row pointers by binary search: no atomics.  workspace:
- *       voltrix_csr_transpose_workspace_bytes(num_edges) bytes, device, 16-byte aligned.
- *   voltrix_launch_bfs_seed: level[start] = 0 (level int32[num_nodes], -1 = unvisited, kept by the caller across
- *       components), queue[0] = start (queue int32[num_nodes]), ctrl int32[8] = {head, tail, appended, depth, done, ...},
+ *       voltrix_csr_transpose_workspace_bytes(num_edges) bytes, device, 16-byte aligned, need not be initialised; every element of
+ *       t_indptr and t_indices is written.
+ *   voltrix_launch_bfs_seed: level[start] = 0 (level int32[num_nodes], -1 = unvisited: THE CALLER SETS IT, and rank, to -1 before
+ *       the first component and keeps them across components; queue, ctrl and level_off need not be initialised: the seed
+ *       writes what the level launches read), queue[0] = start (queue int32[num_nodes]),
+ *       ctrl int32[8] = {head, tail, appended, depth, done, ...},
  *       level_off int32[num_nodes + 2] (level_off[d] = queue position of level d's first node).
  *   voltrix_launch_bfs_levels: one single-workgroup launch that walks every level while the frontier stays <= 2048 nodes,
  *       then `wide_levels` whole-chip levels.  The caller reads ctrl (its sync) and calls again until ctrl[4] != 0; then
@@ -733,7 +761,7 @@ void voltrix_launch_cm_rank(void* indptr, void* indices, void* t_indptr, void* t
 /* out = inv(chol(gram + eps trace(gram) I))^T for a k x k symmetric positive semi-definite gram (float32, row-major,
  * k <= 64), float32 [k][k]: the small factor of a Cholesky QR (X <- X out has orthonormal columns), on the device so that
  * the spectral row order's subspace iteration (voltrix/reorder.py) has no host sync per step.  One workgroup, double
- * arithmetic.  VOLTRIX_ERR_BAD_SHAPE for k outside 1..64. */
+ * arithmetic.  VOLTRIX_ERR_BAD_SHAPE for k outside 1..64.  Every element of out is written. */
 void voltrix_launch_chol_inv_transposed(void* gram, int k, double eps, void* out, void* stream, int* return_code);
 
 #ifdef __cplusplus

@@ -33,6 +33,19 @@ def test_library_exports_every_declared_symbol():
     assert capi.fused_panel_geometry() == (hybrid.FUSED_WAVES, hybrid.FUSED_ROW_BLOCKS) == (4, 8)
 
 
+def test_every_size_function_returns_64_bits():
+    """The ``*_workspace_bytes`` functions return ``int64_t``; a binding left at ctypes' default ``int`` cuts the size of a large graph's
+    workspace short, and the launch then writes past the buffer allocated from it.  Three were (stream table, its fill phase, panel parts)."""
+    lib = capi.lib()
+    sizes = [name for name in _declared_functions() if name.endswith("_workspace_bytes")]
+    assert len(sizes) >= 12
+    for name in sizes:
+        assert getattr(lib, name).restype is ctypes.c_int64, name
+    units = 1 << 30
+    assert lib.voltrix_stream_table_fill_workspace_bytes(ctypes.c_int64(units)) >= 4 * 4 * units
+    assert lib.voltrix_unit_table_fill_workspace_bytes(ctypes.c_int64(units)) >= 5 * 4 * units
+
+
 def test_tile_space_enumeration_and_defaults():
     f16 = capi.tiles(True)
     f32 = capi.tiles(False)

@@ -126,17 +126,9 @@ def lib() -> ctypes.CDLL:
         _lib = ctypes.CDLL(LIB_PATH)
         _lib.voltrix_abi_version.restype = ctypes.c_int
         _lib.voltrix_spmm_num_tiles.restype = ctypes.c_int
-        _lib.voltrix_csr_preprocess_workspace_bytes.restype = ctypes.c_int64
-        _lib.voltrix_panel_plan_workspace_bytes.restype = ctypes.c_int64
-        _lib.voltrix_spmm_f32_workspace_bytes.restype = ctypes.c_int64
-        _lib.voltrix_fused_records_workspace_bytes.restype = ctypes.c_int64
-        _lib.voltrix_unit_table_workspace_bytes.restype = ctypes.c_int64
-        _lib.voltrix_unit_table_fill_workspace_bytes.restype = ctypes.c_int64
-        _lib.voltrix_cm_rank_workspace_bytes.restype = ctypes.c_int64
-        _lib.voltrix_csr_transpose_workspace_bytes.restype = ctypes.c_int64
-        _lib.voltrix_edge_softmax_workspace_bytes.restype = ctypes.c_int64
-        _lib.voltrix_edge_softmax_heads_workspace_bytes.restype = ctypes.c_int64
-        _lib.voltrix_gat_score_workspace_bytes.restype = ctypes.c_int64
+        for name in SYMBOLS:      # every size function returns int64_t: the default restype (int) would cut a size above 2^31 - 1 short,
+            if name.endswith("_workspace_bytes"):      # and the workspace allocated from it would be too small for the launch
+                getattr(_lib, name).restype = ctypes.c_int64
         for name in SYMBOLS:
             if name.startswith("voltrix_launch_") or name in ("voltrix_spmm_default_tile", "voltrix_spmm_tile_at"):
                 getattr(_lib, name).restype = None
