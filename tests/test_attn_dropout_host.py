@@ -101,7 +101,7 @@ def test_header_declares_and_binding_lists_the_entry_points():
         assert name in capi.SYMBOLS, name
         assert re.search(rf"\b{name}\s*\(", text), name
         assert hasattr(capi.lib(), name)
-        assert name in capi._ARGTYPES, name
+        assert name in capi.SIGNATURES, name
     assert capi.lib().voltrix_abi_version() == 2
     assert callable(voltrix.dropout_mask) and callable(voltrix.apply_dropout_mask)
 

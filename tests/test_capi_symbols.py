@@ -1,27 +1,32 @@
 """CPU: the C-ABI library loads and exports every symbol include/voltrix_capi.h declares; host-only entry points
 (tile enumeration, the host `preprocess` launch, argument validation) behave.  No GPU compute is called here."""
 import ctypes
-import os
-import re
+import inspect
 
 import numpy as np
 import pytest
 
-from conftest import REPO, load_csr_fixture
+from capi_header import prototypes
+from conftest import load_csr_fixture
 
 from voltrix import capi
 
-HEADER = os.path.join(REPO, "include", "voltrix_capi.h")
-
 
 def _declared_functions():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(voltrix_[a-z0-9_]+)\s*\(", text)))
+    return sorted(prototypes())
 
 
-def test_header_and_binding_list_agree():
-    assert _declared_functions() == sorted(capi.SYMBOLS)
+def test_header_and_binding_agree_in_every_type():
+    """Every prototype of the header -- its name, its return type and each parameter's type -- is the binding's entry, and is what the
+    loaded library's functions are set to: a wrong width or a missing argument is refused by ctypes, not passed on."""
+    declared = prototypes()
+    assert set(declared) == set(capi.SYMBOLS) == set(capi.SIGNATURES) and len(capi.SYMBOLS) == len(declared)
+    lib = capi.lib()
+    for name, (restype, params) in declared.items():
+        argtypes = [ctype for ctype, _ in params]
+        assert capi.SIGNATURES[name] == (restype, argtypes), name
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
 
 
 def test_library_exports_every_declared_symbol():
@@ -44,6 +49,89 @@ def test_every_size_function_returns_64_bits():
     units = 1 << 30
     assert lib.voltrix_stream_table_fill_workspace_bytes(ctypes.c_int64(units)) >= 4 * 4 * units
     assert lib.voltrix_unit_table_fill_workspace_bytes(ctypes.c_int64(units)) >= 5 * 4 * units
+    assert lib.voltrix_stream_table_fill_workspace_bytes(units) >= 4 * 4 * units      # a plain int goes through argtypes whole
+    assert lib.voltrix_unit_table_fill_workspace_bytes(units) >= 5 * 4 * units
+    assert lib.voltrix_unit_table_fill_workspace_bytes(1 << 32) > 1 << 32
+
+
+def test_a_wrong_width_or_a_missing_argument_is_refused():
+    """Host code only: ctypes refuses the call before the library is entered."""
+    lib = capi.lib()
+    assert lib.voltrix_edge_softmax_workspace_bytes(ctypes.c_int(4), ctypes.c_int64(5)) >= 0
+    with pytest.raises((ctypes.ArgumentError, TypeError)):
+        lib.voltrix_edge_softmax_workspace_bytes(ctypes.c_int(4), ctypes.c_int(5))      # nnz is int64_t
+    with pytest.raises((ctypes.ArgumentError, TypeError)):
+        lib.voltrix_edge_softmax_workspace_bytes(4)
+    rc = ctypes.c_int(-1)
+    with pytest.raises((ctypes.ArgumentError, TypeError)):
+        lib.voltrix_launch_cast_f32_f16(None, None, 16, rc)                             # no stream
+    with pytest.raises((ctypes.ArgumentError, TypeError)):
+        lib.voltrix_launch_cast_f32_f16(None, None, 16.0, None, rc)                     # a float where count is int64_t
+    assert rc.value == -1
+
+
+# the wrappers KernelTimer brackets and the label each is counted under (KernelTimer.summary() keys; bench.py reads them)
+TIMED = {
+    "launch_spmm": "spmm",
+    "launch_spmm_sched": "spmm",
+    "launch_spmm_panel": "spmm_panel",
+    "launch_spmm_fused": "spmm_fused",
+    "launch_combine_partials": "combine_partials",
+    "launch_cast_f32_f16_scaled": "cast_f32_f16_scaled",
+    "launch_cast_f32_f16": "cast_f32_f16",
+    "launch_scale_rows": "scale_rows",
+    "launch_spmm_csr_rows": "spmm_csr_rows",
+    "launch_sddmm_csr": "sddmm_csr",
+    "launch_edge_softmax_csr": "edge_softmax_csr",
+    "launch_edge_softmax_backward_csr": "edge_softmax_backward_csr",
+    "launch_sddmm_heads_csr": "sddmm_heads_csr",
+    "launch_edge_softmax_heads_csr": "edge_softmax_heads_csr",
+    "launch_edge_softmax_heads_backward_csr": "edge_softmax_heads_backward_csr",
+    "launch_spmm_csr_heads": "spmm_csr_heads",
+    "launch_gat_score_csr": "gat_score_csr",
+    "launch_gat_score_rowsum_csr": "gat_score_rowsum_csr",
+    "launch_gatv2_score_csr": "gatv2_score_csr",
+    "launch_gatv2_rowsum_csr": "gatv2_rowsum_csr",
+    "launch_attn_aggregate_csr": "attn_aggregate_csr",
+    "launch_attn_aggregate_grad_scores_csr": "attn_aggregate_grad_scores_csr",
+    "launch_attn_aggregate_grad_feat_csr": "attn_aggregate_grad_feat_csr",
+    "launch_spmm_f32_as_f16": "spmm_f32_as_f16",
+    "launch_window_order": "window_order",
+    "launch_csr_window_count": "csr_window_count",
+    "launch_csr_fill": "csr_fill",
+}
+
+
+def test_the_timed_wrappers_their_labels_and_their_stream_positions():
+    timed = {name: fn for name, fn in vars(capi).items() if hasattr(fn, "timer_label")}
+    assert {name: fn.timer_label for name, fn in timed.items()} == TIMED and len(TIMED) == 27
+    for name, fn in timed.items():
+        assert fn.__name__ == name
+        for signature in (inspect.signature(fn), inspect.signature(fn.__wrapped__)):   # the public signature is the wrapped function's
+            assert list(signature.parameters).index("stream") == fn.stream_index, name
+    # the position counted by hand before the table existed, for three shapes of signature
+    assert capi.launch_spmm.stream_index == 10 and capi.launch_cast_f32_f16.stream_index == 2
+    assert capi.launch_attn_aggregate_grad_scores_csr.stream_index == 11
+
+
+def test_a_timed_wrapper_brackets_its_own_stream_under_its_label(monkeypatch):
+    from contextlib import contextmanager
+
+    from voltrix.utils import KernelTimer
+
+    seen = []
+
+    class Recorder:
+        @contextmanager
+        def bracket(self, label, stream):
+            seen.append((label, stream))
+            yield
+
+    monkeypatch.setattr(KernelTimer, "active", Recorder())
+    z = np.zeros(64, np.uint8).ctypes.data
+    assert capi.launch_spmm(z, z, z, 16, 0, 12, z, z, True, (128, 4, 1), 1234) == 1          # refused on the host: no HIP call
+    assert capi.launch_spmm(z, z, z, 16, 0, 12, z, z, True, (128, 4, 1), stream=5678) == 1
+    assert seen == [("spmm", 1234), ("spmm", 5678)]
 
 
 def test_tile_space_enumeration_and_defaults():

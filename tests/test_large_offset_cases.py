@@ -264,21 +264,22 @@ def _launch_on_the_host(name, nnz):
 
     buf = np.zeros(4096 + 16, np.uint8)
     aligned = buf.ctypes.data + (-buf.ctypes.data) % 16
-    types = capi._ARGTYPES[name]
+    types = capi.SIGNATURES[name][1]
     args = [aligned if v == P else nnz if v == NNZ else v for v in LAUNCHERS_WITH_NNZ[name]]
     assert len(args) + 2 == len(types), name
     for value, ctype in zip(LAUNCHERS_WITH_NNZ[name], types):      # the table follows the binding: pointers, the 64-bit nnz, floats
         assert (value == P) == (ctype is ctypes.c_void_p) and (value == NNZ) == (ctype is ctypes.c_int64), (name, value, ctype)
         assert isinstance(value, float) == (ctype is ctypes.c_float), (name, value, ctype)
     rc = ctypes.c_int(-1)
-    capi._bound(name)(*args, None, rc)
+    getattr(capi.lib(), name)(*args, None, rc)
     return rc.value
 
 
 def test_every_launcher_with_nnz_refuses_two_to_the_31_on_the_host():
-    from voltrix import capi
+    from capi_header import prototypes
 
-    with_nnz = {name for name, types in capi._ARGTYPES.items() if ctypes.c_int64 in types and "scatter" not in name and "scale_rows" not in name}
+    with_nnz = {name for name, (_, params) in prototypes().items()       # every launcher the header declares with an `int64_t nnz`
+                if name.startswith("voltrix_launch_") and (ctypes.c_int64, "nnz") in params}
     assert with_nnz == set(LAUNCHERS_WITH_NNZ)               # a new launcher that takes nnz belongs in the table
     for name in LAUNCHERS_WITH_NNZ:
         assert _launch_on_the_host(name, 2 ** 31) == 1, name     # VOLTRIX_ERR_BAD_SHAPE, before any HIP call

@@ -17,96 +17,103 @@ CSRC_DIR = os.path.join(_ROOT, "csrc")
 
 _lib = None
 
-# every symbol include/voltrix_capi.h declares (tests/test_capi_symbols.py cross-checks this list with the header)
-SYMBOLS = (
-    "voltrix_abi_version",
-    "voltrix_launch_preprocess",
-    "voltrix_launch_hmat_gen",
-    "voltrix_launch_hmat_packed_swizzle",
-    "voltrix_launch_spmm",
-    "voltrix_launch_spmm_f32_tile",
-    "voltrix_launch_spmm_f16",
-    "voltrix_launch_spmm_f16_tile",
-    "voltrix_spmm_f32_workspace_bytes",
-    "voltrix_launch_spmm_f32_as_f16",
-    "voltrix_launch_spmm_f16_sched",
-    "voltrix_launch_spmm_bf16_sched",
-    "voltrix_launch_combine_partials",
-    "voltrix_stream_table_workspace_bytes",
-    "voltrix_stream_table_fill_workspace_bytes",
-    "voltrix_launch_stream_table_count",
-    "voltrix_launch_stream_table_fill",
-    "voltrix_launch_spmm_stream_f16",
-    "voltrix_launch_spmm_stream_bf16",
-    "voltrix_launch_spmm_panel_f16",
-    "voltrix_launch_spmm_panel_bf16",
-    "voltrix_launch_spmm_panel_parts_f16",
-    "voltrix_launch_spmm_panel_parts_bf16",
-    "voltrix_launch_combine_panel_partials",
-    "voltrix_launch_xcd_ranges_of_work",
-    "voltrix_launch_xcd_ranges_of_windows",
-    "voltrix_launch_xcd_ranges_of_panels",
-    "voltrix_panel_parts_workspace_bytes",
-    "voltrix_launch_panel_parts_count",
-    "voltrix_launch_panel_parts_fill",
-    "voltrix_launch_spmm_fused_f16",
-    "voltrix_launch_spmm_fused_bf16",
-    "voltrix_fused_panel_geometry",
-    "voltrix_fused_records_workspace_bytes",
-    "voltrix_launch_fused_records_count",
-    "voltrix_launch_fused_records_fill",
-    "voltrix_panel_plan_workspace_bytes",
-    "voltrix_launch_panel_plan_count",
-    "voltrix_launch_panel_plan_fill",
-    "voltrix_launch_panel_order",
-    "voltrix_spmm_default_tile",
-    "voltrix_spmm_num_tiles",
-    "voltrix_spmm_tile_at",
-    "voltrix_launch_window_order",
-    "voltrix_launch_spmm_bf16",
-    "voltrix_launch_spmm_bf16_tile",
-    "voltrix_launch_cast_f32_f16",
-    "voltrix_launch_cast_f32_f16_scaled",
-    "voltrix_launch_scale_rows",
-    "voltrix_launch_spmm_csr_rows",
-    "voltrix_launch_spmm_csr_rows_weighted",
-    "voltrix_launch_scatter_values",
-    "voltrix_launch_sddmm_csr",
-    "voltrix_edge_softmax_workspace_bytes",
-    "voltrix_launch_edge_softmax_csr",
-    "voltrix_launch_edge_softmax_backward_csr",
-    "voltrix_launch_sddmm_heads_csr",
-    "voltrix_edge_softmax_heads_workspace_bytes",
-    "voltrix_launch_edge_softmax_heads_csr",
-    "voltrix_launch_edge_softmax_heads_backward_csr",
-    "voltrix_launch_spmm_csr_heads",
-    "voltrix_launch_gat_score_csr",
-    "voltrix_gat_score_workspace_bytes",
-    "voltrix_launch_gat_score_rowsum_csr",
-    "voltrix_launch_gatv2_score_csr",
-    "voltrix_launch_gatv2_rowsum_csr",
-    "voltrix_launch_attn_aggregate_csr",
-    "voltrix_launch_attn_aggregate_grad_scores_csr",
-    "voltrix_launch_attn_aggregate_grad_feat_csr",
-    "voltrix_launch_dropout_mask",
-    "voltrix_launch_attn_aggregate_dropout_csr",
-    "voltrix_launch_attn_aggregate_dropout_grad_scores_csr",
-    "voltrix_launch_attn_aggregate_dropout_grad_feat_csr",
-    "voltrix_csr_preprocess_workspace_bytes",
-    "voltrix_launch_csr_window_count",
-    "voltrix_launch_csr_fill",
-    "voltrix_unit_table_workspace_bytes",
-    "voltrix_unit_table_fill_workspace_bytes",
-    "voltrix_launch_unit_table_count",
-    "voltrix_launch_unit_table_fill",
-    "voltrix_csr_transpose_workspace_bytes",
-    "voltrix_launch_csr_transpose",
-    "voltrix_launch_bfs_seed",
-    "voltrix_launch_bfs_levels",
-    "voltrix_cm_rank_workspace_bytes",
-    "voltrix_launch_cm_rank",
-    "voltrix_launch_chol_inv_transposed",
-)
+# ---- the binding: one entry per symbol include/voltrix_capi.h declares, ``name: (return type, [parameter types])``.  lib() sets
+# ---- restype and argtypes of every symbol from it, so plain ints, floats, data_ptr() values and None convert in C (12 -> 4 us per
+# ---- call on the host) and a wrong width or a missing argument is a ctypes.ArgumentError / TypeError before the library is entered.
+# ---- tests/test_capi_symbols.py compares every entry with the header's prototype: a new entry point is one line here.  The order is
+# ---- the one SYMBOLS has always had (the header's, but for a few entry points it declares further down).
+_P, _I, _L, _F, _D, _RC_P = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.POINTER(ctypes.c_int)
+_U32, _U64 = ctypes.c_uint32, ctypes.c_uint64
+SIGNATURES = {
+    "voltrix_abi_version": (_I, []),
+    "voltrix_launch_preprocess": (None, [_P, _P, _I, _P, _P, _P, _P, _RC_P]),
+    "voltrix_launch_hmat_gen": (None, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_hmat_packed_swizzle": (None, [_I, _P, _P, _P, _RC_P]),
+    "voltrix_launch_spmm": (None, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_f32_tile": (None, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_f16": (None, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_f16_tile": (None, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _RC_P]),
+    "voltrix_spmm_f32_workspace_bytes": (_L, [_L, _I]),
+    "voltrix_launch_spmm_f32_as_f16": (None, [_P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_f16_sched": (None, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _RC_P]),
+    "voltrix_launch_spmm_bf16_sched": (None, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _RC_P]),
+    "voltrix_launch_combine_partials": (None, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _RC_P]),
+    "voltrix_stream_table_workspace_bytes": (_L, [_I]),
+    "voltrix_stream_table_fill_workspace_bytes": (_L, [_L]),
+    "voltrix_launch_stream_table_count": (None, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _RC_P]),
+    "voltrix_launch_stream_table_fill": (None, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_stream_f16": (None, [_P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _RC_P]),
+    "voltrix_launch_spmm_stream_bf16": (None, [_P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _RC_P]),
+    "voltrix_launch_spmm_panel_f16": (None, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_panel_bf16": (None, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_panel_parts_f16": (None, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_panel_parts_bf16": (None, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_combine_panel_partials": (None, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _RC_P]),
+    "voltrix_launch_xcd_ranges_of_work": (None, [_P, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_xcd_ranges_of_windows": (None, [_P, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_xcd_ranges_of_panels": (None, [_P, _P, _I, _I, _I, _P, _P, _P, _RC_P]),
+    "voltrix_panel_parts_workspace_bytes": (_L, [_I]),
+    "voltrix_launch_panel_parts_count": (None, [_P, _I, _I, _P, _P, _P, _P, _RC_P]),
+    "voltrix_launch_panel_parts_fill": (None, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_fused_f16": (None, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_fused_bf16": (None, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _RC_P]),
+    "voltrix_fused_panel_geometry": (None, [_RC_P, _RC_P]),
+    "voltrix_fused_records_workspace_bytes": (_L, [_I]),
+    "voltrix_launch_fused_records_count": (None, [_P, _P, _I, _P, _P, _P, _RC_P]),
+    "voltrix_launch_fused_records_fill": (None, [_P, _P, _P, _I, _P, _L, _P, _P, _RC_P]),
+    "voltrix_panel_plan_workspace_bytes": (_L, [_I, _I, _I]),
+    "voltrix_launch_panel_plan_count": (None, [_P, _P, _I, _I, _L, _I, _I, _I, _P, _P, _P, _P, _P, _RC_P]),
+    "voltrix_launch_panel_plan_fill": (None, [_P, _P, _I, _I, _L, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _P, _RC_P]),
+    "voltrix_launch_panel_order": (None, [_P, _I, _I, _P, _P, _P, _RC_P]),
+    "voltrix_spmm_default_tile": (None, [_I, _I, _RC_P, _RC_P, _RC_P]),
+    "voltrix_spmm_num_tiles": (_I, [_I]),
+    "voltrix_spmm_tile_at": (None, [_I, _I, _RC_P, _RC_P, _RC_P]),
+    "voltrix_launch_window_order": (None, [_P, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_bf16": (None, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_bf16_tile": (None, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _RC_P]),
+    "voltrix_launch_cast_f32_f16": (None, [_P, _P, _L, _P, _RC_P]),
+    "voltrix_launch_cast_f32_f16_scaled": (None, [_P, _P, _L, _P, _P, _RC_P]),
+    "voltrix_launch_scale_rows": (None, [_P, _P, _P, _L, _I, _I, _P, _RC_P]),
+    "voltrix_launch_spmm_csr_rows": (None, [_P, _P, _I, _I, _P, _I, _P, _I, _P, _RC_P]),
+    "voltrix_launch_spmm_csr_rows_weighted": (None, [_P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _RC_P]),
+    "voltrix_launch_scatter_values": (None, [_P, _P, _P, _L, _I, _P, _RC_P]),
+    "voltrix_launch_sddmm_csr": (None, [_P, _P, _I, _L, _I, _P, _I, _P, _I, _P, _P, _RC_P]),
+    "voltrix_edge_softmax_workspace_bytes": (_L, [_I, _L]),
+    "voltrix_launch_edge_softmax_csr": (None, [_P, _I, _L, _P, _F, _P, _P, _P, _RC_P]),
+    "voltrix_launch_edge_softmax_backward_csr": (None, [_P, _I, _L, _P, _P, _F, _P, _P, _P, _RC_P]),
+    "voltrix_launch_sddmm_heads_csr": (None, [_P, _P, _I, _L, _I, _I, _P, _I, _P, _I, _P, _P, _RC_P]),
+    "voltrix_edge_softmax_heads_workspace_bytes": (_L, [_I, _L, _I]),
+    "voltrix_launch_edge_softmax_heads_csr": (None, [_P, _I, _L, _I, _P, _F, _P, _P, _P, _RC_P]),
+    "voltrix_launch_edge_softmax_heads_backward_csr": (None, [_P, _I, _L, _I, _P, _P, _F, _P, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_csr_heads": (None, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _RC_P]),
+    "voltrix_launch_gat_score_csr": (None, [_P, _P, _I, _L, _I, _P, _P, _F, _P, _P, _RC_P]),
+    "voltrix_gat_score_workspace_bytes": (_L, [_I, _L, _I]),
+    "voltrix_launch_gat_score_rowsum_csr": (None, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _F, _P, _P, _P, _RC_P]),
+    "voltrix_launch_gatv2_score_csr": (None, [_P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _F, _P, _P, _RC_P]),
+    "voltrix_launch_gatv2_rowsum_csr": (None, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _F, _P, _P, _RC_P]),
+    "voltrix_launch_attn_aggregate_csr": (None, [_P, _P, _P, _I, _L, _I, _I, _P, _I, _F, _P, _P, _P, _P, _RC_P]),
+    "voltrix_launch_attn_aggregate_grad_scores_csr": (None, [_P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _F, _P, _P, _RC_P]),
+    "voltrix_launch_attn_aggregate_grad_feat_csr": (None, [_P, _P, _P, _I, _L, _I, _I, _P, _I, _P, _P, _P, _F, _P, _P, _RC_P]),
+    "voltrix_launch_dropout_mask": (None, [_L, _I, _U32, _U64, _U64, _P, _P, _RC_P]),
+    "voltrix_launch_attn_aggregate_dropout_csr": (None, [_P, _P, _P, _I, _L, _I, _I, _P, _I, _F, _P, _P, _P, _P, _F, _P, _RC_P]),
+    "voltrix_launch_attn_aggregate_dropout_grad_scores_csr": (None, [_P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _F, _P, _P, _F, _P, _RC_P]),
+    "voltrix_launch_attn_aggregate_dropout_grad_feat_csr": (None, [_P, _P, _P, _I, _L, _I, _I, _P, _I, _P, _P, _P, _F, _P, _P, _F, _P, _RC_P]),
+    "voltrix_csr_preprocess_workspace_bytes": (_L, [_I, _I, _L, _I]),
+    "voltrix_launch_csr_window_count": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
+    "voltrix_launch_csr_fill": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
+    "voltrix_unit_table_workspace_bytes": (_L, [_I]),
+    "voltrix_unit_table_fill_workspace_bytes": (_L, [_L]),
+    "voltrix_launch_unit_table_count": (None, [_P, _I, _I, _P, _P, _P, _P, _RC_P]),
+    "voltrix_launch_unit_table_fill": (None, [_P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _RC_P]),
+    "voltrix_csr_transpose_workspace_bytes": (_L, [_L]),
+    "voltrix_launch_csr_transpose": (None, [_P, _P, _I, _I, _L, _P, _P, _P, _P, _RC_P]),
+    "voltrix_launch_bfs_seed": (None, [_I, _I, _P, _P, _P, _P, _P, _RC_P]),
+    "voltrix_launch_bfs_levels": (None, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _RC_P]),
+    "voltrix_cm_rank_workspace_bytes": (_L, [_L]),
+    "voltrix_launch_cm_rank": (None, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _RC_P, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_chol_inv_transposed": (None, [_P, _I, _D, _P, _P, _RC_P]),
+}
+SYMBOLS = tuple(SIGNATURES)
 
 
 def build(force: bool = False) -> str:
@@ -123,15 +130,11 @@ def lib() -> ctypes.CDLL:
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             build()
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.voltrix_abi_version.restype = ctypes.c_int
-        _lib.voltrix_spmm_num_tiles.restype = ctypes.c_int
-        for name in SYMBOLS:      # every size function returns int64_t: the default restype (int) would cut a size above 2^31 - 1 short,
-            if name.endswith("_workspace_bytes"):      # and the workspace allocated from it would be too small for the launch
-                getattr(_lib, name).restype = ctypes.c_int64
-        for name in SYMBOLS:
-            if name.startswith("voltrix_launch_") or name in ("voltrix_spmm_default_tile", "voltrix_spmm_tile_at"):
-                getattr(_lib, name).restype = None
+        loaded = ctypes.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in SIGNATURES.items():   # e.g. a size function left at the default restype (int) would cut a
+            fn = getattr(loaded, name)                         # size above 2^31 - 1 short, and the workspace allocated from it would
+            fn.restype, fn.argtypes = restype, argtypes        # be too small for the launch
+        _lib = loaded
     return _lib
 
 
@@ -148,23 +151,92 @@ def check(rc: int, what: str) -> None:
         raise VoltrixError(f"{what}: return code {rc} ({_RC.get(rc, 'unknown')})")
 
 
+def _call(name: str, *args) -> int:
+    """Entry point ``name`` on ``args`` and a return-code slot of its own (the last parameter of every launcher); returns the code."""
+    rc = ctypes.c_int(-1)
+    getattr(lib(), name)(*args, rc)
+    return rc.value
+
+
+def _checked(name: str, *args) -> None:
+    """The same for the wrappers that raise: ``VoltrixError`` unless the code is 0 (not through ``_call``: one frame less per launch)."""
+    rc = ctypes.c_int(-1)
+    getattr(lib(), name)(*args, rc)
+    if rc.value != 0:
+        check(rc.value, name)
+
+
 def _ptr(t):
+    """``t``'s address as a ``void*`` for raw calls of the library (tests, experiments): unlike a plain int it keeps its 64 bits in a
+    call of a function without argument types as well.  The wrappers below pass ``data_ptr()`` itself."""
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _opt(t):
+    """The address of an optional tensor argument: None, the null pointer, where there is none."""
+    return None if t is None else t.data_ptr()
+
+
+def _stream_of(stream):
+    """``stream``, or torch's current stream where the caller gave None."""
+    if stream is not None:
+        return stream
+    import torch
+
+    return torch.cuda.current_stream().cuda_stream
+
+
+_CODES = None
+
+
+def _dtype_code(dtype) -> int:
+    """The ``dtype`` argument of the entry points that take one: 0 fp32 / 1 fp16 / 2 bfloat16."""
+    import torch
+
+    global _CODES
+    if _CODES is None:
+        _CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+    return _CODES[dtype]
+
+
+# ---- kernel-isolated timing hook (utils.KernelTimer / bench_kineto): a launch wrapper decorated with ``@_timed(label)`` is bracketed
+# ---- by an event pair on its stream while a timer is active; free otherwise.  The stream is the wrapper's parameter named ``stream``.
+def _timed(label: str):
+    import functools
+    import inspect
+
+    def decorate(fn):
+        stream_index = list(inspect.signature(fn).parameters).index("stream")
+
+        @functools.wraps(fn)
+        def wrapper(*args, **kwargs):
+            from .utils import KernelTimer
+
+            if KernelTimer.active is None:
+                return fn(*args, **kwargs)
+            stream = kwargs.get("stream")
+            if stream is None and len(args) > stream_index:
+                stream = args[stream_index]
+            with KernelTimer.active.bracket(label, stream):
+                return fn(*args, **kwargs)
+
+        wrapper.timer_label, wrapper.stream_index = label, stream_index
+        return wrapper
+
+    return decorate
 
 
 def default_tile(embedding_dim: int, is_f16: bool):
     fs, d, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    lib().voltrix_spmm_default_tile(ctypes.c_int(embedding_dim), ctypes.c_int(int(is_f16)), ctypes.byref(fs),
-                                    ctypes.byref(d), ctypes.byref(w))
+    lib().voltrix_spmm_default_tile(embedding_dim, int(is_f16), fs, d, w)
     return fs.value, d.value, w.value
 
 
 def tiles(is_f16: bool):
     out = []
-    for i in range(lib().voltrix_spmm_num_tiles(ctypes.c_int(int(is_f16)))):
+    for i in range(lib().voltrix_spmm_num_tiles(int(is_f16))):
         fs, d, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        lib().voltrix_spmm_tile_at(ctypes.c_int(int(is_f16)), ctypes.c_int(i), ctypes.byref(fs), ctypes.byref(d),
-                                   ctypes.byref(w))
+        lib().voltrix_spmm_tile_at(int(is_f16), i, fs, d, w)
         out.append((fs.value, d.value, w.value))
     return out
 
@@ -174,45 +246,37 @@ SLAB_AUTO, SLAB_ONE_GRID, SLAB_LAUNCHES = -1, 0, 1                       # `slab
 
 
 def csr_preprocess_workspace_bytes(num_nodes: int, num_cols: int, num_edges: int, path=None) -> int:
-    return int(lib().voltrix_csr_preprocess_workspace_bytes(ctypes.c_int(num_nodes), ctypes.c_int(num_cols),
-                                                            ctypes.c_int64(num_edges), ctypes.c_int(CSR_PATHS[path])))
+    return int(lib().voltrix_csr_preprocess_workspace_bytes(num_nodes, num_cols, num_edges, CSR_PATHS[path]))
 
 
+@_timed("csr_window_count")
 def launch_csr_window_count(indptr, indices, num_nodes, num_cols, workspace, block_partition, pointer1, status,
                             stream, path=None) -> None:
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_csr_window_count(_ptr(indptr), _ptr(indices), ctypes.c_int(num_nodes), ctypes.c_int(num_cols),
-                                          ctypes.c_int64(indices.numel()), ctypes.c_int(CSR_PATHS[path]), _ptr(workspace),
-                                          _ptr(block_partition), _ptr(pointer1), _ptr(status), ctypes.c_void_p(stream),
-                                          ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_csr_window_count")
+    _checked("voltrix_launch_csr_window_count", indptr.data_ptr(), indices.data_ptr(), num_nodes, num_cols, indices.numel(),
+             CSR_PATHS[path], workspace.data_ptr(), block_partition.data_ptr(), pointer1.data_ptr(), status.data_ptr(), stream)
 
 
+@_timed("csr_fill")
 def launch_csr_fill(indptr, indices, num_nodes, num_cols, workspace, pointer1, hspa_packed, hind, stream, path=None) -> None:
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_csr_fill(_ptr(indptr), _ptr(indices), ctypes.c_int(num_nodes), ctypes.c_int(num_cols),
-                                  ctypes.c_int64(indices.numel()), ctypes.c_int(CSR_PATHS[path]), _ptr(workspace),
-                                  _ptr(pointer1), _ptr(hspa_packed), _ptr(hind), ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_csr_fill")
+    _checked("voltrix_launch_csr_fill", indptr.data_ptr(), indices.data_ptr(), num_nodes, num_cols, indices.numel(), CSR_PATHS[path],
+             workspace.data_ptr(), pointer1.data_ptr(), hspa_packed.data_ptr(), hind.data_ptr(), stream)
 
 
+@_timed("spmm")
 def launch_spmm(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_dim, input_ptr, output_ptr, is_f16,
                 tile, stream, window_order=0, out_scale=0) -> int:
     """Raw-pointer launch (used by bench.py and the tests); ``window_order`` is 0 (natural) or the device pointer of
     the schedule written by :func:`launch_window_order`; ``out_scale`` is 0 or the device pointer of the float written
     by :func:`launch_cast_f32_f16_scaled`.  Returns the return code."""
-    rc = ctypes.c_int(-1)
     if is_f16 == "bf16":  # operand kind: True = fp16, False = fp32, "bf16" = bfloat16 (same tiles as fp16)
-        fn = lib().voltrix_launch_spmm_bf16_tile
+        name = "voltrix_launch_spmm_bf16_tile"
     else:
-        fn = lib().voltrix_launch_spmm_f16_tile if is_f16 else lib().voltrix_launch_spmm_f32_tile
-    fn(ctypes.c_void_p(blk_offsets), ctypes.c_void_p(hspa_packed), ctypes.c_void_p(hind), ctypes.c_int(num_nodes),
-       ctypes.c_int(num_edges), ctypes.c_int(embedding_dim), ctypes.c_void_p(input_ptr), ctypes.c_void_p(output_ptr),
-       ctypes.c_int(tile[0]), ctypes.c_int(tile[1]), ctypes.c_int(tile[2]), ctypes.c_void_p(window_order),
-       ctypes.c_void_p(out_scale), ctypes.c_void_p(stream), ctypes.byref(rc))
-    return rc.value
+        name = "voltrix_launch_spmm_f16_tile" if is_f16 else "voltrix_launch_spmm_f32_tile"
+    return _call(name, blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_dim, input_ptr, output_ptr, tile[0], tile[1],
+                 tile[2], window_order, out_scale, stream)
 
 
+@_timed("spmm")
 def launch_spmm_sched(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_dim, input_ptr, output_ptr, tile,
                       stream, window_order=0, out_scale=0, atomic_out=False, bf16=False, table=None, partials=0,
                       row_map=0, units_per_wave=1) -> int:
@@ -220,29 +284,19 @@ def launch_spmm_sched(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embe
     result onto a pre-zeroed output with float atomics (two-level format without a join pass); ``table`` = a
     ``voltrix.schedule.UnitTable`` (replaces ``window_order``), ``partials`` = device pointer of its partial tiles.
     Returns the return code."""
-    rc = ctypes.c_int(-1)
-    fn = lib().voltrix_launch_spmm_bf16_sched if bf16 else lib().voltrix_launch_spmm_f16_sched
-    fn(ctypes.c_void_p(blk_offsets), ctypes.c_void_p(hspa_packed), ctypes.c_void_p(hind), ctypes.c_int(num_nodes),
-       ctypes.c_int(num_edges), ctypes.c_int(embedding_dim), ctypes.c_void_p(input_ptr), ctypes.c_void_p(output_ptr),
-       ctypes.c_int(tile[0]), ctypes.c_int(tile[1]), ctypes.c_int(tile[2]), ctypes.c_void_p(window_order),
-       ctypes.c_void_p(out_scale), ctypes.c_int(int(atomic_out)),
-       ctypes.c_void_p(table.units.data_ptr() if table is not None else 0),
-       ctypes.c_void_p(table.unit_ptr.data_ptr() if table is not None else 0),
-       ctypes.c_int(table.max_units_per_xcd if table is not None else 0), ctypes.c_void_p(partials),
-       ctypes.c_void_p(row_map), ctypes.c_int(int(units_per_wave)), ctypes.c_void_p(stream), ctypes.byref(rc))
-    return rc.value
+    units, unit_ptr, max_units = (table.units.data_ptr(), table.unit_ptr.data_ptr(), table.max_units_per_xcd) if table is not None \
+        else (None, None, 0)
+    return _call("voltrix_launch_spmm_bf16_sched" if bf16 else "voltrix_launch_spmm_f16_sched", blk_offsets, hspa_packed, hind,
+                 num_nodes, num_edges, embedding_dim, input_ptr, output_ptr, tile[0], tile[1], tile[2], window_order, out_scale,
+                 int(atomic_out), units, unit_ptr, max_units, partials, row_map, int(units_per_wave), stream)
 
 
+@_timed("combine_partials")
 def launch_combine_partials(table, partials_ptr, output_ptr, num_nodes, embedding_dim, accumulate, stream,
                             row_map=0) -> int:
     """Sum the partial tiles of the cut windows of ``table`` (a ``voltrix.schedule.UnitTable``) into the output."""
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_combine_partials(ctypes.c_void_p(table.cuts.data_ptr()), ctypes.c_int(table.num_cuts),
-                                          ctypes.c_void_p(partials_ptr), ctypes.c_void_p(output_ptr),
-                                          ctypes.c_int(num_nodes), ctypes.c_int(embedding_dim),
-                                          ctypes.c_int(int(accumulate)), ctypes.c_void_p(row_map),
-                                          ctypes.c_void_p(stream), ctypes.byref(rc))
-    return rc.value
+    return _call("voltrix_launch_combine_partials", table.cuts.data_ptr(), table.num_cuts, partials_ptr, output_ptr, num_nodes,
+                 embedding_dim, int(accumulate), row_map, stream)
 
 
 def build_unit_table(blk_offsets, num_nodes: int, max_stages: int = 0, stream=None, xcd_ptr=None):
@@ -253,26 +307,19 @@ def build_unit_table(blk_offsets, num_nodes: int, max_stages: int = 0, stream=No
     import torch
 
     dev = blk_offsets.device
-    stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    workspace = torch.empty(max(16, int(lib().voltrix_unit_table_workspace_bytes(ctypes.c_int(num_nodes)))),
-                            dtype=torch.uint8, device=dev)
+    stream = _stream_of(stream)
+    workspace = torch.empty(max(16, int(lib().voltrix_unit_table_workspace_bytes(num_nodes))), dtype=torch.uint8, device=dev)
     header = torch.empty(8, dtype=torch.int32, device=dev)
-    rc = ctypes.c_int(-1)
-    xp = ctypes.c_void_p(xcd_ptr.data_ptr() if xcd_ptr is not None else 0)
-    lib().voltrix_launch_unit_table_count(_ptr(blk_offsets), ctypes.c_int(num_nodes), ctypes.c_int(int(max_stages)), xp,
-                                          _ptr(workspace), _ptr(header), ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_unit_table_count")
+    _checked("voltrix_launch_unit_table_count", blk_offsets.data_ptr(), num_nodes, int(max_stages), _opt(xcd_ptr),
+             workspace.data_ptr(), header.data_ptr(), stream)
     head = [int(v) for v in header.tolist()]   # the sync
     num_units, num_cuts, top = head[0], head[1], head[5]
     units = torch.empty((num_units, 4), dtype=torch.int32, device=dev)
     cuts = torch.empty((num_cuts, 4), dtype=torch.int32, device=dev)
     unit_ptr = torch.empty(9, dtype=torch.int32, device=dev)
-    fill_ws = torch.empty(max(16, int(lib().voltrix_unit_table_fill_workspace_bytes(ctypes.c_int64(num_units)))),
-                          dtype=torch.uint8, device=dev)
-    lib().voltrix_launch_unit_table_fill(_ptr(blk_offsets), ctypes.c_int(num_nodes), xp, _ptr(workspace), _ptr(fill_ws),
-                                         ctypes.c_int(num_units), ctypes.c_int(num_cuts), ctypes.c_int(top), _ptr(units),
-                                         _ptr(unit_ptr), _ptr(cuts), ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_unit_table_fill")
+    fill_ws = torch.empty(max(16, int(lib().voltrix_unit_table_fill_workspace_bytes(num_units))), dtype=torch.uint8, device=dev)
+    _checked("voltrix_launch_unit_table_fill", blk_offsets.data_ptr(), num_nodes, _opt(xcd_ptr), workspace.data_ptr(),
+             fill_ws.data_ptr(), num_units, num_cuts, top, units.data_ptr(), unit_ptr.data_ptr(), cuts.data_ptr(), stream)
     return units, unit_ptr, cuts, head
 
 
@@ -283,29 +330,21 @@ def build_stream_table(blk_offsets, hspa_packed, hind, num_nodes: int, run_cost:
     import torch
 
     dev = blk_offsets.device
-    stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    L = lib()
-    workspace = torch.empty(max(16, int(L.voltrix_stream_table_workspace_bytes(ctypes.c_int(num_nodes)))), dtype=torch.uint8,
-                            device=dev)
+    stream = _stream_of(stream)
+    workspace = torch.empty(max(16, int(lib().voltrix_stream_table_workspace_bytes(num_nodes))), dtype=torch.uint8, device=dev)
     header = torch.empty(8, dtype=torch.int32, device=dev)
-    rc = ctypes.c_int(-1)
-    L.voltrix_launch_stream_table_count(_ptr(blk_offsets), _ptr(hspa_packed), _ptr(hind), ctypes.c_int(num_nodes),
-                                        ctypes.c_int(int(run_cost)), ctypes.c_int(int(cut_stages)), _ptr(workspace),
-                                        _ptr(header), ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_stream_table_count")
+    _checked("voltrix_launch_stream_table_count", blk_offsets.data_ptr(), hspa_packed.data_ptr(), hind.data_ptr(), num_nodes,
+             int(run_cost), int(cut_stages), workspace.data_ptr(), header.data_ptr(), stream)
     num_units, num_cuts, num_slots, run_bound, rcost, cut = [int(v) for v in header.tolist()][:6]   # the sync
     units = torch.empty((num_units, 8), dtype=torch.int32, device=dev)
     cuts = torch.empty((num_cuts, 4), dtype=torch.int32, device=dev)
     runs = torch.empty((max(1, run_bound), 4), dtype=torch.int32, device=dev)
     run_ptr = torch.empty(9, dtype=torch.int32, device=dev)
     header2 = torch.empty(4, dtype=torch.int32, device=dev)
-    fill_ws = torch.empty(max(16, int(L.voltrix_stream_table_fill_workspace_bytes(ctypes.c_int64(num_units)))),
-                          dtype=torch.uint8, device=dev)
-    L.voltrix_launch_stream_table_fill(_ptr(blk_offsets), ctypes.c_int(num_nodes), _ptr(workspace), _ptr(fill_ws),
-                                       ctypes.c_int(num_units), ctypes.c_int(num_cuts), ctypes.c_int(run_bound),
-                                       ctypes.c_int(max(2, rcost)), _ptr(units), _ptr(cuts), _ptr(runs), _ptr(run_ptr),
-                                       _ptr(header2), ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_stream_table_fill")
+    fill_ws = torch.empty(max(16, int(lib().voltrix_stream_table_fill_workspace_bytes(num_units))), dtype=torch.uint8, device=dev)
+    _checked("voltrix_launch_stream_table_fill", blk_offsets.data_ptr(), num_nodes, workspace.data_ptr(), fill_ws.data_ptr(),
+             num_units, num_cuts, run_bound, max(2, rcost), units.data_ptr(), cuts.data_ptr(), runs.data_ptr(), run_ptr.data_ptr(),
+             header2.data_ptr(), stream)
     num_runs, max_runs, oversized = [int(v) for v in header2.tolist()][:3]
     assert oversized == 0, "stream table with a run of more than 64 units (run_cost > 128?): the kernel cannot walk it"
     return units, runs[:num_runs], run_ptr, cuts, (num_units, num_cuts, num_slots, num_runs, max_runs, rcost, cut)
@@ -316,18 +355,14 @@ def launch_spmm_stream(hspa_packed, hind, num_nodes: int, embedding_dim: int, fe
     """``voltrix_launch_spmm_stream_f16 / _bf16`` on a ``voltrix.schedule.StreamTable`` (the stream kernel through the C-ABI)."""
     import torch
 
-    stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    fn = lib().voltrix_launch_spmm_stream_bf16 if feat.dtype == torch.bfloat16 else lib().voltrix_launch_spmm_stream_f16
+    stream = _stream_of(stream)
+    name = "voltrix_launch_spmm_stream_bf16" if feat.dtype == torch.bfloat16 else "voltrix_launch_spmm_stream_f16"
     from .utils import timed_launch
 
-    rc = ctypes.c_int(-1)
     with timed_launch("spmm_stream", stream):
-        fn(_ptr(hspa_packed), _ptr(hind), ctypes.c_int(num_nodes), ctypes.c_int(embedding_dim), _ptr(feat),
-           ctypes.c_int64(int(input_rows)), _ptr(output), _ptr(table.units), _ptr(table.runs), _ptr(table.run_ptr),
-           ctypes.c_int(table.max_runs_per_xcd), _ptr(partials), ctypes.c_void_p(out_scale.data_ptr() if out_scale is not None else 0),
-           ctypes.c_int(tile[0]), ctypes.c_int(tile[1]), ctypes.c_int(tile[2]), ctypes.c_int(int(slab_policy)),
-           ctypes.c_void_p(stream), ctypes.byref(rc))
-    return rc.value
+        return _call(name, hspa_packed.data_ptr(), hind.data_ptr(), num_nodes, embedding_dim, feat.data_ptr(), int(input_rows),
+                     output.data_ptr(), table.units.data_ptr(), table.runs.data_ptr(), table.run_ptr.data_ptr(),
+                     table.max_runs_per_xcd, partials.data_ptr(), _opt(out_scale), tile[0], tile[1], tile[2], int(slab_policy), stream)
 
 
 def xcd_ranges_of_work(work, align: int = 1, stream=None):
@@ -336,11 +371,7 @@ def xcd_ranges_of_work(work, align: int = 1, stream=None):
     import torch
 
     out = torch.empty(9, dtype=torch.int32, device=work.device)
-    rc = ctypes.c_int(-1)
-    stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    lib().voltrix_launch_xcd_ranges_of_work(_ptr(work), ctypes.c_int(work.numel()), ctypes.c_int(int(align)), _ptr(out),
-                                            ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_xcd_ranges_of_work")
+    _checked("voltrix_launch_xcd_ranges_of_work", work.data_ptr(), work.numel(), int(align), out.data_ptr(), _stream_of(stream))
     return out
 
 
@@ -349,11 +380,7 @@ def xcd_ranges_of_windows(blk_offsets, num_nodes: int, align: int = 1, stream=No
     import torch
 
     out = torch.empty(9, dtype=torch.int32, device=blk_offsets.device)
-    rc = ctypes.c_int(-1)
-    stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    lib().voltrix_launch_xcd_ranges_of_windows(_ptr(blk_offsets), ctypes.c_int(num_nodes), ctypes.c_int(int(align)), _ptr(out),
-                                               ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_xcd_ranges_of_windows")
+    _checked("voltrix_launch_xcd_ranges_of_windows", blk_offsets.data_ptr(), num_nodes, int(align), out.data_ptr(), _stream_of(stream))
     return out
 
 
@@ -364,12 +391,8 @@ def xcd_ranges_of_panels(panel_ptr, resid_blk_offsets, num_nodes: int, panel_row
 
     dev = panel_ptr.device
     out, out_w = torch.empty(9, dtype=torch.int32, device=dev), torch.empty(9, dtype=torch.int32, device=dev)
-    rc = ctypes.c_int(-1)
-    stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    lib().voltrix_launch_xcd_ranges_of_panels(_ptr(panel_ptr), _ptr(resid_blk_offsets), ctypes.c_int(num_nodes),
-                                              ctypes.c_int(panel_rows), ctypes.c_int(int(kstep_cost_x10)), _ptr(out),
-                                              _ptr(out_w), ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_xcd_ranges_of_panels")
+    _checked("voltrix_launch_xcd_ranges_of_panels", panel_ptr.data_ptr(), resid_blk_offsets.data_ptr(), num_nodes, panel_rows,
+             int(kstep_cost_x10), out.data_ptr(), out_w.data_ptr(), _stream_of(stream))
     return out, out_w
 
 
@@ -381,104 +404,76 @@ def build_panel_parts(panel_ptr, cap: int, panel_xcd_ptr=None, stream=None):
 
     dev = panel_ptr.device
     num_panels = panel_ptr.numel() - 1
-    stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    workspace = torch.empty(max(16, int(lib().voltrix_panel_parts_workspace_bytes(ctypes.c_int(num_panels)))),
-                            dtype=torch.uint8, device=dev)
+    stream = _stream_of(stream)
+    workspace = torch.empty(max(16, int(lib().voltrix_panel_parts_workspace_bytes(num_panels))), dtype=torch.uint8, device=dev)
     header = torch.empty(8, dtype=torch.int32, device=dev)
-    rc = ctypes.c_int(-1)
-    xp = ctypes.c_void_p(panel_xcd_ptr.data_ptr() if panel_xcd_ptr is not None else 0)
-    lib().voltrix_launch_panel_parts_count(_ptr(panel_ptr), ctypes.c_int(num_panels), ctypes.c_int(int(cap)), xp,
-                                           _ptr(workspace), _ptr(header), ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_panel_parts_count")
+    _checked("voltrix_launch_panel_parts_count", panel_ptr.data_ptr(), num_panels, int(cap), _opt(panel_xcd_ptr), workspace.data_ptr(),
+             header.data_ptr(), stream)
     head = [int(v) for v in header.tolist()]   # the sync
     parts = torch.empty((head[0], 4), dtype=torch.int32, device=dev)
     cuts = torch.empty((max(1, head[1]), 4), dtype=torch.int32, device=dev)
     part_xcd_ptr = torch.empty(9, dtype=torch.int32, device=dev)
-    lib().voltrix_launch_panel_parts_fill(_ptr(panel_ptr), ctypes.c_int(num_panels), ctypes.c_int(int(cap)), xp,
-                                          _ptr(workspace), _ptr(parts), _ptr(part_xcd_ptr), _ptr(cuts),
-                                          ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_panel_parts_fill")
+    _checked("voltrix_launch_panel_parts_fill", panel_ptr.data_ptr(), num_panels, int(cap), _opt(panel_xcd_ptr), workspace.data_ptr(),
+             parts.data_ptr(), part_xcd_ptr.data_ptr(), cuts.data_ptr(), stream)
     return parts, part_xcd_ptr, cuts[:head[1]], head
 
 
 def spmm_f32_workspace_bytes(input_rows: int, embedding_dim: int) -> int:
-    return int(lib().voltrix_spmm_f32_workspace_bytes(ctypes.c_int64(input_rows), ctypes.c_int(embedding_dim)))
+    return int(lib().voltrix_spmm_f32_workspace_bytes(input_rows, embedding_dim))
 
 
+@_timed("spmm_f32_as_f16")
 def launch_spmm_f32_as_f16(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_dim, feat, output, workspace,
                            stream) -> int:
     """Route B for fp32 features: the reference's launch() arguments + a caller-owned workspace; scaled-fp16 operand on the
     default tile (include/voltrix_capi.h).  Tensors in, return code out."""
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_spmm_f32_as_f16(_ptr(blk_offsets), _ptr(hspa_packed), _ptr(hind), ctypes.c_int(num_nodes),
-                                         ctypes.c_int(num_edges), ctypes.c_int(embedding_dim), _ptr(feat),
-                                         ctypes.c_int64(feat.shape[0]), _ptr(output), _ptr(workspace),
-                                         ctypes.c_void_p(stream), ctypes.byref(rc))
-    return rc.value
+    return _call("voltrix_launch_spmm_f32_as_f16", blk_offsets.data_ptr(), hspa_packed.data_ptr(), hind.data_ptr(), num_nodes,
+                 num_edges, embedding_dim, feat.data_ptr(), feat.shape[0], output.data_ptr(), workspace.data_ptr(), stream)
 
 
+@_timed("spmm_panel")
 def launch_spmm_panel(plan, input_ptr, output_ptr, embedding_dim, accumulate, bf16, tile, out_scale, stream,
                       input_rows: int = 0, slab_policy: int = SLAB_AUTO, partials_ptr: int = 0) -> int:
     """Panel kernel (shared-column half of the two-level format); ``plan`` = voltrix.hybrid.PanelPlan, ``tile`` =
     (fs, depth, ksteps); ``input_rows`` = rows of the dense operand (0: the plan's rows).  A plan with a part table
     (``plan.parts``) goes through ``voltrix_launch_spmm_panel_parts_*`` with ``partials_ptr`` = the call's partial-tile
     buffer.  Returns the return code."""
-    rc = ctypes.c_int(-1)
+    panel = (plan.panel_ptr.data_ptr(), plan.panel_cols.data_ptr(), plan.panel_bits.data_ptr())
+    launch = (plan.num_nodes, embedding_dim, input_ptr, input_rows, output_ptr, int(accumulate), tile[0], tile[1], plan.waves,
+              plan.row_blocks, tile[2], slab_policy, out_scale, stream)
     parts = getattr(plan, "parts", None)
     if parts is not None:
-        fn = lib().voltrix_launch_spmm_panel_parts_bf16 if bf16 else lib().voltrix_launch_spmm_panel_parts_f16
-        fn(_ptr(plan.panel_ptr), _ptr(plan.panel_cols), _ptr(plan.panel_bits), _ptr(parts.parts), ctypes.c_int(parts.num_parts),
-           _ptr(parts.xcd_ptr), ctypes.c_int(parts.max_parts_per_xcd), ctypes.c_void_p(partials_ptr),
-           ctypes.c_int(plan.num_nodes), ctypes.c_int(embedding_dim), ctypes.c_void_p(input_ptr), ctypes.c_int64(input_rows),
-           ctypes.c_void_p(output_ptr), ctypes.c_int(int(accumulate)), ctypes.c_int(tile[0]), ctypes.c_int(tile[1]),
-           ctypes.c_int(plan.waves), ctypes.c_int(plan.row_blocks), ctypes.c_int(tile[2]), ctypes.c_int(slab_policy),
-           ctypes.c_void_p(out_scale), ctypes.c_void_p(stream), ctypes.byref(rc))
-        return rc.value
-    fn = lib().voltrix_launch_spmm_panel_bf16 if bf16 else lib().voltrix_launch_spmm_panel_f16
-    order = plan.panel_order.data_ptr() if plan.panel_order is not None else 0
+        return _call("voltrix_launch_spmm_panel_parts_bf16" if bf16 else "voltrix_launch_spmm_panel_parts_f16", *panel,
+                     parts.parts.data_ptr(), parts.num_parts, parts.xcd_ptr.data_ptr(), parts.max_parts_per_xcd, partials_ptr, *launch)
     xcd_ptr = getattr(plan, "xcd_ptr", None)
-    fn(_ptr(plan.panel_ptr), _ptr(plan.panel_cols), _ptr(plan.panel_bits), ctypes.c_void_p(order),
-       ctypes.c_void_p(xcd_ptr.data_ptr() if xcd_ptr is not None else 0),
-       ctypes.c_int(plan.max_panels_per_xcd if xcd_ptr is not None else 0), ctypes.c_int(plan.num_nodes), ctypes.c_int(embedding_dim), ctypes.c_void_p(input_ptr), ctypes.c_int64(input_rows),
-       ctypes.c_void_p(output_ptr), ctypes.c_int(int(accumulate)), ctypes.c_int(tile[0]), ctypes.c_int(tile[1]),
-       ctypes.c_int(plan.waves), ctypes.c_int(plan.row_blocks), ctypes.c_int(tile[2]), ctypes.c_int(slab_policy),
-       ctypes.c_void_p(out_scale), ctypes.c_void_p(stream), ctypes.byref(rc))
-    return rc.value
+    return _call("voltrix_launch_spmm_panel_bf16" if bf16 else "voltrix_launch_spmm_panel_f16", *panel, _opt(plan.panel_order),
+                 _opt(xcd_ptr), plan.max_panels_per_xcd if xcd_ptr is not None else 0, *launch)
 
 
 def launch_combine_panel_partials(parts, partials_ptr, output_ptr, num_nodes, embedding_dim, panel_rows, accumulate,
                                   stream) -> int:
     """``output (+)= `` the partial tiles of the cut panels, pieces in slot order (``parts`` = voltrix.hybrid.PanelParts)."""
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_combine_panel_partials(_ptr(parts.cuts), ctypes.c_int(parts.num_cuts), ctypes.c_void_p(partials_ptr),
-                                                ctypes.c_void_p(output_ptr), ctypes.c_int(num_nodes),
-                                                ctypes.c_int(embedding_dim), ctypes.c_int(panel_rows),
-                                                ctypes.c_int(int(accumulate)), ctypes.c_void_p(stream), ctypes.byref(rc))
-    return rc.value
+    return _call("voltrix_launch_combine_panel_partials", parts.cuts.data_ptr(), parts.num_cuts, partials_ptr, output_ptr, num_nodes,
+                 embedding_dim, panel_rows, int(accumulate), stream)
 
 
+@_timed("spmm_fused")
 def launch_spmm_fused(plan, fused, input_ptr, output_ptr, embedding_dim, bf16, tile, out_scale, stream,
                       pace_blocks: int = 0) -> int:
     """The two-level product in one launch; ``plan`` = voltrix.hybrid.PanelPlan (8 waves x 4 row blocks), ``fused`` =
     voltrix.hybrid.FusedRecords (4 waves x 8 row blocks), ``tile`` = (fs, depth), ``pace_blocks`` = sync points per column
     sweep between the workgroups of an XCD (0: none).  Returns the return code."""
-    rc = ctypes.c_int(-1)
-    fn = lib().voltrix_launch_spmm_fused_bf16 if bf16 else lib().voltrix_launch_spmm_fused_f16
-    order = plan.panel_order.data_ptr() if plan.panel_order is not None else 0
     xcd_ptr = getattr(plan, "xcd_ptr", None)
-    fn(_ptr(plan.panel_ptr), _ptr(plan.panel_cols), _ptr(plan.panel_bits), ctypes.c_void_p(order),
-       ctypes.c_void_p(xcd_ptr.data_ptr() if xcd_ptr is not None else 0),
-       ctypes.c_int(plan.max_panels_per_xcd if xcd_ptr is not None else 0), _ptr(fused.wave_ptr),
-       _ptr(fused.records), ctypes.c_int(plan.num_nodes), ctypes.c_int(embedding_dim), ctypes.c_void_p(input_ptr),
-       ctypes.c_void_p(output_ptr), ctypes.c_int(tile[0]), ctypes.c_int(tile[1]), ctypes.c_int(int(pace_blocks)),
-       ctypes.c_void_p(out_scale), ctypes.c_void_p(stream), ctypes.byref(rc))
-    return rc.value
+    return _call("voltrix_launch_spmm_fused_bf16" if bf16 else "voltrix_launch_spmm_fused_f16", plan.panel_ptr.data_ptr(),
+                 plan.panel_cols.data_ptr(), plan.panel_bits.data_ptr(), _opt(plan.panel_order), _opt(xcd_ptr),
+                 plan.max_panels_per_xcd if xcd_ptr is not None else 0, fused.wave_ptr.data_ptr(), fused.records.data_ptr(),
+                 plan.num_nodes, embedding_dim, input_ptr, output_ptr, tile[0], tile[1], int(pace_blocks), out_scale, stream)
 
 
 def fused_panel_geometry():
     """``(waves, row_blocks)`` of the one-launch kernel's 512-row panel, asked of the library (4 x 8 since round 4)."""
     waves, row_blocks = ctypes.c_int(0), ctypes.c_int(0)
-    lib().voltrix_fused_panel_geometry(ctypes.byref(waves), ctypes.byref(row_blocks))
+    lib().voltrix_fused_panel_geometry(waves, row_blocks)
     assert waves.value * row_blocks.value * 16 == 512, (waves.value, row_blocks.value)
     return waves.value, row_blocks.value
 
@@ -489,132 +484,61 @@ def build_fused_records(blk_offsets, hspa_packed, hind, num_nodes: int, stream=N
     import torch
 
     dev = blk_offsets.device
-    stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    stream = _stream_of(stream)
     num_waves = fused_panel_geometry()[0] * ((num_nodes + 511) // 512)
-    workspace = torch.empty(max(16, int(lib().voltrix_fused_records_workspace_bytes(ctypes.c_int(num_nodes)))),
-                            dtype=torch.uint8, device=dev)
+    workspace = torch.empty(max(16, int(lib().voltrix_fused_records_workspace_bytes(num_nodes))), dtype=torch.uint8, device=dev)
     wave_ptr = torch.empty(num_waves + 1, dtype=torch.int32, device=dev)
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_fused_records_count(_ptr(blk_offsets), _ptr(hspa_packed), ctypes.c_int(num_nodes), _ptr(workspace),
-                                             _ptr(wave_ptr), ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_fused_records_count")
+    _checked("voltrix_launch_fused_records_count", blk_offsets.data_ptr(), hspa_packed.data_ptr(), num_nodes, workspace.data_ptr(),
+             wave_ptr.data_ptr(), stream)
     num_records = int(wave_ptr[-1])   # the sync
     assert 0 <= num_records <= 4 * (hspa_packed.numel() // 16 + 1), num_records   # at most one record per TC block
     records = torch.empty((num_records + 1, 64), dtype=torch.int32, device=dev).view(torch.uint32)
-    lib().voltrix_launch_fused_records_fill(_ptr(blk_offsets), _ptr(hspa_packed), _ptr(hind), ctypes.c_int(num_nodes),
-                                            _ptr(wave_ptr), ctypes.c_int64(num_records), _ptr(records),
-                                            ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_fused_records_fill")
+    _checked("voltrix_launch_fused_records_fill", blk_offsets.data_ptr(), hspa_packed.data_ptr(), hind.data_ptr(), num_nodes,
+             wave_ptr.data_ptr(), num_records, records.data_ptr(), stream)
     return wave_ptr, records, num_records
 
 
 def launch_panel_order(panel_ptr, num_panels: int, order_out, stream, group: int = 1, xcd_ptr=None) -> None:
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_panel_order(_ptr(panel_ptr), ctypes.c_int(num_panels), ctypes.c_int(group),
-                                     ctypes.c_void_p(xcd_ptr.data_ptr() if xcd_ptr is not None else 0), _ptr(order_out),
-                                     ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_panel_order")
+    _checked("voltrix_launch_panel_order", panel_ptr.data_ptr(), num_panels, group, _opt(xcd_ptr), order_out.data_ptr(), stream)
 
 
 def panel_plan_workspace_bytes(num_nodes: int, waves: int, row_blocks: int) -> int:
-    return int(lib().voltrix_panel_plan_workspace_bytes(ctypes.c_int(num_nodes), ctypes.c_int(waves),
-                                                        ctypes.c_int(row_blocks)))
+    return int(lib().voltrix_panel_plan_workspace_bytes(num_nodes, waves, row_blocks))
 
 
 def launch_panel_plan_count(indptr, indices, num_nodes, num_cols, waves, row_blocks, tau, workspace, panel_ptr,
                             resid_indptr, status, stream) -> int:
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_panel_plan_count(_ptr(indptr), _ptr(indices), ctypes.c_int(num_nodes), ctypes.c_int(num_cols),
-                                          ctypes.c_int64(indices.numel()), ctypes.c_int(waves), ctypes.c_int(row_blocks),
-                                          ctypes.c_int(tau), _ptr(workspace), _ptr(panel_ptr), _ptr(resid_indptr),
-                                          _ptr(status), ctypes.c_void_p(stream), ctypes.byref(rc))
-    return rc.value
+    return _call("voltrix_launch_panel_plan_count", indptr.data_ptr(), indices.data_ptr(), num_nodes, num_cols, indices.numel(), waves,
+                 row_blocks, tau, workspace.data_ptr(), panel_ptr.data_ptr(), resid_indptr.data_ptr(), status.data_ptr(), stream)
 
 
 def launch_panel_plan_fill(indptr, indices, num_nodes, num_cols, waves, row_blocks, tau, workspace, panel_ptr,
                            resid_indptr, total_ksteps, resid_indices, panel_cols, panel_bits, stream) -> None:
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_panel_plan_fill(_ptr(indptr), _ptr(indices), ctypes.c_int(num_nodes), ctypes.c_int(num_cols),
-                                         ctypes.c_int64(indices.numel()), ctypes.c_int(waves), ctypes.c_int(row_blocks),
-                                         ctypes.c_int(tau), _ptr(workspace), _ptr(panel_ptr), _ptr(resid_indptr),
-                                         ctypes.c_int64(total_ksteps), _ptr(resid_indices), _ptr(panel_cols),
-                                         _ptr(panel_bits), ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_panel_plan_fill")
+    _checked("voltrix_launch_panel_plan_fill", indptr.data_ptr(), indices.data_ptr(), num_nodes, num_cols, indices.numel(), waves,
+             row_blocks, tau, workspace.data_ptr(), panel_ptr.data_ptr(), resid_indptr.data_ptr(), total_ksteps,
+             resid_indices.data_ptr(), panel_cols.data_ptr(), panel_bits.data_ptr(), stream)
 
 
+@_timed("window_order")
 def launch_window_order(blk_offsets, num_nodes, order_out, stream, chunk: int = 256) -> None:
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_window_order(_ptr(blk_offsets), ctypes.c_int(num_nodes), ctypes.c_int(chunk), _ptr(order_out),
-                                      ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_window_order")
+    _checked("voltrix_launch_window_order", blk_offsets.data_ptr(), num_nodes, chunk, order_out.data_ptr(), stream)
 
 
+@_timed("cast_f32_f16")
 def launch_cast_f32_f16(src, dst, stream) -> None:
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_cast_f32_f16(_ptr(src), _ptr(dst), ctypes.c_int64(src.numel()), ctypes.c_void_p(stream),
-                                      ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_cast_f32_f16")
+    _checked("voltrix_launch_cast_f32_f16", src.data_ptr(), dst.data_ptr(), src.numel(), stream)
 
 
-_cast_scaled = None   # the entry point with its argument types set: plain ints convert in C (12 -> 4 us per call on the host)
-
-
+@_timed("cast_f32_f16_scaled")
 def launch_cast_f32_f16_scaled(src, dst, scale, stream) -> None:
     """dst = fp16(src * 2^-e), scale[0] = 2^e (``scale``: float32[2] device tensor); see include/voltrix_capi.h."""
-    global _cast_scaled
-    if _cast_scaled is None:
-        fn = lib().voltrix_launch_cast_f32_f16_scaled
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.POINTER(ctypes.c_int)]
-        _cast_scaled = fn
-    rc = ctypes.c_int(-1)
-    _cast_scaled(src.data_ptr(), dst.data_ptr(), src.numel(), scale.data_ptr(), stream, rc)
-    if rc.value != 0:
-        check(rc.value, "voltrix_launch_cast_f32_f16_scaled")
+    _checked("voltrix_launch_cast_f32_f16_scaled", src.data_ptr(), dst.data_ptr(), src.numel(), scale.data_ptr(), stream)
 
 
-# ---- the CSR / attention launchers: argument types per symbol (include/voltrix_capi.h), set on the first use of a symbol -- with them
-# ---- plain ints and data_ptr() values convert in C (12 -> 4 us per call on the host)
-_P, _I, _L, _F, _RC_P = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.POINTER(ctypes.c_int)
-_U32, _U64 = ctypes.c_uint32, ctypes.c_uint64
-_ARGTYPES = {
-    "voltrix_launch_spmm_csr_rows": [_P, _P, _I, _I, _P, _I, _P, _I, _P, _RC_P],
-    "voltrix_launch_spmm_csr_rows_weighted": [_P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _RC_P],
-    "voltrix_launch_sddmm_csr": [_P, _P, _I, _L, _I, _P, _I, _P, _I, _P, _P, _RC_P],
-    "voltrix_launch_edge_softmax_csr": [_P, _I, _L, _P, _F, _P, _P, _P, _RC_P],
-    "voltrix_launch_edge_softmax_backward_csr": [_P, _I, _L, _P, _P, _F, _P, _P, _P, _RC_P],
-    "voltrix_launch_sddmm_heads_csr": [_P, _P, _I, _L, _I, _I, _P, _I, _P, _I, _P, _P, _RC_P],
-    "voltrix_launch_edge_softmax_heads_csr": [_P, _I, _L, _I, _P, _F, _P, _P, _P, _RC_P],
-    "voltrix_launch_edge_softmax_heads_backward_csr": [_P, _I, _L, _I, _P, _P, _F, _P, _P, _P, _RC_P],
-    "voltrix_launch_spmm_csr_heads": [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _RC_P],
-    "voltrix_launch_gat_score_csr": [_P, _P, _I, _L, _I, _P, _P, _F, _P, _P, _RC_P],
-    "voltrix_launch_gat_score_rowsum_csr": [_P, _P, _P, _I, _L, _I, _P, _P, _P, _F, _P, _P, _P, _RC_P],
-    "voltrix_launch_gatv2_score_csr": [_P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _F, _P, _P, _RC_P],
-    "voltrix_launch_gatv2_rowsum_csr": [_P, _P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _F, _P, _P, _RC_P],
-    "voltrix_launch_attn_aggregate_csr": [_P, _P, _P, _I, _L, _I, _I, _P, _I, _F, _P, _P, _P, _P, _RC_P],
-    "voltrix_launch_attn_aggregate_grad_scores_csr": [_P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _F, _P, _P, _RC_P],
-    "voltrix_launch_attn_aggregate_grad_feat_csr": [_P, _P, _P, _I, _L, _I, _I, _P, _I, _P, _P, _P, _F, _P, _P, _RC_P],
-    "voltrix_launch_dropout_mask": [_L, _I, _U32, _U64, _U64, _P, _P, _RC_P],
-    "voltrix_launch_attn_aggregate_dropout_csr": [_P, _P, _P, _I, _L, _I, _I, _P, _I, _F, _P, _P, _P, _P, _F, _P, _RC_P],
-    "voltrix_launch_attn_aggregate_dropout_grad_scores_csr": [_P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _F, _P, _P, _F, _P,
-                                                              _RC_P],
-    "voltrix_launch_attn_aggregate_dropout_grad_feat_csr": [_P, _P, _P, _I, _L, _I, _I, _P, _I, _P, _P, _P, _F, _P, _P, _F, _P, _RC_P],
-    "voltrix_launch_scatter_values": [_P, _P, _P, _L, _I, _P, _RC_P],
-    "voltrix_launch_scale_rows": [_P, _P, _P, _L, _I, _I, _P, _RC_P],
-}
-_bound_fns = {}
+# ---- the CSR / attention launchers
 
 
-def _bound(name: str):
-    """The library's entry point ``name`` with its argument types set."""
-    fn = _bound_fns.get(name)
-    if fn is None:
-        fn = getattr(lib(), name)
-        fn.argtypes = _ARGTYPES[name]
-        _bound_fns[name] = fn
-    return fn
-
-
+@_timed("spmm_csr_rows")
 def launch_spmm_csr_rows(indptr, indices, num_rows: int, feat, output, stream, xcd_ranges: int = 0, values=None) -> None:
     """``output = csr(ones) @ feat`` -- or ``csr(values) @ feat`` with ``values`` (device float32 [nnz], CSR order) -- with the CSR
     row-gather kernel (device int32 CSR; fp32 / fp16 / bf16 ``feat`` whose rows are a multiple of 16 bytes; fp32 ``output``
@@ -624,19 +548,17 @@ def launch_spmm_csr_rows(indptr, indices, num_rows: int, feat, output, stream, x
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
     assert feat.dim() == 2 and feat.is_contiguous() and output.is_contiguous() and output.dtype == torch.float32
     assert output.shape == (num_rows, feat.shape[1])
-    dtype = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[feat.dtype]
-    rc = ctypes.c_int(-1)
+    dtype = _dtype_code(feat.dtype)
     if values is None:
-        _bound("voltrix_launch_spmm_csr_rows")(indptr.data_ptr(), indices.data_ptr(), num_rows, feat.shape[1], feat.data_ptr(), dtype,
-                                               output.data_ptr(), int(xcd_ranges), stream, rc)
-        check(rc.value, "voltrix_launch_spmm_csr_rows")
+        _checked("voltrix_launch_spmm_csr_rows", indptr.data_ptr(), indices.data_ptr(), num_rows, feat.shape[1], feat.data_ptr(), dtype,
+                 output.data_ptr(), int(xcd_ranges), stream)
         return
     assert values.dtype == torch.float32 and values.is_contiguous() and values.numel() == indices.numel() and values.is_cuda
-    _bound("voltrix_launch_spmm_csr_rows_weighted")(indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), num_rows, feat.shape[1],
-                                                    feat.data_ptr(), dtype, output.data_ptr(), int(xcd_ranges), stream, rc)
-    check(rc.value, "voltrix_launch_spmm_csr_rows_weighted")
+    _checked("voltrix_launch_spmm_csr_rows_weighted", indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), num_rows, feat.shape[1],
+             feat.data_ptr(), dtype, output.data_ptr(), int(xcd_ranges), stream)
 
 
+@_timed("sddmm_csr")
 def launch_sddmm_csr(indptr, indices, num_rows: int, x, y, out, stream) -> None:
     """``out[e] = <x[row_e], y[indices[e]]>`` for every entry of a device int32 CSR (the sampled dense-dense product,
     voltrix/sddmm_kernels.hpp): ``x`` [num_rows, F], ``y`` [*, F], dtype pairs (fp32, fp16 / bf16 / fp32), (fp16, fp16), (bf16, bf16),
@@ -646,18 +568,16 @@ def launch_sddmm_csr(indptr, indices, num_rows: int, x, y, out, stream) -> None:
     assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
     assert x.dim() == 2 and y.dim() == 2 and x.is_contiguous() and y.is_contiguous() and x.shape[0] == num_rows
     assert x.shape[1] == y.shape[1] and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == indices.numel()
-    codes = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_sddmm_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), x.shape[1], x.data_ptr(),
-                                       codes[x.dtype], y.data_ptr(), codes[y.dtype], out.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_sddmm_csr")
+    _checked("voltrix_launch_sddmm_csr", indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), x.shape[1], x.data_ptr(),
+             _dtype_code(x.dtype), y.data_ptr(), _dtype_code(y.dtype), out.data_ptr(), stream)
 
 
 def edge_softmax_workspace_bytes(num_rows: int, nnz: int) -> int:
     """Bytes of device workspace both edge softmax entry points need (a function of ``nnz`` alone; 0 for nnz == 0)."""
-    return int(lib().voltrix_edge_softmax_workspace_bytes(ctypes.c_int(num_rows), ctypes.c_int64(nnz)))
+    return int(lib().voltrix_edge_softmax_workspace_bytes(num_rows, nnz))
 
 
+@_timed("edge_softmax_csr")
 def launch_edge_softmax_csr(indptr, num_rows: int, scores, scale: float, out, workspace, stream) -> None:
     """``out`` = softmax of ``scale * scores`` over every row of a device int32 CSR (voltrix/edge_softmax_kernels.hpp): ``scores`` and
     ``out`` float32 [nnz] in CSR order, ``workspace`` uint8 of ``edge_softmax_workspace_bytes`` bytes; see include/voltrix_capi.h."""
@@ -666,12 +586,11 @@ def launch_edge_softmax_csr(indptr, num_rows: int, scores, scale: float, out, wo
     assert indptr.dtype == torch.int32 and indptr.numel() == num_rows + 1 and indptr.is_contiguous()
     assert scores.dtype == torch.float32 and out.dtype == torch.float32 and scores.is_contiguous() and out.is_contiguous()
     assert out.numel() == scores.numel() and workspace.numel() >= edge_softmax_workspace_bytes(num_rows, scores.numel())
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_edge_softmax_csr")(indptr.data_ptr(), num_rows, scores.numel(), scores.data_ptr(), float(scale), out.data_ptr(),
-                                              workspace.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_edge_softmax_csr")
+    _checked("voltrix_launch_edge_softmax_csr", indptr.data_ptr(), num_rows, scores.numel(), scores.data_ptr(), float(scale),
+             out.data_ptr(), workspace.data_ptr(), stream)
 
 
+@_timed("edge_softmax_backward_csr")
 def launch_edge_softmax_backward_csr(indptr, num_rows: int, alpha, grad_alpha, scale: float, grad_scores, workspace, stream) -> None:
     """``grad_scores = scale * alpha * (grad_alpha - rowsum(alpha * grad_alpha))`` (the edge softmax's backward), all float32 [nnz] in
     CSR order; the forward's workspace size; see include/voltrix_capi.h."""
@@ -681,25 +600,14 @@ def launch_edge_softmax_backward_csr(indptr, num_rows: int, alpha, grad_alpha, s
     for t in (alpha, grad_alpha, grad_scores):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == alpha.numel()
     assert workspace.numel() >= edge_softmax_workspace_bytes(num_rows, alpha.numel())
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_edge_softmax_backward_csr")(indptr.data_ptr(), num_rows, alpha.numel(), alpha.data_ptr(), grad_alpha.data_ptr(),
-                                                       float(scale), grad_scores.data_ptr(), workspace.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_edge_softmax_backward_csr")
+    _checked("voltrix_launch_edge_softmax_backward_csr", indptr.data_ptr(), num_rows, alpha.numel(), alpha.data_ptr(),
+             grad_alpha.data_ptr(), float(scale), grad_scores.data_ptr(), workspace.data_ptr(), stream)
 
 
 # ---- multi-head forms (csrc/capi_heads.hip): node tensors [n, H, D], edge tensors [nnz, H] with the head index fastest
-_CODES = None
 
 
-def _dtype_code(dtype) -> int:
-    import torch
-
-    global _CODES
-    if _CODES is None:
-        _CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-    return _CODES[dtype]
-
-
+@_timed("sddmm_heads_csr")
 def launch_sddmm_heads_csr(indptr, indices, num_rows: int, x, y, out, stream) -> None:
     """``out[e, h] = <x[row_e, h], y[indices[e], h]>`` for every entry of a device int32 CSR (voltrix/sddmm_heads_kernels.hpp): ``x``
     [num_rows, H, D], ``y`` [*, H, D], the dtype pairs of ``launch_sddmm_csr``, D a multiple of 16 bytes of ``y``; ``out`` float32
@@ -710,19 +618,17 @@ def launch_sddmm_heads_csr(indptr, indices, num_rows: int, x, y, out, stream) ->
     assert x.dim() == 3 and y.dim() == 3 and x.is_contiguous() and y.is_contiguous() and x.shape[0] == num_rows
     assert x.shape[1:] == y.shape[1:] and out.dtype == torch.float32 and out.is_contiguous()
     assert out.shape == (indices.numel(), x.shape[1])
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_sddmm_heads_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), x.shape[1], x.shape[2],
-                                             x.data_ptr(), _dtype_code(x.dtype), y.data_ptr(), _dtype_code(y.dtype), out.data_ptr(), stream,
-                                             rc)
-    check(rc.value, "voltrix_launch_sddmm_heads_csr")
+    _checked("voltrix_launch_sddmm_heads_csr", indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), x.shape[1], x.shape[2],
+             x.data_ptr(), _dtype_code(x.dtype), y.data_ptr(), _dtype_code(y.dtype), out.data_ptr(), stream)
 
 
 def edge_softmax_heads_workspace_bytes(num_rows: int, nnz: int, heads: int) -> int:
     """Bytes of device workspace both multi-head edge softmax entry points need (a function of ``nnz`` and ``heads`` alone; with
     ``heads == 1`` the single-head size)."""
-    return int(lib().voltrix_edge_softmax_heads_workspace_bytes(ctypes.c_int(num_rows), ctypes.c_int64(nnz), ctypes.c_int(heads)))
+    return int(lib().voltrix_edge_softmax_heads_workspace_bytes(num_rows, nnz, heads))
 
 
+@_timed("edge_softmax_heads_csr")
 def launch_edge_softmax_heads_csr(indptr, num_rows: int, scores, scale: float, out, workspace, stream) -> None:
     """``out[:, h]`` = softmax of ``scale * scores[:, h]`` over every row of a device int32 CSR, for every head
     (voltrix/edge_softmax_heads_kernels.hpp): ``scores`` and ``out`` float32 [nnz, H], ``workspace`` uint8 of
@@ -734,12 +640,11 @@ def launch_edge_softmax_heads_csr(indptr, num_rows: int, scores, scale: float, o
     assert scores.is_contiguous() and out.is_contiguous() and out.shape == scores.shape
     nnz, heads = scores.shape
     assert workspace.numel() >= edge_softmax_heads_workspace_bytes(num_rows, nnz, heads)
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_edge_softmax_heads_csr")(indptr.data_ptr(), num_rows, nnz, heads, scores.data_ptr(), float(scale),
-                                                    out.data_ptr(), workspace.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_edge_softmax_heads_csr")
+    _checked("voltrix_launch_edge_softmax_heads_csr", indptr.data_ptr(), num_rows, nnz, heads, scores.data_ptr(), float(scale),
+             out.data_ptr(), workspace.data_ptr(), stream)
 
 
+@_timed("edge_softmax_heads_backward_csr")
 def launch_edge_softmax_heads_backward_csr(indptr, num_rows: int, alpha, grad_alpha, scale: float, grad_scores, workspace, stream) -> None:
     """The multi-head edge softmax's backward, all float32 [nnz, H]; the forward's workspace size; see include/voltrix_capi.h."""
     import torch
@@ -749,13 +654,11 @@ def launch_edge_softmax_heads_backward_csr(indptr, num_rows: int, alpha, grad_al
         assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous() and t.shape == alpha.shape
     nnz, heads = alpha.shape
     assert workspace.numel() >= edge_softmax_heads_workspace_bytes(num_rows, nnz, heads)
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_edge_softmax_heads_backward_csr")(indptr.data_ptr(), num_rows, nnz, heads, alpha.data_ptr(),
-                                                             grad_alpha.data_ptr(), float(scale), grad_scores.data_ptr(),
-                                                             workspace.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_edge_softmax_heads_backward_csr")
+    _checked("voltrix_launch_edge_softmax_heads_backward_csr", indptr.data_ptr(), num_rows, nnz, heads, alpha.data_ptr(),
+             grad_alpha.data_ptr(), float(scale), grad_scores.data_ptr(), workspace.data_ptr(), stream)
 
 
+@_timed("spmm_csr_heads")
 def launch_spmm_csr_heads(indptr, indices, values, num_rows: int, feat, output, stream) -> None:
     """``output[r, h] = sum_{e in row r} values[e, h] * feat[indices[e], h]`` (voltrix/spmm_csr_heads_kernels.hpp): device int32 CSR,
     ``values`` float32 [nnz, H], fp32 / fp16 / bf16 ``feat`` [*, H, D] with D a multiple of 16 bytes, fp32 ``output`` [num_rows, H, D];
@@ -766,10 +669,8 @@ def launch_spmm_csr_heads(indptr, indices, values, num_rows: int, feat, output, 
     assert feat.dim() == 3 and feat.is_contiguous() and output.is_contiguous() and output.dtype == torch.float32
     assert output.shape == (num_rows,) + tuple(feat.shape[1:])
     assert values.dtype == torch.float32 and values.is_contiguous() and values.shape == (indices.numel(), feat.shape[1])
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_spmm_csr_heads")(indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), num_rows, feat.shape[1],
-                                            feat.shape[2], feat.data_ptr(), _dtype_code(feat.dtype), output.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_spmm_csr_heads")
+    _checked("voltrix_launch_spmm_csr_heads", indptr.data_ptr(), indices.data_ptr(), values.data_ptr(), num_rows, feat.shape[1],
+             feat.shape[2], feat.data_ptr(), _dtype_code(feat.dtype), output.data_ptr(), stream)
 
 
 # ---- GAT edge scores (csrc/capi_gat_score.hip): node scalars [n, H], edge tensors [nnz, H] with the head index fastest
@@ -777,9 +678,10 @@ def launch_spmm_csr_heads(indptr, indices, values, num_rows: int, feat, output, 
 
 def gat_score_workspace_bytes(num_rows: int, nnz: int, heads: int = 1) -> int:
     """Bytes of device workspace ``launch_gat_score_rowsum_csr`` needs (a function of ``nnz`` and ``heads`` alone; 0 for nnz == 0)."""
-    return int(lib().voltrix_gat_score_workspace_bytes(ctypes.c_int(num_rows), ctypes.c_int64(nnz), ctypes.c_int(heads)))
+    return int(lib().voltrix_gat_score_workspace_bytes(num_rows, nnz, heads))
 
 
+@_timed("gat_score_csr")
 def launch_gat_score_csr(indptr, indices, num_rows: int, el, er, slope: float, out, stream) -> None:
     """``out[e, h] = leaky_relu(el[row_e, h] + er[indices[e], h], slope)`` for every entry of a device int32 CSR
     (voltrix/gat_score_kernels.hpp): ``el`` float32 [num_rows, H], ``er`` float32 [*, H], ``out`` float32 [nnz, H]; see
@@ -791,12 +693,11 @@ def launch_gat_score_csr(indptr, indices, num_rows: int, el, er, slope: float, o
     for t in (el, er, out):
         assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous() and t.shape[1] == out.shape[1]
     assert el.shape[0] == num_rows and out.shape[0] == indices.numel()
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_gat_score_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), out.shape[1], el.data_ptr(),
-                                           er.data_ptr(), float(slope), out.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_gat_score_csr")
+    _checked("voltrix_launch_gat_score_csr", indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), out.shape[1],
+             el.data_ptr(), er.data_ptr(), float(slope), out.data_ptr(), stream)
 
 
+@_timed("gat_score_rowsum_csr")
 def launch_gat_score_rowsum_csr(indptr, indices, order, num_rows: int, a, b, grad, slope: float, out, workspace, stream) -> None:
     """``out[r, h] = sum_{e in row r} gate(a[r, h] + b[indices[e], h]) grad[order[e] if order is not None else e, h]`` with ``gate(z) =
     1 if z > 0 else slope``: ``a`` float32 [num_rows, H], ``b`` float32 [*, H], ``grad`` float32 [nnz, H], ``order`` None or int32
@@ -813,16 +714,14 @@ def launch_gat_score_rowsum_csr(indptr, indices, order, num_rows: int, a, b, gra
     if order is not None:
         assert order.dtype == torch.int32 and order.is_contiguous() and order.numel() == nnz
     assert workspace.numel() >= gat_score_workspace_bytes(num_rows, nnz, heads)
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_gat_score_rowsum_csr")(indptr.data_ptr(), indices.data_ptr(), order.data_ptr() if order is not None else None,
-                                                  num_rows, nnz, heads, a.data_ptr(), b.data_ptr(), grad.data_ptr(), float(slope),
-                                                  out.data_ptr(), workspace.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_gat_score_rowsum_csr")
+    _checked("voltrix_launch_gat_score_rowsum_csr", indptr.data_ptr(), indices.data_ptr(), _opt(order), num_rows, nnz, heads,
+             a.data_ptr(), b.data_ptr(), grad.data_ptr(), float(slope), out.data_ptr(), workspace.data_ptr(), stream)
 
 
 # ---- GATv2 edge scores (csrc/capi_gatv2_score.hip): node tensors [n, H, D], a [H, D], edge tensors [nnz, H] with the head index fastest
 
 
+@_timed("gatv2_score_csr")
 def launch_gatv2_score_csr(indptr, indices, num_rows: int, xl, xr, a, slope: float, out, stream) -> None:
     """``out[e, h] = sum_d a[h, d] * leaky_relu(xl[row_e, h, d] + xr[indices[e], h, d], slope)`` for every entry of a device int32 CSR
     (voltrix/gatv2_score_kernels.hpp): ``xl`` [num_rows, H, D] and ``xr`` [*, H, D] of one type (fp32 / fp16 / bf16), D a multiple of
@@ -835,13 +734,11 @@ def launch_gatv2_score_csr(indptr, indices, num_rows: int, xl, xr, a, slope: flo
     assert xl.shape[1:] == xr.shape[1:] and xl.dtype == xr.dtype
     assert a.dtype == torch.float32 and a.is_contiguous() and a.shape == xl.shape[1:]
     assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (indices.numel(), xl.shape[1])
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_gatv2_score_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), xl.shape[1], xl.shape[2],
-                                             xl.data_ptr(), xr.data_ptr(), _dtype_code(xl.dtype), a.data_ptr(), float(slope),
-                                             out.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_gatv2_score_csr")
+    _checked("voltrix_launch_gatv2_score_csr", indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), xl.shape[1], xl.shape[2],
+             xl.data_ptr(), xr.data_ptr(), _dtype_code(xl.dtype), a.data_ptr(), float(slope), out.data_ptr(), stream)
 
 
+@_timed("gatv2_rowsum_csr")
 def launch_gatv2_rowsum_csr(indptr, indices, order, num_rows: int, p, q, grad, slope: float, out, stream) -> None:
     """``out[r, h, d] = sum_{e in row r} gate(p[r, h, d] + q[indices[e], h, d]) grad[order[e] if order is not None else e, h]`` with
     ``gate(z) = 1 if z > 0 else slope``: ``p`` [num_rows, H, D] and ``q`` [*, H, D] of one type, ``grad`` float32 [nnz, H], ``order``
@@ -857,11 +754,8 @@ def launch_gatv2_rowsum_csr(indptr, indices, order, num_rows: int, p, q, grad, s
     assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == p.shape
     if order is not None:
         assert order.dtype == torch.int32 and order.is_contiguous() and order.numel() == nnz
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_gatv2_rowsum_csr")(indptr.data_ptr(), indices.data_ptr(), order.data_ptr() if order is not None else None,
-                                              num_rows, nnz, heads, p.shape[2], p.data_ptr(), q.data_ptr(), _dtype_code(p.dtype),
-                                              grad.data_ptr(), float(slope), out.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_gatv2_rowsum_csr")
+    _checked("voltrix_launch_gatv2_rowsum_csr", indptr.data_ptr(), indices.data_ptr(), _opt(order), num_rows, nnz, heads, p.shape[2],
+             p.data_ptr(), q.data_ptr(), _dtype_code(p.dtype), grad.data_ptr(), float(slope), out.data_ptr(), stream)
 
 
 # ---- edge softmax + aggregation in one launch (csrc/capi_attn_aggregate.hip): scores [nnz, H], feat [n, H, D], row statistics [n, H]
@@ -880,11 +774,10 @@ def launch_dropout_mask(nnz: int, heads: int, threshold: int, seed: int, offset:
     see include/voltrix_capi.h."""
     _check_keep_mask(mask, nnz, heads)
     assert 0 <= threshold < 2 ** 32 and 0 <= seed < 2 ** 64 and 0 <= offset < 2 ** 64
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_dropout_mask")(nnz, heads, threshold, seed, offset, mask.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_dropout_mask")
+    _checked("voltrix_launch_dropout_mask", nnz, heads, threshold, seed, offset, mask.data_ptr(), stream)
 
 
+@_timed("attn_aggregate_csr")
 def launch_attn_aggregate_csr(indptr, indices, scores, num_rows: int, feat, scale: float, out, m, l, stream, mask=None,
                               keep_scale: float = 1.0) -> None:
     """``out[r, h] = sum_{e in row r} softmax(scale * scores)[e, h] * feat[indices[e], h]`` with the row statistics ``m``, ``l``
@@ -902,21 +795,16 @@ def launch_attn_aggregate_csr(indptr, indices, scores, num_rows: int, feat, scal
     assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.shape == (indices.numel(), heads)
     for t in (m, l):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (num_rows, heads)
-    rc = ctypes.c_int(-1)
+    args = (indptr.data_ptr(), indices.data_ptr(), scores.data_ptr(), num_rows, indices.numel(), heads, feat.shape[2], feat.data_ptr(),
+            _dtype_code(feat.dtype), float(scale), out.data_ptr(), m.data_ptr(), l.data_ptr())
     if mask is not None:
         _check_keep_mask(mask, indices.numel(), heads)
-        _bound("voltrix_launch_attn_aggregate_dropout_csr")(indptr.data_ptr(), indices.data_ptr(), scores.data_ptr(), num_rows,
-                                                            indices.numel(), heads, feat.shape[2], feat.data_ptr(),
-                                                            _dtype_code(feat.dtype), float(scale), out.data_ptr(), m.data_ptr(),
-                                                            l.data_ptr(), mask.data_ptr(), float(keep_scale), stream, rc)
-        check(rc.value, "voltrix_launch_attn_aggregate_dropout_csr")
+        _checked("voltrix_launch_attn_aggregate_dropout_csr", *args, mask.data_ptr(), float(keep_scale), stream)
         return
-    _bound("voltrix_launch_attn_aggregate_csr")(indptr.data_ptr(), indices.data_ptr(), scores.data_ptr(), num_rows, indices.numel(), heads,
-                                                feat.shape[2], feat.data_ptr(), _dtype_code(feat.dtype), float(scale), out.data_ptr(),
-                                                m.data_ptr(), l.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_attn_aggregate_csr")
+    _checked("voltrix_launch_attn_aggregate_csr", *args, stream)
 
 
+@_timed("attn_aggregate_grad_scores_csr")
 def launch_attn_aggregate_grad_scores_csr(indptr, indices, num_rows: int, grad_out, feat, scores, m, l, delta, scale: float, out,
                                           stream, mask=None, keep_scale: float = 1.0) -> None:
     """``out[e, h] = scale * alpha[e, h] * (<grad_out[row_e, h], feat[indices[e], h]> - delta[row_e, h])`` with ``alpha`` recomputed from
@@ -934,23 +822,16 @@ def launch_attn_aggregate_grad_scores_csr(indptr, indices, num_rows: int, grad_o
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (nnz, heads)
     for t in (m, l, delta):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (num_rows, heads)
-    rc = ctypes.c_int(-1)
+    args = (indptr.data_ptr(), indices.data_ptr(), num_rows, nnz, heads, feat.shape[2], grad_out.data_ptr(), feat.data_ptr(),
+            _dtype_code(feat.dtype), scores.data_ptr(), m.data_ptr(), l.data_ptr(), delta.data_ptr(), float(scale), out.data_ptr())
     if mask is not None:
         _check_keep_mask(mask, nnz, heads)
-        _bound("voltrix_launch_attn_aggregate_dropout_grad_scores_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, nnz, heads,
-                                                                        feat.shape[2], grad_out.data_ptr(), feat.data_ptr(),
-                                                                        _dtype_code(feat.dtype), scores.data_ptr(), m.data_ptr(),
-                                                                        l.data_ptr(), delta.data_ptr(), float(scale), out.data_ptr(),
-                                                                        mask.data_ptr(), float(keep_scale), stream, rc)
-        check(rc.value, "voltrix_launch_attn_aggregate_dropout_grad_scores_csr")
+        _checked("voltrix_launch_attn_aggregate_dropout_grad_scores_csr", *args, mask.data_ptr(), float(keep_scale), stream)
         return
-    _bound("voltrix_launch_attn_aggregate_grad_scores_csr")(indptr.data_ptr(), indices.data_ptr(), num_rows, nnz, heads, feat.shape[2],
-                                                            grad_out.data_ptr(), feat.data_ptr(), _dtype_code(feat.dtype),
-                                                            scores.data_ptr(), m.data_ptr(), l.data_ptr(), delta.data_ptr(), float(scale),
-                                                            out.data_ptr(), stream, rc)
-    check(rc.value, "voltrix_launch_attn_aggregate_grad_scores_csr")
+    _checked("voltrix_launch_attn_aggregate_grad_scores_csr", *args, stream)
 
 
+@_timed("attn_aggregate_grad_feat_csr")
 def launch_attn_aggregate_grad_feat_csr(t_indptr, t_indices, order, num_cols: int, grad_out, scores, m, l, scale: float, out,
                                         stream, mask=None, keep_scale: float = 1.0) -> None:
     """``out[c, h] = sum_{e in row c of the transposed CSR} alpha[order[e], h] * grad_out[t_indices[e], h]`` with ``alpha`` recomputed
@@ -969,21 +850,13 @@ def launch_attn_aggregate_grad_feat_csr(t_indptr, t_indices, order, num_cols: in
     assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.shape == (nnz, heads)
     for t in (m, l):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (grad_out.shape[0], heads)
-    rc = ctypes.c_int(-1)
+    args = (t_indptr.data_ptr(), t_indices.data_ptr(), order.data_ptr(), num_cols, nnz, heads, grad_out.shape[2], grad_out.data_ptr(),
+            _dtype_code(grad_out.dtype), scores.data_ptr(), m.data_ptr(), l.data_ptr(), float(scale), out.data_ptr())
     if mask is not None:
         _check_keep_mask(mask, nnz, heads)
-        _bound("voltrix_launch_attn_aggregate_dropout_grad_feat_csr")(t_indptr.data_ptr(), t_indices.data_ptr(), order.data_ptr(),
-                                                                      num_cols, nnz, heads, grad_out.shape[2], grad_out.data_ptr(),
-                                                                      _dtype_code(grad_out.dtype), scores.data_ptr(), m.data_ptr(),
-                                                                      l.data_ptr(), float(scale), out.data_ptr(), mask.data_ptr(),
-                                                                      float(keep_scale), stream, rc)
-        check(rc.value, "voltrix_launch_attn_aggregate_dropout_grad_feat_csr")
+        _checked("voltrix_launch_attn_aggregate_dropout_grad_feat_csr", *args, mask.data_ptr(), float(keep_scale), stream)
         return
-    _bound("voltrix_launch_attn_aggregate_grad_feat_csr")(t_indptr.data_ptr(), t_indices.data_ptr(), order.data_ptr(), num_cols, nnz, heads,
-                                                          grad_out.shape[2], grad_out.data_ptr(), _dtype_code(grad_out.dtype),
-                                                          scores.data_ptr(), m.data_ptr(), l.data_ptr(), float(scale), out.data_ptr(),
-                                                          stream, rc)
-    check(rc.value, "voltrix_launch_attn_aggregate_grad_feat_csr")
+    _checked("voltrix_launch_attn_aggregate_grad_feat_csr", *args, stream)
 
 
 def launch_scatter_values(values, slots, plane, stream) -> None:
@@ -993,12 +866,11 @@ def launch_scatter_values(values, slots, plane, stream) -> None:
 
     assert values.dtype == torch.float32 and slots.dtype == torch.int64 and values.numel() == slots.numel()
     assert values.is_contiguous() and slots.is_contiguous() and plane.is_contiguous() and values.is_cuda and plane.is_cuda
-    dtype = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[plane.dtype]
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_scatter_values")(values.data_ptr(), slots.data_ptr(), plane.data_ptr(), values.numel(), dtype, stream, rc)
-    check(rc.value, "voltrix_launch_scatter_values")
+    _checked("voltrix_launch_scatter_values", values.data_ptr(), slots.data_ptr(), plane.data_ptr(), values.numel(),
+             _dtype_code(plane.dtype), stream)
 
 
+@_timed("scale_rows")
 def launch_scale_rows(src, scale, dst, stream) -> None:
     """dst[i, :] = src[i, :] * scale[i] (``scale`` float32 [rows]; fp32 / fp16 / bf16 rows of a 16-byte multiple; in place
     allowed); see include/voltrix_capi.h."""
@@ -1006,59 +878,8 @@ def launch_scale_rows(src, scale, dst, stream) -> None:
 
     assert src.dim() == 2 and src.is_contiguous() and dst.is_contiguous() and dst.shape == src.shape and dst.dtype == src.dtype
     assert scale.dtype == torch.float32 and scale.numel() == src.shape[0] and scale.is_contiguous()
-    dtype = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[src.dtype]
-    rc = ctypes.c_int(-1)
-    _bound("voltrix_launch_scale_rows")(src.data_ptr(), scale.data_ptr(), dst.data_ptr(), src.shape[0], src.shape[1], dtype, stream, rc)
-    check(rc.value, "voltrix_launch_scale_rows")
-
-
-# ---- kernel-isolated timing hook (utils.KernelTimer / bench_kineto): every launch wrapper above that takes a stream is
-# ---- bracketed by an event pair on that stream while a timer is active; free otherwise.
-def _timed(fn, name, stream_index=None, stream_kw="stream"):
-    import functools
-
-    @functools.wraps(fn)
-    def wrapper(*args, **kwargs):
-        from .utils import KernelTimer
-
-        if KernelTimer.active is None:
-            return fn(*args, **kwargs)
-        stream = kwargs.get(stream_kw)
-        if stream is None and stream_index is not None and len(args) > stream_index:
-            stream = args[stream_index]
-        with KernelTimer.active.bracket(name, stream):
-            return fn(*args, **kwargs)
-
-    return wrapper
-
-
-launch_spmm = _timed(launch_spmm, "spmm", 10)
-launch_spmm_sched = _timed(launch_spmm_sched, "spmm", 9)
-launch_spmm_panel = _timed(launch_spmm_panel, "spmm_panel", 8)
-launch_spmm_fused = _timed(launch_spmm_fused, "spmm_fused", 8)
-launch_combine_partials = _timed(launch_combine_partials, "combine_partials", 6)
-launch_cast_f32_f16_scaled = _timed(launch_cast_f32_f16_scaled, "cast_f32_f16_scaled", 3)
-launch_cast_f32_f16 = _timed(launch_cast_f32_f16, "cast_f32_f16", 2)
-launch_scale_rows = _timed(launch_scale_rows, "scale_rows", 3)
-launch_spmm_csr_rows = _timed(launch_spmm_csr_rows, "spmm_csr_rows", 5)
-launch_sddmm_csr = _timed(launch_sddmm_csr, "sddmm_csr", 6)
-launch_edge_softmax_csr = _timed(launch_edge_softmax_csr, "edge_softmax_csr", 6)
-launch_edge_softmax_backward_csr = _timed(launch_edge_softmax_backward_csr, "edge_softmax_backward_csr", 7)
-launch_sddmm_heads_csr = _timed(launch_sddmm_heads_csr, "sddmm_heads_csr", 6)
-launch_edge_softmax_heads_csr = _timed(launch_edge_softmax_heads_csr, "edge_softmax_heads_csr", 6)
-launch_edge_softmax_heads_backward_csr = _timed(launch_edge_softmax_heads_backward_csr, "edge_softmax_heads_backward_csr", 7)
-launch_spmm_csr_heads = _timed(launch_spmm_csr_heads, "spmm_csr_heads", 6)
-launch_gat_score_csr = _timed(launch_gat_score_csr, "gat_score_csr", 7)
-launch_gat_score_rowsum_csr = _timed(launch_gat_score_rowsum_csr, "gat_score_rowsum_csr", 10)
-launch_gatv2_score_csr = _timed(launch_gatv2_score_csr, "gatv2_score_csr", 8)
-launch_gatv2_rowsum_csr = _timed(launch_gatv2_rowsum_csr, "gatv2_rowsum_csr", 9)
-launch_attn_aggregate_csr = _timed(launch_attn_aggregate_csr, "attn_aggregate_csr", 9)
-launch_attn_aggregate_grad_scores_csr = _timed(launch_attn_aggregate_grad_scores_csr, "attn_aggregate_grad_scores_csr", 11)
-launch_attn_aggregate_grad_feat_csr = _timed(launch_attn_aggregate_grad_feat_csr, "attn_aggregate_grad_feat_csr", 10)
-launch_spmm_f32_as_f16 = _timed(launch_spmm_f32_as_f16, "spmm_f32_as_f16", 9)
-launch_window_order = _timed(launch_window_order, "window_order", 3)
-launch_csr_window_count = _timed(launch_csr_window_count, "csr_window_count", 8)
-launch_csr_fill = _timed(launch_csr_fill, "csr_fill", 8)
+    _checked("voltrix_launch_scale_rows", src.data_ptr(), scale.data_ptr(), dst.data_ptr(), src.shape[0], src.shape[1],
+             _dtype_code(src.dtype), stream)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1069,17 +890,13 @@ def csr_transpose(indptr, indices, num_rows: int, num_cols: int, stream=None):
     import torch
 
     dev = indptr.device
-    stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    stream = _stream_of(stream)
     nnz = int(indices.numel())
-    ws = torch.empty(max(16, int(lib().voltrix_csr_transpose_workspace_bytes(ctypes.c_int64(nnz)))), dtype=torch.uint8,
-                     device=dev)
+    ws = torch.empty(max(16, int(lib().voltrix_csr_transpose_workspace_bytes(nnz))), dtype=torch.uint8, device=dev)
     t_indptr = torch.empty(num_cols + 1, dtype=torch.int32, device=dev)
     t_indices = torch.empty(nnz, dtype=torch.int32, device=dev)
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_csr_transpose(_ptr(indptr), _ptr(indices), ctypes.c_int(num_rows), ctypes.c_int(num_cols),
-                                       ctypes.c_int64(nnz), _ptr(ws), _ptr(t_indptr), _ptr(t_indices),
-                                       ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_csr_transpose")
+    _checked("voltrix_launch_csr_transpose", indptr.data_ptr(), indices.data_ptr(), num_rows, num_cols, nnz, ws.data_ptr(),
+             t_indptr.data_ptr(), t_indices.data_ptr(), stream)
     return t_indptr, t_indices
 
 
@@ -1090,11 +907,7 @@ def chol_inv_transposed(gram, eps: float = 1e-10, stream=None):
     k = gram.shape[0]
     assert gram.is_cuda and gram.dtype == torch.float32 and gram.shape == (k, k) and gram.is_contiguous()
     out = torch.empty_like(gram)
-    stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    rc = ctypes.c_int(-1)
-    lib().voltrix_launch_chol_inv_transposed(_ptr(gram), ctypes.c_int(k), ctypes.c_double(eps), _ptr(out),
-                                             ctypes.c_void_p(stream), ctypes.byref(rc))
-    check(rc.value, "voltrix_launch_chol_inv_transposed")
+    _checked("voltrix_launch_chol_inv_transposed", gram.data_ptr(), k, eps, out.data_ptr(), _stream_of(stream))
     return out
 
 
@@ -1115,25 +928,17 @@ class CmSearch:
         self.syncs = 0
 
     def _graph_args(self):
-        a, b, c, d = self.graph
-        return (_ptr(a), _ptr(b), _ptr(c), _ptr(d), ctypes.c_int(self.n), ctypes.c_int(self.t_rows))
+        return (*(t.data_ptr() for t in self.graph), self.n, self.t_rows)
 
     def levels(self, start: int, wide_levels: int = 4, stream=None):
         """Breadth-first levels of ``start``'s component: returns ``(nodes, levels)``; ``queue[:nodes]`` holds the component
         level by level, ``level_off[:levels + 1]`` the offsets.  One host read per `wide_levels` whole-chip levels (a graph
         whose frontiers stay narrow is walked by one launch)."""
-        import torch
-
-        stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        rc = ctypes.c_int(-1)
-        lib().voltrix_launch_bfs_seed(ctypes.c_int(int(start)), ctypes.c_int(self.n), _ptr(self.level), _ptr(self.queue),
-                                      _ptr(self.ctrl), _ptr(self.level_off), ctypes.c_void_p(stream), ctypes.byref(rc))
-        check(rc.value, "voltrix_launch_bfs_seed")
+        stream = _stream_of(stream)
+        state = (self.level.data_ptr(), self.queue.data_ptr(), self.ctrl.data_ptr(), self.level_off.data_ptr())
+        _checked("voltrix_launch_bfs_seed", int(start), self.n, *state, stream)
         while True:
-            lib().voltrix_launch_bfs_levels(*self._graph_args(), _ptr(self.level), _ptr(self.queue), _ptr(self.ctrl),
-                                            _ptr(self.level_off), ctypes.c_int(wide_levels), ctypes.c_void_p(stream),
-                                            ctypes.byref(rc))
-            check(rc.value, "voltrix_launch_bfs_levels")
+            _checked("voltrix_launch_bfs_levels", *self._graph_args(), *state, wide_levels, stream)
             ctrl = self.ctrl.tolist()       # the sync
             self.syncs += 1
             if ctrl[4]:
@@ -1143,17 +948,13 @@ class CmSearch:
         """Cuthill-McKee order inside the levels of the component in ``queue`` (in place) and ``rank`` = base + position."""
         import torch
 
-        stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        stream = _stream_of(stream)
         offsets = self.level_off[:levels + 1].cpu()          # the sync
         self.syncs += 1
         sizes = (offsets[1:] - offsets[:-1])
         big = int(sizes[sizes > 1024].max()) if bool((sizes > 1024).any()) else 0
-        ws = torch.empty(max(16, int(lib().voltrix_cm_rank_workspace_bytes(ctypes.c_int64(big)))), dtype=torch.uint8,
-                         device=self.level.device)
+        ws = torch.empty(max(16, int(lib().voltrix_cm_rank_workspace_bytes(big))), dtype=torch.uint8, device=self.level.device)
         host = (ctypes.c_int * (levels + 1))(*offsets.tolist())
-        rc = ctypes.c_int(-1)
-        lib().voltrix_launch_cm_rank(*self._graph_args(), _ptr(self.level), _ptr(self.rank), _ptr(self.tie), _ptr(self.queue),
-                                     _ptr(self.level_off), host, ctypes.c_int(levels), ctypes.c_int(int(base)), _ptr(ws),
-                                     ctypes.c_void_p(stream), ctypes.byref(rc))
-        check(rc.value, "voltrix_launch_cm_rank")
+        _checked("voltrix_launch_cm_rank", *self._graph_args(), self.level.data_ptr(), self.rank.data_ptr(), self.tie.data_ptr(),
+                 self.queue.data_ptr(), self.level_off.data_ptr(), host, levels, int(base), ws.data_ptr(), stream)
         return offsets
