@@ -683,6 +683,44 @@ void voltrix_launch_attn_aggregate_dropout_grad_feat_csr(void* t_indptr, void* t
                                                          void* l, float scale, void* grad_feat, void* mask, float keep_scale,
                                                          void* stream, int* return_code);
 
+/* Max / min / mean neighbour aggregation on a DEVICE CSR (spmm_csr_reduce_kernels.hpp): op 0 max, 1 min, 2 mean.
+ *   output[r, f] = max | min | mean over the entries e of row r of input[indices[e], f]
+ *   arg[r, f]    = the CSR ENTRY id e of the winner (max / min; not its column: with duplicate (row, col) entries a column id would match
+ *                  twice in the backward)
+ * input = device [*, embedding_dim] of dtype 0 fp32 / 1 fp16 / 2 bfloat16, read as it is; output = device float[num_rows, embedding_dim];
+ * arg = device int32[num_rows, embedding_dim] or NULL (then it is neither computed nor stored; it must be NULL for mean).  Every element
+ * of output and arg is written.  Selection: entry e with value v replaces the winner when v > best (min: v < best) or v is the row's
+ * first NaN -- strict, so the first entry in CSR order wins ties, +0 and -0 tie, a NaN among a row's entries gives NaN with arg at the
+ * first NaN (torch.amax), a row whose entries are all -inf gives -inf with arg at its first entry.  A selection does not round: output
+ * is the winning element converted to fp32, whatever the dtype.  A row without entries gives 0 and arg = -1.  mean: fp32 additions in
+ * CSR order and one fp32 division by the row's entry count, |output - ref| <= (deg + 1) 2^-23 sum_e |input_e| / deg; duplicate entries
+ * count twice; a row without entries gives 0.  One launch, a row per lane group (a hub row serialises its wave, as in
+ * voltrix_launch_spmm_csr_heads), 16 bytes of every gathered row per lane, no workspace, no float atomics, no host synchronisation,
+ * the same bits on every call; element offsets are 64-bit (num_rows * embedding_dim may pass 2^31).
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: negative sizes, an unknown dtype or op, a non-NULL arg with mean,
+ * embedding_dim not a multiple of 16 bytes of input (8 for 16-bit, 4 for fp32), a null or misaligned pointer; VOLTRIX_OK without a
+ * launch for num_rows == 0 or embedding_dim == 0.  On a pattern without entries every row is filled (0, arg = -1) and indices and input
+ * are not read (they must still be valid pointers: the entry count is the device's indptr[num_rows]).  Nothing is checked on the device.
+ * Alignment: indptr, indices 4 bytes; input, output, arg 16 bytes (16 bytes per lane).  No reference counterpart. */
+void voltrix_launch_spmm_csr_reduce(void* indptr, void* indices, int num_rows, int embedding_dim, void* input, int dtype, int op,
+                                    void* output, void* arg, void* stream, int* return_code);
+
+/* The backward of max / min, on the TRANSPOSED CSR (voltrix_launch_csr_transpose; num_cols rows):
+ *   output[c, f] = sum over the entries e of row c of the transpose with arg[t_indices[e], f] == t_order[e] of grad_out[t_indices[e], f]
+ * num_entries = the pattern's entry count nnz; t_order = device int32[nnz], the entry of the CSR that entry e of the transpose is; grad_out
+ * = device float[*, embedding_dim]; arg =
+ * the forward's device int32[*, embedding_dim] (only compared, never used as an index); output = device float[num_cols, embedding_dim],
+ * every row written, columns without entries zero.  A gather: the gradient of an element goes to its one winner, fp32 additions in the
+ * transposed CSR's order (|output - ref| <= k 2^-23 sum |terms| for k terms), no float atomics, the same bits on every call; a row of
+ * grad_out is loaded only where one of a lane's four components matched.  One launch, a column per lane group and 4 features per lane (a
+ * hub column serialises its wave), no workspace, no host synchronisation, 64-bit element offsets.  The backward of mean needs no entry
+ * point: voltrix_launch_spmm_csr_rows on the transposed CSR applied to grad_out / deg.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: negative sizes, nnz > INT_MAX, embedding_dim not a multiple of 4, a null or
+ * misaligned pointer; VOLTRIX_OK without a launch for num_cols == 0 or embedding_dim == 0; with nnz == 0 output is zero-filled and
+ * nothing but t_indptr is read.  Alignment: t_indptr, t_indices, t_order 4 bytes; grad_out, arg, output 16 bytes. */
+void voltrix_launch_spmm_csr_reduce_backward(void* t_indptr, void* t_indices, void* t_order, int num_cols, int64_t num_entries, int embedding_dim,
+                                             void* grad_out, void* arg, void* output, void* stream, int* return_code);
+
 /* Rows of a dense row-major matrix times a per-row factor: dst[i, :] = T(float(src[i, :]) * scale[i]); dst may be src.
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,

@@ -20,6 +20,7 @@ from .edge_softmax import edge_softmax
 from .gat_score import gat_score
 from .gatv2_score import gatv2_score
 from .attn_aggregate import attn_aggregate
+from .spmm_reduce import spmm_reduce
 from .dropout import apply_dropout_mask, dropout_mask
 from .graphed import GraphedSpMM
 from . import autograd, hybrid, jit, sidecar, utils

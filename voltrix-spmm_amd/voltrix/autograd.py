@@ -438,6 +438,56 @@ class AttnAggregate(_PatternOp):
         return _AttnAggregateFunction.apply(feat, scores, self, float(scale), mask, keep_scale)
 
 
+class _SpMMReduceFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, op):
+        from .spmm_reduce import row_degrees, spmm_reduce
+
+        ctx.op, ctx.in_dtype = op, feat.dtype
+        if op.reduce == "mean":
+            ctx.save_for_backward(row_degrees(op.indptr))       # nothing but the degrees
+            return spmm_reduce(op.indptr, op.indices, feat, op.num_rows, "mean")
+        out, arg = spmm_reduce(op.indptr, op.indices, feat, op.num_rows, op.reduce, return_arg=True)
+        ctx.save_for_backward(arg)                              # the winners' entry ids: never feat
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .spmm_reduce import spmm_mean_backward, spmm_reduce_backward
+
+        op = ctx.op
+        (saved,) = ctx.saved_tensors
+        if op.reduce == "mean":
+            grad = spmm_mean_backward(op.t_indptr, op.t_indices, grad_out, saved, op.num_cols)
+        else:
+            grad = spmm_reduce_backward(op.t_indptr, op.t_indices, op.t_order, grad_out, saved, op.num_cols)
+        return grad.to(ctx.in_dtype), None
+
+
+class SpMMReduce(_PatternOp):
+    """``out[r] = max | min | mean over the entries e of row r of feat[col_e]`` per element on a CSR pattern [num_rows, num_cols]
+    (``num_cols`` defaults to ``num_rows``), differentiable in ``feat`` [num_cols, ...]: ``SpMMReduce(indptr, indices, n, reduce="max")(feat)``
+    -- the aggregator of max-pool GraphSAGE, PNA and GIN-max (``voltrix.spmm_reduce``).  Built once per pattern like the attention
+    operators: the device CSR, its transpose and the transposed edge order, or ``SpMMReduce(pattern, reduce=...)`` on a ``CsrPattern``
+    shared with them.  max / min save the winners' entry ids ``arg`` (int32, the shape of ``out``) and not ``feat``; the gradient of an
+    element goes to its one winner (the first in CSR order on a tie) by a gather on the transposed CSR.  mean saves nothing but the
+    degrees; its gradient is the CSR row-gather sum on the transposed CSR applied to ``dC / deg``.  No index op, no float atomics, the
+    same bits on every call; ``out`` is float32 and the gradient comes back in ``feat``'s dtype."""
+
+    def __init__(self, indptr, indices: torch.Tensor = None, num_rows: int = None, num_cols: int = None, transposed=None,
+                 reduce: str = "max"):
+        from .spmm_reduce import REDUCTIONS
+
+        if reduce not in REDUCTIONS:
+            raise ValueError(f"SpMMReduce: reduce must be one of {REDUCTIONS}, got {reduce!r}")
+        super().__init__(indptr, indices, num_rows, num_cols, transposed)
+        self.reduce = reduce
+
+    def __call__(self, feat: torch.Tensor) -> torch.Tensor:
+        assert feat.dim() >= 2 and feat.shape[0] == self.num_cols, (tuple(feat.shape), self.num_cols)
+        return _SpMMReduceFunction.apply(feat, self)
+
+
 class SpMM:
     """``C = A @ B`` with a gradient for ``B``.  ``A``: binary CSR [num_rows, num_cols] (``num_cols`` defaults to
     ``num_rows``), or, with ``values`` (round 6), the weighted matrix ``csr(values)``.  Builds two reference-format handles on the current device (A and A^T); both go through

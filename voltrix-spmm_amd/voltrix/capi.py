@@ -98,6 +98,8 @@ SIGNATURES = {
     "voltrix_launch_attn_aggregate_dropout_csr": (None, [_P, _P, _P, _I, _L, _I, _I, _P, _I, _F, _P, _P, _P, _P, _F, _P, _RC_P]),
     "voltrix_launch_attn_aggregate_dropout_grad_scores_csr": (None, [_P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P, _F, _P, _P, _F, _P, _RC_P]),
     "voltrix_launch_attn_aggregate_dropout_grad_feat_csr": (None, [_P, _P, _P, _I, _L, _I, _I, _P, _I, _P, _P, _P, _F, _P, _P, _F, _P, _RC_P]),
+    "voltrix_launch_spmm_csr_reduce": (None, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_csr_reduce_backward": (None, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _RC_P]),
     "voltrix_csr_preprocess_workspace_bytes": (_L, [_I, _I, _L, _I]),
     "voltrix_launch_csr_window_count": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
     "voltrix_launch_csr_fill": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
@@ -857,6 +859,43 @@ def launch_attn_aggregate_grad_feat_csr(t_indptr, t_indices, order, num_cols: in
         _checked("voltrix_launch_attn_aggregate_dropout_grad_feat_csr", *args, mask.data_ptr(), float(keep_scale), stream)
         return
     _checked("voltrix_launch_attn_aggregate_grad_feat_csr", *args, stream)
+
+
+# ---- max / min / mean aggregation (csrc/capi_spmm_reduce.hip)
+
+REDUCE_OPS = {"max": 0, "min": 1, "mean": 2}   # `op` of voltrix_launch_spmm_csr_reduce
+
+
+def launch_spmm_csr_reduce(indptr, indices, num_rows: int, feat, op: str, output, arg, stream) -> None:
+    """``output[r] = max | min | mean`` over the entries of row ``r`` of ``feat[indices[e]]`` (voltrix/spmm_csr_reduce_kernels.hpp): device
+    int32 CSR, fp32 / fp16 / bf16 ``feat`` [*, F] whose rows are a multiple of 16 bytes, fp32 ``output`` [num_rows, F], ``arg`` int32
+    [num_rows, F] (the CSR entry id of the winner; max / min) or None; see include/voltrix_capi.h."""
+    import torch
+
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    assert feat.dim() == 2 and feat.is_contiguous() and output.is_contiguous() and output.dtype == torch.float32
+    assert output.shape == (num_rows, feat.shape[1])
+    assert arg is None or (arg.dtype == torch.int32 and arg.is_contiguous() and arg.shape == output.shape)
+    _checked("voltrix_launch_spmm_csr_reduce", indptr.data_ptr(), indices.data_ptr(), num_rows, feat.shape[1], feat.data_ptr(),
+             _dtype_code(feat.dtype), REDUCE_OPS[op], output.data_ptr(), _opt(arg), stream)
+
+
+def launch_spmm_csr_reduce_backward(t_indptr, t_indices, t_order, num_cols: int, grad_out, arg, output, stream) -> None:
+    """``output[c, f] = sum_{e in row c of the transposed CSR, arg[t_indices[e], f] == t_order[e]} grad_out[t_indices[e], f]``: int32
+    ``t_order`` [nnz], fp32 ``grad_out`` and int32 ``arg`` [num_rows, F] with F a multiple of 4, fp32 ``output`` [num_cols, F]; see
+    include/voltrix_capi.h."""
+    import torch
+
+    assert t_indptr.dtype == torch.int32 and t_indices.dtype == torch.int32 and t_indptr.numel() == num_cols + 1
+    assert t_indptr.is_contiguous() and t_indices.is_contiguous()
+    nnz = t_indices.numel()
+    assert t_order.dtype == torch.int32 and t_order.is_contiguous() and t_order.numel() == nnz
+    assert grad_out.dim() == 2 and grad_out.dtype == torch.float32 and grad_out.is_contiguous()
+    assert arg.dtype == torch.int32 and arg.is_contiguous() and arg.shape == grad_out.shape
+    assert output.dtype == torch.float32 and output.is_contiguous() and output.shape == (num_cols, grad_out.shape[1])
+    _checked("voltrix_launch_spmm_csr_reduce_backward", t_indptr.data_ptr(), t_indices.data_ptr(), t_order.data_ptr(), num_cols, nnz,
+             grad_out.shape[1], grad_out.data_ptr(), arg.data_ptr(), output.data_ptr(), stream)
 
 
 def launch_scatter_values(values, slots, plane, stream) -> None:
