@@ -721,6 +721,57 @@ void voltrix_launch_spmm_csr_reduce(void* indptr, void* indices, int num_rows, i
 void voltrix_launch_spmm_csr_reduce_backward(void* t_indptr, void* t_indices, void* t_order, int num_cols, int64_t num_entries, int embedding_dim,
                                              void* grad_out, void* arg, void* output, void* stream, int* return_code);
 
+/* Neighbour sampling on a device int32 CSR and the relabelling of a sampled block (voltrix/neighbor_sample_kernels.hpp): what produces
+ * the rectangular [num_dst, num_src] patterns the CSR operators above take (GraphSAGE-style mini-batches).  No reference counterpart.
+ * THE SAMPLING RULE.  For a seed row r (its global row id), fan-out k = fanout, degree d = indptr[r + 1] - indptr[r]:
+ *   draw(r, i) = word i & 3 of Philox4x32-10(counter = (r, (i >> 2) | 0x80000000, offset & 0xffffffff, offset >> 32),
+ *                key = (seed & 0xffffffff, seed >> 32)); bit 31 of counter word 1 separates these draws from
+ *                voltrix_launch_dropout_mask's (edge, h >> 2, ...) counters: one seed for both gives unrelated streams.
+ *   replace = 0, d <= k: every entry of the row, in CSR order, no draw used.  fanout = -1 (VOLTRIX_SAMPLE_ALL) means this for every
+ *                row, whatever replace is.
+ *   replace = 0, d > k:  Floyd's algorithm on entry positions: for i = 0 .. k - 1, j = d - k + i, t = (uint64(draw(r, i)) * (j + 1)) >> 32;
+ *                take t unless it is taken already, then take j.  The k positions are output in ascending order (a sampled row keeps CSR
+ *                order).  A function of (seed, offset, r, d, k) only: not of the other seeds, their order or the launch geometry.  The
+ *                multiply-shift has a relative bias of at most d / 2^32 per position.
+ *   replace = 1, d > 0:  exactly k entries, entry i at position (uint64(draw(r, i)) * d) >> 32, in draw order; d == 0: none.
+ * seeds = device int32[num_seeds] global row ids; a seed outside [0, num_rows) has degree 0 inside the kernel (never an out-of-bounds
+ * read; callers reject it earlier).  s_indptr = device int32[num_seeds + 1], the caller's prefix sum of the per-seed counts the rule
+ * gives (min(d, k); d > 0 ? k : 0 with replace; d for fanout = -1); num_sampled = s_indptr[num_seeds].  Outputs, every element written
+ * when s_indptr is the rule's, neither needs initialising: s_indices = device int32[num_sampled], the global column ids; s_entries =
+ * device int32[num_sampled], the CSR entry id of every sampled entry (edge features, edge values, arg-style bookkeeping).  A row never
+ * writes past its own segment of s_indptr.  One lane per seed, 256 per workgroup, O(k^2) compares and k gathers per row whatever its
+ * degree (fanout = -1 copies a row with one lane: O(d)); the sorted positions live in 256 k 4 bytes of dynamic LDS (k <= 64); no
+ * atomics, no workspace, no host synchronisation, the same bits on every call.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: negative sizes, num_sampled > INT_MAX, fanout outside 1 .. 64 and not -1,
+ * replace outside {0, 1}, a null or misaligned pointer (indices, s_indices, s_entries only where num_sampled > 0); VOLTRIX_OK without a
+ * launch for num_seeds == 0 or num_sampled == 0.  Alignment: 4 bytes everywhere. */
+#define VOLTRIX_SAMPLE_ALL (-1)
+void voltrix_launch_sample_neighbors(void* indptr, void* indices, int num_rows, void* seeds, int num_seeds, void* s_indptr,
+                                     int64_t num_sampled, int fanout, int replace, uint64_t seed, uint64_t offset, void* s_indices,
+                                     void* s_entries, void* stream, int* return_code);
+
+/* Relabelling a sampled block: global column ids -> positions in src_ids, the seeds first.  table = device int32[num_cols], ZERO ON
+ * ENTRY (the one buffer here that must be initialised); three launches on one stream:
+ *   voltrix_launch_block_mark:        table[cols[e]] = 1 for e < num_sampled (plain stores of one value);
+ *   voltrix_launch_block_mark_seeds:  table[seeds[i]] = -(i + 1) -- the seeds win over the marks.  Duplicate seeds are the caller's to
+ *                                     exclude (one of the stores wins: which is not defined);
+ *   (the caller takes rank = the inclusive count of table > 0 over the columns, device int32[num_cols], and num_src = num_seeds +
+ *   rank[num_cols - 1])
+ *   voltrix_launch_block_relabel:     local[e] = t < 0 ? -t - 1 : num_seeds + rank[c] - 1 with c = cols[e], t = table[c]; src_ids[num_seeds +
+ *                                     rank[c] - 1] = c for marked c; src_ids[i] = seeds[i].
+ * So src_ids[0 .. num_seeds) is the seeds in the given order and the rest the other sampled columns in ascending id: deterministic, and
+ * a gather feat[src_ids] reads ascending addresses.  Every element of local (device int32[num_sampled]) and src_ids (device
+ * int32[num_src]) is written; neither needs initialising.  A column or seed outside [0, num_cols) is skipped by the mark launches and
+ * gives local = -1: never an out-of-bounds access.  No atomics, no host synchronisation inside.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: negative sizes, num_sampled > INT_MAX, num_src < num_seeds, a null or
+ * misaligned pointer among those the sizes make the launch touch; VOLTRIX_OK without a launch where there is nothing to do
+ * (num_sampled == 0 or num_cols == 0 for block_mark, num_seeds == 0 or num_cols == 0 for block_mark_seeds, both counts 0 for
+ * block_relabel).  Alignment: 4 bytes everywhere. */
+void voltrix_launch_block_mark(void* cols, int64_t num_sampled, int num_cols, void* table, void* stream, int* return_code);
+void voltrix_launch_block_mark_seeds(void* seeds, int num_seeds, int num_cols, void* table, void* stream, int* return_code);
+void voltrix_launch_block_relabel(void* cols, int64_t num_sampled, void* seeds, int num_seeds, void* table, void* rank, int num_cols,
+                                  int num_src, void* local, void* src_ids, void* stream, int* return_code);
+
 /* Rows of a dense row-major matrix times a per-row factor: dst[i, :] = T(float(src[i, :]) * scale[i]); dst may be src.
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,

@@ -22,6 +22,7 @@ from .gatv2_score import gatv2_score
 from .attn_aggregate import attn_aggregate
 from .spmm_reduce import spmm_reduce
 from .dropout import apply_dropout_mask, dropout_mask
+from .sampling import Block, compact_block, sample_blocks, sample_neighbors
 from .graphed import GraphedSpMM
 from . import autograd, hybrid, jit, sidecar, utils
 

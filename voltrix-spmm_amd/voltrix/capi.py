@@ -100,6 +100,10 @@ SIGNATURES = {
     "voltrix_launch_attn_aggregate_dropout_grad_feat_csr": (None, [_P, _P, _P, _I, _L, _I, _I, _P, _I, _P, _P, _P, _F, _P, _P, _F, _P, _RC_P]),
     "voltrix_launch_spmm_csr_reduce": (None, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _RC_P]),
     "voltrix_launch_spmm_csr_reduce_backward": (None, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _RC_P]),
+    "voltrix_launch_sample_neighbors": (None, [_P, _P, _I, _P, _I, _P, _L, _I, _I, _U64, _U64, _P, _P, _P, _RC_P]),
+    "voltrix_launch_block_mark": (None, [_P, _L, _I, _P, _P, _RC_P]),
+    "voltrix_launch_block_mark_seeds": (None, [_P, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_block_relabel": (None, [_P, _L, _P, _I, _P, _P, _I, _I, _P, _P, _P, _RC_P]),
     "voltrix_csr_preprocess_workspace_bytes": (_L, [_I, _I, _L, _I]),
     "voltrix_launch_csr_window_count": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
     "voltrix_launch_csr_fill": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
@@ -896,6 +900,55 @@ def launch_spmm_csr_reduce_backward(t_indptr, t_indices, t_order, num_cols: int,
     assert output.dtype == torch.float32 and output.is_contiguous() and output.shape == (num_cols, grad_out.shape[1])
     _checked("voltrix_launch_spmm_csr_reduce_backward", t_indptr.data_ptr(), t_indices.data_ptr(), t_order.data_ptr(), num_cols, nnz,
              grad_out.shape[1], grad_out.data_ptr(), arg.data_ptr(), output.data_ptr(), stream)
+
+
+SAMPLE_ALL, SAMPLE_MAX_FANOUT = -1, 64      # `fanout` of voltrix_launch_sample_neighbors: every entry of every row; the largest fan-out
+
+
+def launch_sample_neighbors(indptr, indices, num_rows: int, seeds, s_indptr, num_sampled: int, fanout: int, replace: bool, seed: int,
+                            offset: int, s_indices, s_entries, stream) -> None:
+    """At most ``fanout`` entries of every seed row of a device int32 CSR by the sampling rule of voltrix/neighbor_sample_kernels.hpp:
+    ``s_indices`` / ``s_entries`` int32 [num_sampled] get the global column ids and the CSR entry ids, in the segments ``s_indptr``
+    (int32 [S + 1], the prefix sum of the rule's per-seed counts) gives; see include/voltrix_capi.h."""
+    import torch
+
+    for t in (indptr, indices, seeds, s_indptr, s_indices, s_entries):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+    assert indptr.numel() == num_rows + 1 and s_indptr.numel() == seeds.numel() + 1
+    assert s_indices.numel() == num_sampled == s_entries.numel()
+    _checked("voltrix_launch_sample_neighbors", indptr.data_ptr(), indices.data_ptr(), num_rows, seeds.data_ptr(), seeds.numel(),
+             s_indptr.data_ptr(), num_sampled, int(fanout), int(bool(replace)), int(seed), int(offset), s_indices.data_ptr(),
+             s_entries.data_ptr(), stream)
+
+
+def launch_block_mark(cols, num_cols: int, table, stream) -> None:
+    """``table[cols[e]] = 1`` (device int32; ``table`` [num_cols] zero on entry); see include/voltrix_capi.h."""
+    import torch
+
+    assert cols.dtype == torch.int32 and cols.is_contiguous() and table.dtype == torch.int32 and table.is_contiguous()
+    assert table.numel() == num_cols and cols.is_cuda and table.is_cuda
+    _checked("voltrix_launch_block_mark", cols.data_ptr(), cols.numel(), num_cols, table.data_ptr(), stream)
+
+
+def launch_block_mark_seeds(seeds, num_cols: int, table, stream) -> None:
+    """``table[seeds[i]] = -(i + 1)``, after ``launch_block_mark`` on the same stream; see include/voltrix_capi.h."""
+    import torch
+
+    assert seeds.dtype == torch.int32 and seeds.is_contiguous() and table.dtype == torch.int32 and table.is_contiguous()
+    assert table.numel() == num_cols and seeds.is_cuda and table.is_cuda
+    _checked("voltrix_launch_block_mark_seeds", seeds.data_ptr(), seeds.numel(), num_cols, table.data_ptr(), stream)
+
+
+def launch_block_relabel(cols, seeds, table, rank, num_cols: int, local, src_ids, stream) -> None:
+    """``local[e]`` = the position of ``cols[e]`` in ``src_ids`` (the seeds, then the other marked columns ascending) and ``src_ids``
+    itself, from the marked ``table`` and ``rank``, the inclusive count of its positive entries; see include/voltrix_capi.h."""
+    import torch
+
+    for t in (cols, seeds, table, rank, local, src_ids):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+    assert table.numel() == num_cols == rank.numel() and local.numel() == cols.numel() and src_ids.numel() >= seeds.numel()
+    _checked("voltrix_launch_block_relabel", cols.data_ptr(), cols.numel(), seeds.data_ptr(), seeds.numel(), table.data_ptr(),
+             rank.data_ptr(), num_cols, src_ids.numel(), local.data_ptr(), src_ids.data_ptr(), stream)
 
 
 def launch_scatter_values(values, slots, plane, stream) -> None:
