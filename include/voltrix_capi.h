@@ -772,6 +772,55 @@ void voltrix_launch_block_mark_seeds(void* seeds, int num_seeds, int num_cols, v
 void voltrix_launch_block_relabel(void* cols, int64_t num_sampled, void* seeds, int num_seeds, void* table, void* rank, int num_cols,
                                   int num_src, void* local, void* src_ids, void* stream, int* return_code);
 
+/* Induced subgraphs and random walks on a device int32 CSR (voltrix/induced_subgraph_kernels.hpp): what subgraph mini-batch training
+ * needs (Cluster-GCN, GraphSAINT-RW).  No reference counterpart.
+ * THE SUBGRAPH CONTRACT.  rows = device int32[num_sub_rows] global row ids, any order, duplicates allowed (a duplicate row is emitted
+ * twice); cols = device int32[C] global column ids in [0, num_cols), no duplicates, known to these calls only through table = device
+ * int32[num_cols] with table[cols[j]] = -(j + 1) and 0 elsewhere (ZERO it, then voltrix_launch_block_mark_seeds(cols, C, num_cols,
+ * table)).  Row i of the result is row rows[i] of the CSR with exactly those entries whose column is in cols, IN CSR ORDER: a stable
+ * compaction, so a sorted row stays sorted only if cols is ascending; a column that appears twice in a row is kept twice.  s_local[e]
+ * is the position in cols of the entry's column (the local id of cols[j] is j: feat[cols] is the subgraph's feature matrix);
+ * s_entries[e] is the entry's index in indices (edge values, edge features, arg-style bookkeeping, as in
+ * voltrix_launch_sample_neighbors).  Columns in indices outside [0, num_cols) are never selected and never read through; a row id
+ * outside [0, num_rows) has degree 0 inside the kernels (never an out-of-bounds read; callers reject it earlier).
+ *   voltrix_launch_subgraph_count: counts[i] = the number of kept entries of row rows[i]; every element of counts (device
+ *                                  int32[num_sub_rows]) is written;
+ *   (the caller takes s_indptr = the exclusive prefix sum of counts, device int32[num_sub_rows + 1], and num_selected =
+ *   s_indptr[num_sub_rows])
+ *   voltrix_launch_subgraph_fill:  s_local, s_entries = device int32[num_selected]; every element of both is written, neither needs
+ *                                  initialising; a row never writes more than s_indptr[i + 1] - s_indptr[i].
+ * group = 4, 8, 16, 32 or 64: the lanes that own one row and walk it `group` entries at a time (coalesced loads of indices, a gather
+ * of table, the group's slice of a 64-bit ballot: a stable compaction without LDS); every width gives the same bits.  A hub row is
+ * walked by one group.  No atomics, no workspace, no host synchronisation inside.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any HIP call: negative sizes, num_selected > INT_MAX, a group outside the five widths,
+ * a null or misaligned pointer (s_local and s_entries only where num_selected > 0); VOLTRIX_OK without a launch for num_sub_rows == 0
+ * (and, for the fill, num_selected == 0).  Alignment: 4 bytes everywhere. */
+void voltrix_launch_subgraph_count(void* indptr, void* indices, int num_rows, void* rows, int num_sub_rows, void* table, int num_cols,
+                                   int group, void* counts, void* stream, int* return_code);
+void voltrix_launch_subgraph_fill(void* indptr, void* indices, int num_rows, void* rows, int num_sub_rows, void* table, int num_cols,
+                                  int group, void* s_indptr, int64_t num_selected, void* s_local, void* s_entries, void* stream,
+                                  int* return_code);
+
+/* THE WALK RULE.  nodes[w, 0] = starts[w].  At step t (0-based) walker w stands on node v of degree d = indptr[v + 1] - indptr[v]:
+ *   d == 0:     the walk is over; this and every later step write -1 in nodes and in entries;
+ *   otherwise:  the walker takes the entry at position (uint64(draw(w, t)) * d) >> 32 of row v: entries[w, t] is its CSR entry id,
+ *               nodes[w, t + 1] its column;
+ *   draw(w, t) = word t & 3 of Philox4x32-10(counter = (w, (t >> 2) | 0xC0000000, offset & 0xffffffff, offset >> 32),
+ *               key = (seed & 0xffffffff, seed >> 32)); bits 31 and 30 of counter word 1 separate these draws from
+ *               voltrix_launch_sample_neighbors' ((i >> 2) | 0x80000000, i < 64) and voltrix_launch_dropout_mask's (h >> 2 < 2^29):
+ *               one seed for all three gives unrelated streams.
+ * A node id outside [0, num_rows) -- a column of a rectangular CSR, a start the caller did not reject -- is recorded as it is and ends
+ * the walk like a dead end (degree 0: indptr is never read out of bounds).  w is the walker's index in starts = device
+ * int32[num_walkers]: duplicate starts are different walks; the result is a function of (seed, offset, w, starts[w], the graph) only.
+ * Outputs, every element written, the -1 padding included: step_major = 0: nodes = device int32[num_walkers, length + 1], entries =
+ * device int32[num_walkers, length]; step_major = 1: [length + 1, num_walkers] and [length, num_walkers] (coalesced stores).  One lane
+ * per walker, one Philox evaluation per four steps; no atomics, no workspace, no host synchronisation.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any HIP call: negative sizes, length > 2^20, num_walkers * (length + 1) > INT_MAX,
+ * step_major outside {0, 1}, a null or misaligned pointer (indices and entries only where length > 0); VOLTRIX_OK without a launch for
+ * num_walkers == 0.  Alignment: 4 bytes everywhere. */
+void voltrix_launch_random_walk(void* indptr, void* indices, int num_rows, void* starts, int num_walkers, int length, uint64_t seed,
+                                uint64_t offset, void* nodes, void* entries, int step_major, void* stream, int* return_code);
+
 /* Rows of a dense row-major matrix times a per-row factor: dst[i, :] = T(float(src[i, :]) * scale[i]); dst may be src.
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,

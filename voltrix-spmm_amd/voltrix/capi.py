@@ -104,6 +104,9 @@ SIGNATURES = {
     "voltrix_launch_block_mark": (None, [_P, _L, _I, _P, _P, _RC_P]),
     "voltrix_launch_block_mark_seeds": (None, [_P, _I, _I, _P, _P, _RC_P]),
     "voltrix_launch_block_relabel": (None, [_P, _L, _P, _I, _P, _P, _I, _I, _P, _P, _P, _RC_P]),
+    "voltrix_launch_subgraph_count": (None, [_P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_subgraph_fill": (None, [_P, _P, _I, _P, _I, _P, _I, _I, _P, _L, _P, _P, _P, _RC_P]),
+    "voltrix_launch_random_walk": (None, [_P, _P, _I, _P, _I, _I, _U64, _U64, _P, _P, _I, _P, _RC_P]),
     "voltrix_csr_preprocess_workspace_bytes": (_L, [_I, _I, _L, _I]),
     "voltrix_launch_csr_window_count": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
     "voltrix_launch_csr_fill": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
@@ -949,6 +952,49 @@ def launch_block_relabel(cols, seeds, table, rank, num_cols: int, local, src_ids
     assert table.numel() == num_cols == rank.numel() and local.numel() == cols.numel() and src_ids.numel() >= seeds.numel()
     _checked("voltrix_launch_block_relabel", cols.data_ptr(), cols.numel(), seeds.data_ptr(), seeds.numel(), table.data_ptr(),
              rank.data_ptr(), num_cols, src_ids.numel(), local.data_ptr(), src_ids.data_ptr(), stream)
+
+
+SUBGRAPH_GROUPS, WALK_MAX_LENGTH = (4, 8, 16, 32, 64), 2 ** 20      # the lane-group widths of the subgraph kernels; the longest walk
+
+
+def launch_subgraph_count(indptr, indices, num_rows: int, rows, table, group: int, counts, stream) -> None:
+    """``counts[i]`` = the number of entries of row ``rows[i]`` whose column ``table`` marks (``table[cols[j]] = -(j + 1)``), walked by
+    lane groups of ``group`` lanes; see include/voltrix_capi.h."""
+    import torch
+
+    for t in (indptr, indices, rows, table, counts):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+    assert indptr.numel() == num_rows + 1 and counts.numel() == rows.numel()
+    _checked("voltrix_launch_subgraph_count", indptr.data_ptr(), indices.data_ptr(), num_rows, rows.data_ptr(), rows.numel(),
+             table.data_ptr(), table.numel(), int(group), counts.data_ptr(), stream)
+
+
+def launch_subgraph_fill(indptr, indices, num_rows: int, rows, table, group: int, s_indptr, s_local, s_entries, stream) -> None:
+    """The kept entries of every row ``rows[i]`` into its segment of ``s_indptr`` (the prefix sum of ``launch_subgraph_count``'s
+    counts): ``s_local`` the position of the column in ``cols``, ``s_entries`` the CSR entry id; see include/voltrix_capi.h."""
+    import torch
+
+    for t in (indptr, indices, rows, table, s_indptr, s_local, s_entries):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+    assert indptr.numel() == num_rows + 1 and s_indptr.numel() == rows.numel() + 1 and s_local.numel() == s_entries.numel()
+    _checked("voltrix_launch_subgraph_fill", indptr.data_ptr(), indices.data_ptr(), num_rows, rows.data_ptr(), rows.numel(),
+             table.data_ptr(), table.numel(), int(group), s_indptr.data_ptr(), s_local.numel(), s_local.data_ptr(),
+             s_entries.data_ptr(), stream)
+
+
+def launch_random_walk(indptr, indices, num_rows: int, starts, length: int, seed: int, offset: int, nodes, entries, stream,
+                       step_major: bool = False) -> None:
+    """``starts.numel()`` random walks of ``length`` steps by the walk rule of voltrix/induced_subgraph_kernels.hpp into ``nodes``
+    ``[W, length + 1]`` and ``entries`` ``[W, length]`` (``step_major``: ``[length + 1, W]`` and ``[length, W]``); see
+    include/voltrix_capi.h."""
+    import torch
+
+    for t in (indptr, indices, starts, nodes, entries):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+    count = starts.numel()
+    assert indptr.numel() == num_rows + 1 and nodes.numel() == count * (length + 1) and entries.numel() == count * length
+    _checked("voltrix_launch_random_walk", indptr.data_ptr(), indices.data_ptr(), num_rows, starts.data_ptr(), count, int(length),
+             int(seed), int(offset), nodes.data_ptr(), entries.data_ptr(), int(bool(step_major)), stream)
 
 
 def launch_scatter_values(values, slots, plane, stream) -> None:
