@@ -821,6 +821,41 @@ void voltrix_launch_subgraph_fill(void* indptr, void* indices, int num_rows, voi
 void voltrix_launch_random_walk(void* indptr, void* indices, int num_rows, void* starts, int num_walkers, int length, uint64_t seed,
                                 uint64_t offset, void* nodes, void* entries, int step_major, void* stream, int* return_code);
 
+/* Negative sampling on a device int32 CSR [num_rows, num_cols] and the endpoints of CSR entries (voltrix/negative_sample_kernels.hpp):
+ * what link-prediction mini-batches need next to voltrix_launch_sample_neighbors (the layers) and voltrix_launch_sddmm_csr (the
+ * scores).  No reference counterpart.
+ * THE NEGATIVE RULE.  src = device int32[num_src] GLOBAL row ids, duplicates allowed; k slots per position, T = max_tries tries per slot:
+ *   draw(p, q) = word q & 3 of Philox4x32-10(counter = (p, (q >> 2) | 0x40000000, offset & 0xffffffff, offset >> 32),
+ *                key = (seed & 0xffffffff, seed >> 32)); p is the POSITION in src, not the row id, so duplicate sources get different
+ *                negatives.  Bit 30 set with bit 31 clear is the last free domain of counter word 1: voltrix_launch_dropout_mask uses
+ *                00, voltrix_launch_sample_neighbors 10, voltrix_launch_random_walk 11: one seed for all four gives unrelated streams.
+ *   slot (p, j): the draws q = j T + t for the tries t = 0 .. T - 1 (j T need not be a multiple of 4).  Try t proposes
+ *                c = (uint64(draw(p, q)) * num_cols) >> 32; it is rejected if c occurs in row src[p] and, with exclude_self = 1, if
+ *                c == src[p].  neg[p, j] = the first accepted c, or -1 if all T tries are rejected.
+ * Slots are independent: one column may appear twice in a row of neg.  neg[p, j] is a function of (seed, offset, p, j, src[p], T, the
+ * graph) only: not of the launch geometry, of k or of the other sources.  A row id outside [0, num_rows) has degree 0 inside the kernel
+ * (never an out-of-bounds read; callers reject it).  Entries of indices outside [0, num_cols) never match and are never read through.
+ * num_cols == 0: every slot is -1.  assume_sorted = 1 is the PRECONDITION that every row's columns ascend (duplicates allowed): a binary
+ * search, O(T log d) per slot, so a hub row costs log d; assume_sorted = 0: a linear scan by the slot's one lane, O(T d), the slow
+ * path; on sorted input both give the same bits.  Output: neg = device int32[num_src, k], every element written, the -1 included;
+ * nothing needs initialising.  One lane per slot, 256 per workgroup; no LDS, no atomics, no workspace, no host synchronisation.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any HIP call: negative sizes, num_entries > INT_MAX, k outside 1 .. 1024, max_tries
+ * outside 1 .. 256, num_src * k > INT_MAX, exclude_self or assume_sorted outside {0, 1}, a null or misaligned pointer (indices may be
+ * null where num_entries == 0); VOLTRIX_OK without a launch for num_src == 0.  Alignment: 4 bytes everywhere. */
+void voltrix_launch_negative_sample(void* indptr, void* indices, int num_rows, int num_cols, int64_t num_entries, void* src, int num_src,
+                                    int k, int max_tries, int exclude_self, int assume_sorted, uint64_t seed, uint64_t offset, void* neg,
+                                    void* stream, int* return_code);
+
+/* ENTRY -> ENDPOINTS.  entries = device int32[num_ids] CSR entry ids.  rows[i] = the one r with indptr[r] <= e < indptr[r + 1], found
+ * as the upper bound of e in indptr minus one, so runs of empty rows before and after are stepped over (no [nnz] row-id array is
+ * kept); cols[i] = indices[e].  An id outside [0, num_entries) writes (-1, -1): never an out-of-bounds read.  rows, cols = device
+ * int32[num_ids], every element written.  One lane per id, O(log num_rows) reads of indptr; no atomics, no workspace, no host
+ * synchronisation.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any HIP call: negative sizes, num_entries > INT_MAX, a null or misaligned pointer
+ * (indices may be null where num_entries == 0); VOLTRIX_OK without a launch for num_ids == 0.  Alignment: 4 bytes everywhere. */
+void voltrix_launch_edge_endpoints(void* indptr, void* indices, int num_rows, int64_t num_entries, void* entries, int num_ids, void* rows,
+                                   void* cols, void* stream, int* return_code);
+
 /* Rows of a dense row-major matrix times a per-row factor: dst[i, :] = T(float(src[i, :]) * scale[i]); dst may be src.
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,

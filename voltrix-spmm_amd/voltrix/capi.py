@@ -107,6 +107,8 @@ SIGNATURES = {
     "voltrix_launch_subgraph_count": (None, [_P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _RC_P]),
     "voltrix_launch_subgraph_fill": (None, [_P, _P, _I, _P, _I, _P, _I, _I, _P, _L, _P, _P, _P, _RC_P]),
     "voltrix_launch_random_walk": (None, [_P, _P, _I, _P, _I, _I, _U64, _U64, _P, _P, _I, _P, _RC_P]),
+    "voltrix_launch_negative_sample": (None, [_P, _P, _I, _I, _L, _P, _I, _I, _I, _I, _I, _U64, _U64, _P, _P, _RC_P]),
+    "voltrix_launch_edge_endpoints": (None, [_P, _P, _I, _L, _P, _I, _P, _P, _P, _RC_P]),
     "voltrix_csr_preprocess_workspace_bytes": (_L, [_I, _I, _L, _I]),
     "voltrix_launch_csr_window_count": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
     "voltrix_launch_csr_fill": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
@@ -995,6 +997,35 @@ def launch_random_walk(indptr, indices, num_rows: int, starts, length: int, seed
     assert indptr.numel() == num_rows + 1 and nodes.numel() == count * (length + 1) and entries.numel() == count * length
     _checked("voltrix_launch_random_walk", indptr.data_ptr(), indices.data_ptr(), num_rows, starts.data_ptr(), count, int(length),
              int(seed), int(offset), nodes.data_ptr(), entries.data_ptr(), int(bool(step_major)), stream)
+
+
+NEGATIVE_MAX_SLOTS, NEGATIVE_MAX_TRIES = 1024, 256      # `k` and `max_tries` of voltrix_launch_negative_sample
+
+
+def launch_negative_sample(indptr, indices, num_rows: int, num_cols: int, src, k: int, max_tries: int, exclude_self: bool,
+                           assume_sorted: bool, seed: int, offset: int, neg, stream) -> None:
+    """``neg`` int32 ``[S, k]``: for every position of ``src``, ``k`` columns that do not occur in its row, by the negative rule of
+    voltrix/negative_sample_kernels.hpp (``-1`` where ``max_tries`` tries were all rejected); see include/voltrix_capi.h."""
+    import torch
+
+    for t in (indptr, indices, src, neg):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+    assert indptr.numel() == num_rows + 1 and neg.numel() == src.numel() * k
+    _checked("voltrix_launch_negative_sample", indptr.data_ptr(), indices.data_ptr(), num_rows, int(num_cols), indices.numel(),
+             src.data_ptr(), src.numel(), int(k), int(max_tries), int(bool(exclude_self)), int(bool(assume_sorted)), int(seed),
+             int(offset), neg.data_ptr(), stream)
+
+
+def launch_edge_endpoints(indptr, indices, num_rows: int, entries, rows, cols, stream) -> None:
+    """``rows[i]`` / ``cols[i]``: the row that holds CSR entry ``entries[i]`` (a search in ``indptr``) and its column; ``-1, -1`` for an
+    id outside ``[0, nnz)``; see include/voltrix_capi.h."""
+    import torch
+
+    for t in (indptr, indices, entries, rows, cols):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+    assert indptr.numel() == num_rows + 1 and rows.numel() == entries.numel() == cols.numel()
+    _checked("voltrix_launch_edge_endpoints", indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), entries.data_ptr(),
+             entries.numel(), rows.data_ptr(), cols.data_ptr(), stream)
 
 
 def launch_scatter_values(values, slots, plane, stream) -> None:
