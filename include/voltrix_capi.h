@@ -316,6 +316,45 @@ void voltrix_launch_spmm_panel_parts_bf16(void* panel_ptr, void* panel_cols, voi
 void voltrix_launch_combine_panel_partials(void* cuts, int num_cuts, void* partials, void* output, int num_nodes,
                                            int embedding_dim, int panel_rows, int accumulate, void* stream, int* return_code);
 
+/* TICKET JOIN of the two-level step (no reference counterpart; protocol: voltrix/spmm_kernels.hpp "Ticket join"): the window
+ * kernel and the panel kernel meet in `output` WITHOUT a zero fill.  tickets int32 [4 + ceil(num_nodes / 16)] (device memory,
+ * 16-byte aligned) is zeroed by the caller at the start of every call (hipMemsetAsync of the whole buffer, before either
+ * launch); word 0 is a sticky error word (nonzero after the call: a bounded wait ran out and the result is not to be
+ * trusted), word 4 + b the ticket of rows [16 b, 16 b + 16).  Per 16-row block the FIRST of the two kernels stores its tile
+ * (write-through 16-byte stores) and the second adds its own with float atomics -- half the atomics of the atomic join, the
+ * same bits but for the sign of an exact zero.  The four launches of a call, all with the same `tickets`:
+ *   voltrix_launch_spmm_*_sched_ticket          the window kernel (arguments of _sched; no window_order, no row_map)
+ *   voltrix_launch_spmm_panel_ticket_*          the panel kernel, on the same or on another stream: panels whole
+ *                                               (panel_order or NULL, parts NULL) or in pieces (parts; panel_order ignored)
+ *   voltrix_launch_combine_partials_ticket      after BOTH kernels (join the streams first), when the unit table has cuts
+ *   voltrix_launch_combine_panel_partials_ticket   after that, when the part table has cuts
+ * The combine passes store a block whose ticket is still 0 (no kernel wrote it) and add otherwise.  Only for embedding_dim <= fs
+ * of BOTH tiles (one column slab), embedding_dim % 8 == 0, a binary 16-bit operand and `output` on ordinary device memory (see
+ * MEMORY REQUIREMENT above); VOLTRIX_ERR_BAD_SHAPE otherwise. */
+void voltrix_launch_spmm_f16_sched_ticket(void* blk_offsets, void* hspa_packed, void* hind, int num_nodes, int num_edges,
+                                          int embedding_dim, void* input, void* output, int fs, int depth, int waves,
+                                          void* out_scale, void* units, void* unit_ptr, int max_units_per_xcd, void* partials,
+                                          int units_per_wave, void* tickets, void* stream, int* return_code);
+void voltrix_launch_spmm_bf16_sched_ticket(void* blk_offsets, void* hspa_packed, void* hind, int num_nodes, int num_edges,
+                                           int embedding_dim, void* input, void* output, int fs, int depth, int waves,
+                                           void* out_scale, void* units, void* unit_ptr, int max_units_per_xcd, void* partials,
+                                           int units_per_wave, void* tickets, void* stream, int* return_code);
+void voltrix_launch_combine_partials_ticket(void* cuts, int num_cuts, void* partials, void* output, int num_nodes,
+                                            int embedding_dim, void* tickets, void* stream, int* return_code);
+void voltrix_launch_spmm_panel_ticket_f16(void* panel_ptr, void* panel_cols, void* panel_bits, void* panel_order, void* parts,
+                                          int num_parts, void* xcd_ptr, int max_per_xcd, void* partials, void* tickets,
+                                          int num_nodes, int embedding_dim, void* input, int64_t input_rows, void* output, int fs,
+                                          int depth, int waves, int row_blocks, int ksteps, int slab_policy, void* out_scale,
+                                          void* stream, int* return_code);
+void voltrix_launch_spmm_panel_ticket_bf16(void* panel_ptr, void* panel_cols, void* panel_bits, void* panel_order, void* parts,
+                                           int num_parts, void* xcd_ptr, int max_per_xcd, void* partials, void* tickets,
+                                           int num_nodes, int embedding_dim, void* input, int64_t input_rows, void* output, int fs,
+                                           int depth, int waves, int row_blocks, int ksteps, int slab_policy, void* out_scale,
+                                           void* stream, int* return_code);
+void voltrix_launch_combine_panel_partials_ticket(void* cuts, int num_cuts, void* partials, void* output, int num_nodes,
+                                                  int embedding_dim, int panel_rows, void* tickets, void* stream,
+                                                  int* return_code);
+
 /* Builders of the two schedules above, on the device (round 4; voltrix/schedule_tables.hpp; the Python host's
  * voltrix/schedule.py::split_equal_work and voltrix/hybrid.py::panel_parts are their torch-tensor restatements).
  * XCD ranges: xcd_ptr int32[9] <- b[0] = 0 <= ... <= b[8] = n such that the eight ranges of the items' work have about equal

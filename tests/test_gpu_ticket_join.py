@@ -1,0 +1,163 @@
+"""GPU: the ticket join of the two-level step (voltrix/spmm_kernels.hpp "Ticket join", hybrid.join_mode) against the atomic join.
+
+The two kernels meet in C without a zero fill: per 16-row block the first producer stores its tile, the second adds its own with
+float atomics.  Two addends per element, so the result is the atomic join's bit for bit -- ``torch.equal`` treats -0.0 == 0.0, the one
+difference the protocol allows.  Every case runs on a C pre-filled with NaN (a block nobody stores stays NaN and fails every check),
+is held to the fp64 bound of test_gpu_spmm.py, repeated ten times, and has to leave the sticky error word of its ticket buffer at zero.
+
+Graph: N = 1040 rows = 65 windows; 512-row panels: two full ones and a 16-row tail panel that has no shared column at all.  F = 128
+fp16, mean degree ~61, half of the edges in a band around the diagonal (+-64, +-96 in the second panel: shared columns at tau = 24),
+half uniform (residual).  Rows 16..31 have no edge (a window without residual edges); rows 32..47 only reach columns nobody else in
+their panel uses (a row block of a panel without a shared column).  ``hub``: row 600 reaches every column, its window is cut into
+units; ``cut_panel``: the same graph with the second (longer) panel forced into two pieces, so the hub's window meets a cut panel and
+its block is written by the combine passes alone."""
+import numpy as np
+import pytest
+import torch
+
+import voltrix
+from test_gpu_spmm import _assert_close
+from voltrix import capi, hybrid
+from voltrix.jit_kernels.spmm import handle_unit_table
+from voltrix.spmm.spmm import _operand, _run_two_level
+
+pytestmark = pytest.mark.gpu
+
+N, F, TAU = 1040, 128, 24
+_CACHE = {}
+
+
+def _graph(hub: bool):
+    rng = np.random.default_rng(7)
+    rows = []
+    for r in range(N):
+        if 16 <= r < 32:
+            rows.append(np.zeros(0, np.int64))
+            continue
+        if 32 <= r < 48:
+            rows.append(np.sort(rng.choice(np.arange(960, N), 8, replace=False)))     # <= 16 < TAU references per column in panel 0
+            continue
+        half = 64 if r < 512 else 96     # the second panel's band is wider: more shared columns, more k-steps than the first
+        band = rng.choice(np.arange(max(0, r - half), min(N, r + half + 1)), 32 if r < 1024 else 16, replace=False)
+        far = rng.choice(900, 32 if r < 1024 else 0, replace=False)     # the tail panel's rows: a short window, not cut
+        rows.append(np.unique(np.r_[band, far]))
+    if hub:
+        rows[600] = np.arange(N)         # every column: a window several times the median length, cut into units
+    indptr = np.zeros(N + 1, np.int32)
+    indptr[1:] = np.cumsum([len(r) for r in rows])
+    return indptr, np.concatenate(rows).astype(np.int32)
+
+
+def _case(name):
+    """(indptr, indices, handle, feat32) of a variant, built once and left unchanged."""
+    if name not in _CACHE:
+        indptr, indices = _graph(hub=name != "uncut")     # cut_panel: the hub's cut window lies in the cut panel
+        two = voltrix.csr_preprocess_hybrid(torch.from_numpy(indptr), torch.from_numpy(indices), N, tau=TAU)
+        two.hash_tag = f"ticket_join_{name}"
+        assert two.plan.num_shared_edges > 0 and two.plan.num_resid_edges > 0 and two.plan.num_panels == 3
+        nks = (two.plan.panel_ptr[1:] - two.plan.panel_ptr[:-1]).tolist()
+        assert nks[0] > 0 and nks[1] > 0 and nks[2] == 0          # the 16-row tail panel has no shared column
+        if name == "cut_panel":        # forced through the plan's piece bound: the longer panel in pieces, the shorter whole
+            cap = min(nks[0], nks[1]) if nks[0] != nks[1] else nks[0] - 1
+            two.plan.parts = hybrid.panel_parts(two.plan.panel_ptr, cap, two.plan.xcd_ptr)
+            assert two.plan.parts.num_cuts > 0
+        torch.manual_seed(3)
+        _CACHE[name] = (indptr, indices, two, torch.randn(N, F).half().float())
+    return _CACHE[name]
+
+
+def _step(two, feat, join, monkeypatch):
+    monkeypatch.setenv("VOLTRIX_TWO_LEVEL_JOIN", join)
+    operand, out_scale, padded, _ = _operand(feat)
+    out = torch.full((N, padded), float("nan"), device="cuda")
+    _run_two_level(two, operand, out, out_scale)
+    assert hybrid.LAST_JOIN["mode"] == join, (hybrid.LAST_JOIN["mode"], join)
+    return out
+
+
+@pytest.mark.parametrize("name", ["uncut", "hub", "cut_panel"])
+def test_ticket_join_equals_the_atomic_join(cuda_device, name, monkeypatch):
+    monkeypatch.setenv("VOLTRIX_TUNE_SPACE", "none")
+    indptr, indices, two, feat32 = _case(name)
+    feat = feat32.half().cuda()
+    atomic = _step(two, feat, "atomic", monkeypatch)          # also the call that chooses the window kernel's tile
+    if name == "hub":
+        table = handle_unit_table(two.blk_offsets, two.hspa_packed, N, xcd_ptr=two.window_xcd_ptr)
+        assert table.num_cuts > 0
+    # variant 4, in every graph: window 1 has no residual edge (one all-zero TC block), rows 32..47 no shared column
+    b1, b2 = int(two.blk_offsets[1]), int(two.blk_offsets[2])
+    assert b2 - b1 == 1 and int(two.hspa_packed.view(torch.int32)[4 * b1:4 * b1 + 4].abs().sum()) == 0
+    ticket = _step(two, feat, "ticket", monkeypatch)
+    assert hybrid.join_error_word() == 0
+    assert not torch.isnan(ticket).any()
+    assert torch.equal(ticket, atomic)
+    _assert_close(ticket, indptr, indices, feat32, N, "fp16")
+    for _ in range(10):
+        assert torch.equal(_step(two, feat, "ticket", monkeypatch), ticket)
+        assert hybrid.join_error_word() == 0
+
+
+@pytest.mark.parametrize("units_per_wave", [1, 2])
+@pytest.mark.parametrize("name", ["hub", "cut_panel"])
+def test_both_arrival_orders_on_one_stream(cuda_device, name, units_per_wave):
+    """The low-level launchers on ONE stream with a shared ticket buffer: window kernel then panel kernel (the window kernel stores
+    every block, the panel kernel adds) and panel kernel then window kernel (the other way round) -- the same bits, and the atomic
+    join's.  ``units_per_wave`` 2: the paired window kernel the headline step runs."""
+    indptr, indices, two, feat32 = _case(name)
+    plan, feat = two.plan, feat32.half().cuda()
+    table = handle_unit_table(two.blk_offsets, two.hspa_packed, N, pairs=units_per_wave == 2, xcd_ptr=two.window_xcd_ptr)
+    stream = torch.cuda.current_stream().cuda_stream
+    nnz = plan.num_resid_edges
+
+    def window(out, partials, tickets):
+        assert capi.launch_spmm_sched(two.blk_offsets.data_ptr(), two.hspa_packed.data_ptr(), two.hind.data_ptr(), N, nnz, F,
+                                      feat.data_ptr(), out.data_ptr(), (128, 3, 4), stream, 0, 0, tickets is None, False, table,
+                                      partials.data_ptr(), 0, units_per_wave,
+                                      tickets=tickets.data_ptr() if tickets is not None else 0) == 0
+
+    def step(order):
+        ticketed = order != "atomic"
+        out = torch.full((N, F), float("nan"), device="cuda") if ticketed else torch.zeros(N, F, device="cuda")
+        tickets = hybrid.new_tickets(N, out.device) if ticketed else None
+        partials = torch.empty(max(1, table.num_slots) * 16 * F, device="cuda")
+        pending = None
+        for kernel in (("window", "panel") if order != "panel_first" else ("panel", "window")):
+            if kernel == "window":
+                window(out, partials, tickets)
+            else:
+                pending = hybrid.launch_panel(plan, feat, out, accumulate=3 if ticketed else 2, defer_combine=True, tickets=tickets)
+        assert capi.launch_combine_partials(table, partials.data_ptr(), out.data_ptr(), N, F, True, stream,
+                                            tickets=tickets.data_ptr() if ticketed else 0) == 0
+        if pending is not None:
+            pending.run()
+        if ticketed:
+            words = tickets.cpu()
+            assert int(words[0]) == 0                                              # the error word
+            assert bool((words[hybrid.TICKET_HEADER:hybrid.TICKET_HEADER + (N + 15) // 16] >= 2).all())   # every block was written
+        return out
+
+    atomic, first, second = step("atomic"), step("window_first"), step("panel_first")
+    assert torch.equal(first, second) and torch.equal(first, atomic)
+    _assert_close(first, indptr, indices, feat32, N, "fp16")
+
+
+def test_ineligible_calls_keep_the_atomic_join(cuda_device, monkeypatch):
+    """F = 256 spans two column slabs of both kernels: forced ``ticket`` or not, the step takes the atomic join."""
+    monkeypatch.setenv("VOLTRIX_TUNE_SPACE", "none")
+    monkeypatch.setenv("VOLTRIX_TWO_LEVEL_JOIN", "ticket")
+    indptr, indices, two, _ = _case("uncut")
+    torch.manual_seed(5)
+    feat32 = torch.randn(N, 256).half().float()
+    for _ in range(2):       # the first call chooses the tile, the second knows it: FS = 128 < F either way
+        out = voltrix.spmm_two_level(two, feat32.half().cuda())
+        assert hybrid.LAST_JOIN["mode"] == "atomic" and hybrid.LAST_JOIN["tickets"] is None
+    _assert_close(out, indptr, indices, feat32, N, "fp16")
+    # the decision itself (host only): a row map, an fp32 operand, another slab width on one side, an unknown tile
+    plan, op = two.plan, torch.empty(N, 128, dtype=torch.float16)
+    assert hybrid.join_mode(plan, op, window_fs=128, panel_fs=128, forced="ticket") == "ticket"
+    assert hybrid.join_mode(plan, op, window_fs=128, panel_fs=128, row_map=torch.zeros(1), forced="ticket") == "atomic"
+    assert hybrid.join_mode(plan, op, window_fs=64, panel_fs=128, forced="ticket") == "atomic"
+    assert hybrid.join_mode(plan, op, window_fs=None, panel_fs=128, forced="ticket") == "atomic"
+    assert hybrid.join_mode(plan, op.float(), window_fs=128, panel_fs=128, forced="ticket") == "atomic"
+    assert hybrid.join_mode(plan, op, concurrent=False, window_fs=128, panel_fs=128, forced="ticket") == "add"
+    assert hybrid.join_mode(plan, op, window_fs=128, panel_fs=128, forced="atomic") == "atomic"

@@ -42,6 +42,30 @@ void voltrix_launch_combine_partials(void* cuts, int num_cuts, void* partials, v
                                            static_cast<hipStream_t>(stream), static_cast<const int*>(row_map));
 }
 
+void voltrix_launch_spmm_f16_sched_ticket(void* blk_offsets, void* hspa_packed, void* hind, int num_nodes, int num_edges,
+                                          int embedding_dim, void* input, void* output, int fs, int depth, int waves,
+                                          void* out_scale, void* units, void* unit_ptr, int max_units_per_xcd, void* partials,
+                                          int units_per_wave, void* tickets, void* stream, int* return_code) {
+  (void)num_edges;
+  *return_code = dispatch_spmm<2, _Float16>(fs, depth, waves, static_cast<const int*>(blk_offsets),
+                                            static_cast<const uint32_t*>(hspa_packed), static_cast<const int*>(hind),
+                                            num_nodes, embedding_dim, static_cast<const _Float16*>(input),
+                                            static_cast<float*>(output), static_cast<hipStream_t>(stream), nullptr,
+                                            static_cast<const float*>(out_scale), /*atomic_out=*/2,
+                                            static_cast<const int*>(units), static_cast<const int*>(unit_ptr),
+                                            max_units_per_xcd, static_cast<float*>(partials), nullptr, units_per_wave,
+                                            static_cast<int*>(tickets));
+}
+
+void voltrix_launch_combine_partials_ticket(void* cuts, int num_cuts, void* partials, void* output, int num_nodes,
+                                            int embedding_dim, void* tickets, void* stream, int* return_code) {
+  *return_code = tickets == nullptr
+                     ? voltrix::kErrBadShape
+                     : voltrix::combine_partials(static_cast<const int*>(cuts), num_cuts, static_cast<const float*>(partials),
+                                                 static_cast<float*>(output), num_nodes, embedding_dim, /*accumulate=*/1,
+                                                 static_cast<hipStream_t>(stream), nullptr, static_cast<int*>(tickets));
+}
+
 void voltrix_launch_spmm_f16(void* blk_offsets, void* hspa_packed, void* hind, int num_nodes, int num_edges,
                              int embedding_dim, void* input, void* output, void* stream, int* return_code) {
   const TileId t = default_tile(embedding_dim, true);

@@ -49,6 +49,12 @@ SIGNATURES = {
     "voltrix_launch_spmm_panel_parts_f16": (None, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _RC_P]),
     "voltrix_launch_spmm_panel_parts_bf16": (None, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _RC_P]),
     "voltrix_launch_combine_panel_partials": (None, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _RC_P]),
+    "voltrix_launch_spmm_f16_sched_ticket": (None, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_bf16_sched_ticket": (None, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _RC_P]),
+    "voltrix_launch_combine_partials_ticket": (None, [_P, _I, _P, _P, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_panel_ticket_f16": (None, [_P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_spmm_panel_ticket_bf16": (None, [_P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _P, _RC_P]),
+    "voltrix_launch_combine_panel_partials_ticket": (None, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _RC_P]),
     "voltrix_launch_xcd_ranges_of_work": (None, [_P, _I, _I, _P, _P, _RC_P]),
     "voltrix_launch_xcd_ranges_of_windows": (None, [_P, _I, _I, _P, _P, _RC_P]),
     "voltrix_launch_xcd_ranges_of_panels": (None, [_P, _P, _I, _I, _I, _P, _P, _P, _RC_P]),
@@ -290,13 +296,19 @@ def launch_spmm(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_
 @_timed("spmm")
 def launch_spmm_sched(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_dim, input_ptr, output_ptr, tile,
                       stream, window_order=0, out_scale=0, atomic_out=False, bf16=False, table=None, partials=0,
-                      row_map=0, units_per_wave=1) -> int:
+                      row_map=0, units_per_wave=1, tickets=0) -> int:
     """16-bit operand launch with the schedule / output extensions (include/voltrix_capi.h): ``atomic_out`` = add the
     result onto a pre-zeroed output with float atomics (two-level format without a join pass); ``table`` = a
     ``voltrix.schedule.UnitTable`` (replaces ``window_order``), ``partials`` = device pointer of its partial tiles.
-    Returns the return code."""
+    ``tickets`` = device pointer of the call's ticket buffer: the ticket join (``voltrix_launch_spmm_*_sched_ticket``; no
+    ``window_order``, no ``row_map``, ``atomic_out`` is implied).  Returns the return code."""
     units, unit_ptr, max_units = (table.units.data_ptr(), table.unit_ptr.data_ptr(), table.max_units_per_xcd) if table is not None \
         else (None, None, 0)
+    if tickets:
+        assert not window_order and not row_map, "the ticket join takes neither a window order nor a row map"
+        return _call("voltrix_launch_spmm_bf16_sched_ticket" if bf16 else "voltrix_launch_spmm_f16_sched_ticket", blk_offsets,
+                     hspa_packed, hind, num_nodes, num_edges, embedding_dim, input_ptr, output_ptr, tile[0], tile[1], tile[2],
+                     out_scale, units, unit_ptr, max_units, partials, int(units_per_wave), tickets, stream)
     return _call("voltrix_launch_spmm_bf16_sched" if bf16 else "voltrix_launch_spmm_f16_sched", blk_offsets, hspa_packed, hind,
                  num_nodes, num_edges, embedding_dim, input_ptr, output_ptr, tile[0], tile[1], tile[2], window_order, out_scale,
                  int(atomic_out), units, unit_ptr, max_units, partials, row_map, int(units_per_wave), stream)
@@ -304,8 +316,13 @@ def launch_spmm_sched(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embe
 
 @_timed("combine_partials")
 def launch_combine_partials(table, partials_ptr, output_ptr, num_nodes, embedding_dim, accumulate, stream,
-                            row_map=0) -> int:
-    """Sum the partial tiles of the cut windows of ``table`` (a ``voltrix.schedule.UnitTable``) into the output."""
+                            row_map=0, tickets=0) -> int:
+    """Sum the partial tiles of the cut windows of ``table`` (a ``voltrix.schedule.UnitTable``) into the output.  ``tickets``:
+    the ticket join's buffer -- blocks no kernel wrote are stored, the others added to (``accumulate`` is implied)."""
+    if tickets:
+        assert not row_map
+        return _call("voltrix_launch_combine_partials_ticket", table.cuts.data_ptr(), table.num_cuts, partials_ptr, output_ptr,
+                     num_nodes, embedding_dim, tickets, stream)
     return _call("voltrix_launch_combine_partials", table.cuts.data_ptr(), table.num_cuts, partials_ptr, output_ptr, num_nodes,
                  embedding_dim, int(accumulate), row_map, stream)
 
@@ -444,12 +461,22 @@ def launch_spmm_f32_as_f16(blk_offsets, hspa_packed, hind, num_nodes, num_edges,
 
 @_timed("spmm_panel")
 def launch_spmm_panel(plan, input_ptr, output_ptr, embedding_dim, accumulate, bf16, tile, out_scale, stream,
-                      input_rows: int = 0, slab_policy: int = SLAB_AUTO, partials_ptr: int = 0) -> int:
+                      input_rows: int = 0, slab_policy: int = SLAB_AUTO, partials_ptr: int = 0, tickets: int = 0) -> int:
     """Panel kernel (shared-column half of the two-level format); ``plan`` = voltrix.hybrid.PanelPlan, ``tile`` =
     (fs, depth, ksteps); ``input_rows`` = rows of the dense operand (0: the plan's rows).  A plan with a part table
     (``plan.parts``) goes through ``voltrix_launch_spmm_panel_parts_*`` with ``partials_ptr`` = the call's partial-tile
-    buffer.  Returns the return code."""
+    buffer.  ``accumulate`` = 3 with ``tickets`` = the call's ticket buffer: the ticket join
+    (``voltrix_launch_spmm_panel_ticket_*``).  Returns the return code."""
     panel = (plan.panel_ptr.data_ptr(), plan.panel_cols.data_ptr(), plan.panel_bits.data_ptr())
+    if int(accumulate) == 3:
+        parts, xcd_ptr = getattr(plan, "parts", None), getattr(plan, "xcd_ptr", None)
+        if parts is not None:
+            table = (None, parts.parts.data_ptr(), parts.num_parts, parts.xcd_ptr.data_ptr(), parts.max_parts_per_xcd)
+        else:
+            table = (_opt(plan.panel_order), None, 0, _opt(xcd_ptr), plan.max_panels_per_xcd if xcd_ptr is not None else 0)
+        return _call("voltrix_launch_spmm_panel_ticket_bf16" if bf16 else "voltrix_launch_spmm_panel_ticket_f16", *panel, *table,
+                     partials_ptr, tickets, plan.num_nodes, embedding_dim, input_ptr, input_rows, output_ptr, tile[0], tile[1],
+                     plan.waves, plan.row_blocks, tile[2], slab_policy, out_scale, stream)
     launch = (plan.num_nodes, embedding_dim, input_ptr, input_rows, output_ptr, int(accumulate), tile[0], tile[1], plan.waves,
               plan.row_blocks, tile[2], slab_policy, out_scale, stream)
     parts = getattr(plan, "parts", None)
@@ -462,8 +489,12 @@ def launch_spmm_panel(plan, input_ptr, output_ptr, embedding_dim, accumulate, bf
 
 
 def launch_combine_panel_partials(parts, partials_ptr, output_ptr, num_nodes, embedding_dim, panel_rows, accumulate,
-                                  stream) -> int:
-    """``output (+)= `` the partial tiles of the cut panels, pieces in slot order (``parts`` = voltrix.hybrid.PanelParts)."""
+                                  stream, tickets: int = 0) -> int:
+    """``output (+)= `` the partial tiles of the cut panels, pieces in slot order (``parts`` = voltrix.hybrid.PanelParts).
+    ``tickets``: the ticket join's buffer -- blocks nothing has written yet are stored, the others added to."""
+    if tickets:
+        return _call("voltrix_launch_combine_panel_partials_ticket", parts.cuts.data_ptr(), parts.num_cuts, partials_ptr,
+                     output_ptr, num_nodes, embedding_dim, panel_rows, tickets, stream)
     return _call("voltrix_launch_combine_panel_partials", parts.cuts.data_ptr(), parts.num_cuts, partials_ptr, output_ptr, num_nodes,
                  embedding_dim, panel_rows, int(accumulate), stream)
 

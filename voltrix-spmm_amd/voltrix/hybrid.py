@@ -548,11 +548,58 @@ def side_stream(device) -> "torch.cuda.Stream":
     return _SIDE_STREAMS[key]
 
 
+# ---- how the two kernels of the concurrent step meet in C ------------------------------------------------------------------
+JOIN_MODES = ("atomic", "ticket", "add")
+TICKET_HEADER = 4        # int32 words in front of the tickets (spmm_kernels.hpp kTicketHeader): word 0 = sticky error word
+# The join ``join_mode`` picks where the ticket join applies and VOLTRIX_TWO_LEVEL_JOIN does not say otherwise.  Measured on the
+# headline step, five alternating runs each on one machine (profiles/r07/ticket_join_ab.log): atomic join
+# 1.358-1.374 ms (median 1.364), ticket join 1.319-1.338 ms (median 1.326): 2.8 %, every run below every run of the atomic join.
+DEFAULT_JOIN = "ticket"
+LAST_JOIN = {"mode": None, "tickets": None}   # what the last concurrent step on this process did (tests, status reads)
+
+
+def join_mode(plan: PanelPlan, operand: torch.Tensor, concurrent: bool = True, row_map=None, window_fs: int = None,
+              panel_fs: int = None, binary: bool = True, forced: str = None) -> str:
+    """``"atomic"`` | ``"ticket"`` | ``"add"`` for one two-level step -- THE place that decides it.
+    ``add``     one stream: the window kernel stores, the panel kernel read-add-stores afterwards (``concurrent=False``, or forced).
+    ``atomic``  two streams: C is zero-filled, both kernels add with float atomics.
+    ``ticket``  two streams, no zero fill: per 16-row block the first kernel stores, the second adds (spmm_kernels.hpp).  Only
+                where ALL of these hold: the concurrent two-stream path, a 16-bit binary operand, no ``row_map``, and ONE column
+                slab shared by both kernels -- F <= FS with the same FS on both sides (``window_fs``: the slab width the window
+                kernel's chosen tile has, None while that choice has not been made; ``panel_fs``: the panel tile's).
+    ``forced`` / ``VOLTRIX_TWO_LEVEL_JOIN`` name a mode; ``ticket`` where it does not apply is the atomic join."""
+    want = forced if forced is not None else os.getenv("VOLTRIX_TWO_LEVEL_JOIN", DEFAULT_JOIN)
+    assert want in JOIN_MODES, f"VOLTRIX_TWO_LEVEL_JOIN={want!r}: one of {JOIN_MODES}"
+    if not concurrent or want == "add":
+        return "add"
+    if want != "ticket":
+        return "atomic"
+    f = operand.shape[1]
+    eligible = (binary and row_map is None and operand.dtype in (torch.float16, torch.bfloat16)
+                and window_fs is not None and panel_fs is not None and window_fs == panel_fs and f <= window_fs and f % 8 == 0)
+    return "ticket" if eligible else "atomic"
+
+
+def new_tickets(num_nodes: int, device) -> torch.Tensor:
+    """The ticket buffer of one call, zeroed on the current stream: 4 header words + one ticket per 16-row block, padded to
+    16 bytes (58 KB on the headline graph, against the 119 MB zero fill of C it replaces)."""
+    words = TICKET_HEADER + (num_nodes + 15) // 16
+    return torch.zeros((words + 3) // 4 * 4, dtype=torch.int32, device=device)
+
+
+def join_error_word() -> int:
+    """Status read (one host sync): the sticky error word of the last ticket join of this process -- nonzero when a bounded
+    wait of that call ran out (its result is not to be trusted); 0 otherwise, and when no ticket join has run."""
+    tickets = LAST_JOIN["tickets"]
+    return 0 if tickets is None else int(tickets[0].item())
+
+
 def run_two_level(plan: PanelPlan, operand: torch.Tensor, output: torch.Tensor, run_window, out_scale=None,
-                  tile=None, concurrent: bool = True) -> None:
+                  tile=None, concurrent: bool = True, window_fs: int = None) -> None:
     """``output = A_resid @ operand + A_shared @ operand``.  ``run_window(atomic)`` enqueues the window kernel for the
     residual handle on the current stream; with ``atomic`` it adds onto ``output``, otherwise it stores every row.  It
-    returns None or a ``PendingCombine`` (jit_kernels/spmm.py).
+    returns None or a ``PendingCombine`` (jit_kernels/spmm.py).  A caller whose window kernel is a binary 16-bit launch
+    without a row map passes ``window_fs`` (``join_mode``) and takes ``run_window(True, tickets)`` for the ticket join.
 
     The panel kernel runs on a side stream while the window kernel runs on the caller's stream (the first is
     matrix-core bound, the second gather bound: they overlap on the same CUs).  They meet in C through float atomics: C is
@@ -568,7 +615,9 @@ def run_two_level(plan: PanelPlan, operand: torch.Tensor, output: torch.Tensor, 
     if plan.num_ksteps == 0:
         finish(run_window(False))
         return
-    if not concurrent:
+    panel_tile = tile or default_panel_tile(operand.shape[1], plan.waves, plan.row_blocks)
+    mode = join_mode(plan, operand, concurrent, window_fs=window_fs, panel_fs=panel_tile[0] if panel_tile else None)
+    if mode == "add":
         finish(run_window(False))
         launch_panel(plan, operand, output, accumulate=1, out_scale=out_scale, tile=tile)
         return
@@ -576,16 +625,23 @@ def run_two_level(plan: PanelPlan, operand: torch.Tensor, output: torch.Tensor, 
 
     main = torch.cuda.current_stream()
     side = side_stream(operand.device)
-    with timed_launch("zero_fill", main):
-        output.zero_()
+    tickets = None
+    if mode == "ticket":     # a per-call buffer: calls on different streams share no state
+        with timed_launch("zero_fill", main):        # the step's zero fill, whichever buffer it clears (KernelTimer, bench.py)
+            tickets = new_tickets(plan.num_nodes, operand.device)
+    else:
+        with timed_launch("zero_fill", main):
+            output.zero_()
+    LAST_JOIN["mode"], LAST_JOIN["tickets"] = mode, tickets
     fork = torch.cuda.Event()
     fork.record(main)
-    side.wait_event(fork)                        # operand / out_scale / the zero fill were produced on `main`
-    pending_panel = launch_panel(plan, operand, output, accumulate=2, out_scale=out_scale, tile=tile,
-                                 stream=side.cuda_stream, defer_combine=True)
+    side.wait_event(fork)                        # operand / out_scale / the zero fill (the tickets) were produced on `main`
+    pending_panel = launch_panel(plan, operand, output, accumulate=3 if tickets is not None else 2, out_scale=out_scale,
+                                 tile=tile, stream=side.cuda_stream, defer_combine=True, tickets=tickets)
     join = torch.cuda.Event()
     join.record(side)
-    pending = run_window(True)     # (enqueueing the window kernel first changes nothing: 1.374 vs 1.376 ms, profiles/r04)
+    # (enqueueing the window kernel first changes nothing: 1.374 vs 1.376 ms, profiles/r04)
+    pending = run_window(True, tickets) if tickets is not None else run_window(True)
     main.wait_event(join)
     finish(pending)                              # adds onto rows that now hold the panel kernel's part, complete
     finish(pending_panel)                        # pieces of cut panels, in slot order (both kernels are done with C)
@@ -594,8 +650,9 @@ def run_two_level(plan: PanelPlan, operand: torch.Tensor, output: torch.Tensor, 
 class PendingPanelCombine:
     """The partial tiles of cut panels, still to be added to C (``launch_panel(..., defer_combine=True)``)."""
 
-    def __init__(self, plan, partials, output, num_feats, accumulate):
+    def __init__(self, plan, partials, output, num_feats, accumulate, tickets=None):
         self.plan, self.partials, self.output, self.num_feats, self.accumulate = plan, partials, output, num_feats, accumulate
+        self.tickets = tickets       # ticket join: blocks nothing has written yet are stored, not added to
 
     def run(self, raw_stream: int = None):
         """On the current stream (bracketed for a KernelTimer), or on the raw HIP stream handle given."""
@@ -605,15 +662,17 @@ class PendingPanelCombine:
         with timed_launch("combine_panel_partials", current) if raw_stream is None else contextlib.nullcontext():
             rc = capi.launch_combine_panel_partials(self.plan.parts, self.partials.data_ptr(), self.output.data_ptr(),
                                                     self.plan.num_nodes, self.num_feats, self.plan.panel_rows,
-                                                    self.accumulate, current.cuda_stream if raw_stream is None else raw_stream)
+                                                    self.accumulate, current.cuda_stream if raw_stream is None else raw_stream,
+                                                    tickets=self.tickets.data_ptr() if self.tickets is not None else 0)
         capi.check(rc, "voltrix_launch_combine_panel_partials")
         self.partials = None
 
 
 def launch_panel(plan: PanelPlan, feat: torch.Tensor, output: torch.Tensor, accumulate, out_scale=None,
-                 tile=None, stream=None, slab_policy: int = None, defer_combine: bool = False):
+                 tile=None, stream=None, slab_policy: int = None, defer_combine: bool = False, tickets: torch.Tensor = None):
     """``output (+)= A_shared @ feat`` for fp16 / bfloat16 ``feat`` [*, F] and float32 ``output`` [N, F].
-    ``accumulate``: 0 / False store, 1 / True read-add-store, 2 float atomics (include/voltrix_capi.h).
+    ``accumulate``: 0 / False store, 1 / True read-add-store, 2 float atomics, 3 the ticket join with ``tickets`` = the
+    call's ticket buffer (include/voltrix_capi.h).
     Plans with a part table (``plan.parts``): cut panels leave partial tiles that a combine pass adds to ``output`` in
     fixed order -- right after the launch on the same stream, or, with ``defer_combine``, by the returned
     ``PendingPanelCombine`` (the atomic join runs it after both kernels are done)."""
@@ -635,11 +694,12 @@ def launch_panel(plan: PanelPlan, feat: torch.Tensor, output: torch.Tensor, accu
     rc = capi.launch_spmm_panel(plan, feat.data_ptr(), output.data_ptr(), f, int(accumulate),
                                 feat.dtype == torch.bfloat16, tile, out_scale.data_ptr() if out_scale is not None else 0,
                                 stream, input_rows=feat.shape[0], slab_policy=slab_policy,
-                                partials_ptr=partials.data_ptr() if partials is not None else 0)
+                                partials_ptr=partials.data_ptr() if partials is not None else 0,
+                                tickets=tickets.data_ptr() if tickets is not None else 0)
     capi.check(rc, "voltrix_launch_spmm_panel")
     if partials is None:
         return None
-    pending = PendingPanelCombine(plan, partials, output, f, 1 if int(accumulate) else 0)
+    pending = PendingPanelCombine(plan, partials, output, f, 1 if int(accumulate) else 0, tickets=tickets)
     if defer_combine:
         return pending
     pending.run(None if stream == torch.cuda.current_stream().cuda_stream else stream)

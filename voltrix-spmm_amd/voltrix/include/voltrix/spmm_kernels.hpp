@@ -243,6 +243,110 @@ __device__ __forceinline__ float lds_read_f32(unsigned addr) {
   return v;
 }
 
+template <int I, int N, class Fn>
+__device__ __forceinline__ void static_for(Fn&& fn) {
+  if constexpr (I < N) {
+    fn(std::integral_constant<int, I>{});
+    static_for<I + 1, N>(fn);
+  }
+}
+
+// ----------------------------------------------------------------------------------------------
+// Ticket join of the two-level step (hybrid.py::run_two_level, join mode "ticket"): the window kernel and the panel kernel
+// meet in C without a zero fill.  One int32 ticket per 16-row block of C in a per-call buffer, zeroed at the start of the
+// call: word 0 is a sticky error word, words 1 .. 3 pad the header to 16 bytes, word kTicketHeader + b is block b's ticket.
+// A block has at most two producers, one wave of each kernel.  Each DRAWS old = fetch_add(ticket, 1), and the one that drew 0
+// adds 1 once more when its tile is in memory, so a ticket reads
+//   0     untouched
+//   1     the first producer has drawn and is storing its tile
+//   2     either the first producer's tile is in memory, or the second producer has drawn meanwhile (it drew 1)
+//   3     both have drawn and the first producer's tile is in memory
+// old == 0: the producer STORES its tile with write-through (sc1) 16-byte stores, waits for them (vmcnt(0)) and adds 1 again --
+// no release fence: sc1 stores leave the XCD's L2 on their own.  old == 2: the first producer had published before this
+// draw; add the tile with float atomics, which execute at the memory side, so it needs neither a load of C nor an acquire.
+// old == 1: the first producer is inside its stores, and this draw has already made the ticket 2: poll until it reads 3 (the
+// first producer's publish), then add.  After the kernels a nonzero ticket means "written".  A producer never waits between
+// drawing a 0 and publishing, so the waited-for wave needs nothing from the waiter and the wait cannot deadlock; it is bounded
+// all the same (kTicketPollBound polls), and a bound that expires sets the error word and adds anyway.
+// Two addends per element: the sum is the atomic join's, bit for bit, but for the sign of an exact zero.
+constexpr int kTicketHeader = 4;
+constexpr int kTicketPollBound = 1 << 16;   // polls of >= 0.5 us each: tens of ms, against stores that take microseconds
+
+__device__ __forceinline__ int ticket_claim(int* tickets, int block, int lane) {
+  int old = 0;
+  if (lane == 0)
+    old = __hip_atomic_fetch_add(tickets + kTicketHeader + block, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return __builtin_amdgcn_readfirstlane(old);
+}
+
+// after the LAST sc1 store of the tile: every store of this wave has left for memory before the ticket says so
+__device__ __forceinline__ void ticket_publish(int* tickets, int block, int lane) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (lane == 0) __hip_atomic_fetch_add(tickets + kTicketHeader + block, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ void ticket_wait(int* tickets, int block, int lane) {
+  __builtin_amdgcn_s_setprio(0);   // the waited-for wave may share this SIMD
+  int seen = 2;   // this wave drew 1: the ticket reads 2 until the first producer publishes
+  for (int spin = 0; spin < kTicketPollBound && seen < 3; ++spin) {
+    __builtin_amdgcn_s_sleep(8);
+    int v = 0;
+    if (lane == 0) v = __hip_atomic_load(tickets + kTicketHeader + block, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    seen = __builtin_amdgcn_readfirstlane(v);
+  }
+  if (seen < 3 && lane == 0) __hip_atomic_fetch_or(tickets, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <int OFF>
+__device__ __forceinline__ void lds_write_f32_off(unsigned addr, float v) {
+  asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ float4_t lds_read_f32x4_off(unsigned addr) {
+  float4_t v;  // every component is stored by the caller
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
+  return v;
+}
+// one write-through global_store_dwordx4 (sc1: agent scope), exactly where it is written
+__device__ __forceinline__ void store_f32x4_sc1(float* dst, const float4_t v) {
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
+}
+
+// LDS bytes store_tile_sc1 uses: four rows of FS floats, padded so that the four rows a write instruction touches start 16
+// banks apart
+template <int FS>
+constexpr int ticket_tile_lds_bytes() { return 4 * (FS + 16) * 4; }
+
+// A 16-row x FS-column tile in the MFMA D layout (lane 16 g + R holds rows 4 g + j, j = 0 .. 3, of column 16 s + R in
+// acc[s][j]) -> rows [row0, row0 + 16) of C as whole rows: sc1 stores of 16 bytes per lane, every 128-byte line written by
+// one instruction.  Transposed through `lds` (ticket_tile_lds_bytes<FS>() bytes that only this wave touches), four rows
+// (one j) at a time; LDS instructions of one wave execute in order, so a pass may overwrite what the pass before it read.
+// Wave-uniform control flow only (EXEC all ones at the LDS instructions).  `value(s, j)` = the element to store.
+template <int FS, class Value>
+__device__ __forceinline__ void store_tile_sc1(const Value& value, const unsigned lds, float* const output, const int row0,
+                                               const int num_nodes, const int F, const int lane) {
+  constexpr int SLOTS = FS / 16, STRIDE = FS + 16, LPR = FS / 4;   // lanes per row of 16-byte pieces
+  constexpr int NR = FS >= 64 ? FS / 64 : 1;                       // read / store instructions per pass
+  const unsigned waddr = lds + (unsigned)(((lane >> 4) * STRIDE + (lane & 15)) * 4);
+  static_for<0, 4>([&](auto jc) {
+    constexpr int J = decltype(jc)::value;
+    static_for<0, SLOTS>([&](auto sc) {
+      constexpr int S = decltype(sc)::value;
+      lds_write_f32_off<64 * S>(waddr, value(S, J));
+    });
+    // one 16-byte piece per lane at a time (the panel kernel has its whole 128-register accumulator live here)
+    static_for<0, NR>([&](auto rc) {
+      constexpr int R = decltype(rc)::value;
+      const int idx = R * 64 + lane;                         // piece of the pass: row idx / LPR, columns 4 (idx % LPR) ..
+      const int g = idx / LPR < 4 ? idx / LPR : 3;           // FS = 32: the upper half of the wave has nothing to do
+      const float4_t v = lds_read_f32x4_off<0>(lds + (unsigned)((g * STRIDE + 4 * (idx % LPR)) * 4));
+      wait_lgkmcnt0();
+      const int row = row0 + 4 * (idx / LPR) + J, col = 4 * (idx % LPR);
+      if (idx / LPR < 4 && row < num_nodes && col < F) store_f32x4_sc1(output + ((long long)row * F + col), v);
+    });
+  });
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel: remember per (kernel instantiation,
 // device) that it has been raised (one process may drive several GPUs; a function-local flag would cover the first only).
 template <class Tag = void>
@@ -300,17 +404,13 @@ struct SpmmArgs {
   int meta_nt;                   // 1: bitmap / hind DMAs are non-temporal (set by the launcher when one slab covers F, i.e.
                                  // every metadata byte is read exactly once and should not displace rows of B in L2)
   int atomic_out;                // 1: C += result by float atomics (C pre-zeroed; two-level format: no join pass)
+                                 // 2: ticket join (above): C is NOT pre-zeroed, `tickets` is; the first producer of a 16-row
+                                 //    block stores, the second adds (16-bit binary operand, one column slab, no row_map)
+  int* tickets;                  // atomic_out == 2: the call's ticket buffer, int32 [kTicketHeader + num_windows]
 };
 
 // One wave64 = one (row window, FS-column slab) unit.  EB == 2: fp16 (or bfloat16) operand, v_mfma_f32_16x16x32_f16 (_bf16).
 // EB == 4: fp32 operand, exact products on v_mfma_f32_16x16x4_f32 (k-step m of a stage uses LDS rows 4m + lane/16).
-template <int I, int N, class Fn>
-__device__ __forceinline__ void static_for(Fn&& fn) {
-  if constexpr (I < N) {
-    fn(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(fn);
-  }
-}
 
 // NU = units per wave (1, or 2 = "paired" launch of a unit table with F <= FS): a wave that runs two units takes their
 // stages alternately through ONE ring (stage t of the wave = stage t / 2 of unit t % 2) into two accumulator sets, so twice
@@ -743,9 +843,61 @@ __device__ __forceinline__ void spmm_tc16_body(const SpmmArgs<T>& a) {
   // powers of two: exact (barring overflow / underflow of the result itself)
   const float oscale = ((EB == 2 && !T::WEIGHTED) ? kAScaleInv : 1.0f) * (a.out_scale ? *a.out_scale : 1.0f);
   const int ocol0 = fs0 + (lane & 15);
+  // ticket join: unit p's 16-row block is drawn when it goes to C (slot < 0); -1 = nothing to draw, 0 = store, else add
+  int drawn[NU];
+#pragma unroll
+  for (int p = 0; p < NU; ++p) drawn[p] = -1;
+  if constexpr (EB == 2 && !T::WEIGHTED) {
+    if (a.atomic_out == 2) {   // kernel-uniform; the launcher admits one column slab (fs0 == 0) and no row_map
+      // tile of unit p: stored whole (first producer) ...
+      auto store_unit = [&](auto pc) {
+        constexpr int P = decltype(pc)::value;
+        const bool dead = NU > 1 && nst_u[P] == 0;
+        store_tile_sc1<FS>([&](int s, int j) { return dead ? 0.f : acc[P][s][j] * oscale; }, lds0, a.output, w[P] * kBlkH,
+                           a.num_nodes, F, lane);
+        ticket_publish(a.tickets, w[P], lane);
+      };
+      // ... or added onto the first producer's (the atomic join's instructions)
+      auto add_unit = [&](auto pc) {
+        constexpr int P = decltype(pc)::value;
+        const bool dead = NU > 1 && nst_u[P] == 0;
+        const int orow0 = w[P] * kBlkH + 4 * (lane >> 4);
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+          const int col = ocol0 + 16 * s;
+          if (col < F) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (orow0 + j < a.num_nodes)
+                unsafeAtomicAdd(a.output + ((long long)(orow0 + j) * F + col), dead ? 0.f : acc[P][s][j] * oscale);
+          }
+        }
+      };
+      // both units draw before either writes; a unit that drew 0 is stored before this wave waits for anything, and a unit
+      // that has to wait does so after the other unit's epilogue
+#pragma unroll
+      for (int p = 0; p < NU; ++p)
+        if (present[p] && slot[p] < 0) drawn[p] = ticket_claim(a.tickets, w[p], lane);
+      if (drawn[0] == 0) store_unit(std::integral_constant<int, 0>{});
+      if constexpr (NU == 2) {
+        if (drawn[1] == 0) store_unit(std::integral_constant<int, 1>{});
+        if (drawn[1] >= 2) add_unit(std::integral_constant<int, 1>{});
+      }
+      if (drawn[0] >= 1) {
+        if (drawn[0] == 1) ticket_wait(a.tickets, w[0], lane);
+        add_unit(std::integral_constant<int, 0>{});
+      }
+      if constexpr (NU == 2) {
+        if (drawn[1] == 1) {
+          ticket_wait(a.tickets, w[1], lane);
+          add_unit(std::integral_constant<int, 1>{});
+        }
+      }
+    }
+  }
 #pragma unroll
   for (int p = 0; p < NU; ++p) {
-    if (!present[p]) continue;  // wave-uniform
+    if (!present[p] || drawn[p] >= 0) continue;  // wave-uniform
     // NU == 2: a unit without stages may have seen MFMAs of zero A fragments on rows that are not its own (0 x NaN)
     const bool dead = NU > 1 && nst_u[p] == 0;
     if (slot[p] >= 0) {  // a cut window's partial tile: [16][F] fp32, summed in unit order by combine_partials_kernel
@@ -856,10 +1008,17 @@ inline int launch_spmm_tc16(const int* blk_offsets, const uint32_t* hspa_packed,
                             int slab_first = 0, int slab_count = 0 /* > 0: only the column slabs [slab_first, slab_first + slab_count) of the operand, one launch;
                                                                        0: all of them -- one launch per slab_launch_group() slabs, or one grid over all */,
                             long long input_rows = 0 /* rows of the dense operand (0: num_nodes, a square adjacency) */,
-                            int slab_policy = kSlabAuto) {
-  if (num_nodes < 0 || embedding_dim < 0) return kErrBadShape;
+                            int slab_policy = kSlabAuto,
+                            int* tickets = nullptr /* atomic_out == 2: int32 [kTicketHeader + windows], zeroed for this call */) {
+  if (num_nodes < 0 || embedding_dim < 0 || atomic_out < 0 || atomic_out > 2) return kErrBadShape;
   if (num_nodes == 0 || embedding_dim == 0) return kOk;
   if (embedding_dim % (16 / T::EB) != 0) return kErrBadShape;  // 16-byte row chunks
+  if (atomic_out == 2) {   // ticket join: one column slab of a 16-bit binary operand, rows of C as they are, 16-byte stores
+    if (T::EB != 2 || T::WEIGHTED || tickets == nullptr || row_map != nullptr || embedding_dim > T::FS || embedding_dim % 4 != 0 ||
+        ((uintptr_t)output & 15))
+      return kErrBadShape;
+    static_assert(T::EB != 2 || ticket_tile_lds_bytes<T::FS>() <= T::WAVE_LDS, "the tile transpose uses the wave's own ring");
+  }
   if (((uintptr_t)input & 15) || ((uintptr_t)hspa_packed & 15)) return kErrBadShape;
   SpmmArgs<T> a;
   a.blk_offsets = blk_offsets;
@@ -889,6 +1048,7 @@ inline int launch_spmm_tc16(const int* blk_offsets, const uint32_t* hspa_packed,
   a.window_order = window_order;
   a.out_scale = out_scale;
   a.atomic_out = atomic_out;
+  a.tickets = tickets;
   a.meta_nt = total_slabs == 1;   // several slabs (in one launch or one launch each) read the metadata again: keep it cached
   a.slab_major = slab_major_order(a.num_slabs, T::FS * T::EB);
   a.units = reinterpret_cast<const int4*>(units);
@@ -934,8 +1094,14 @@ static __global__ __launch_bounds__(256) void combine_partials_kernel(const int4
                                                                      const float* __restrict__ partials,
                                                                      float* __restrict__ output, const int num_nodes,
                                                                      const int F, const int accumulate,
-                                                                     const int* __restrict__ row_map) {
+                                                                     const int* __restrict__ row_map,
+                                                                     int* __restrict__ tickets) {
   const int4 c = cuts[blockIdx.x];
+  // ticket join: a block no kernel has written (its panel is cut or has no shared column) is STORED and its ticket set, so
+  // that the panel kernel's combine pass, next on the stream, adds.  Every thread reads the ticket before any thread sets it.
+  const bool fresh = tickets != nullptr && tickets[kTicketHeader + c.x] == 0;
+  if (tickets != nullptr) __syncthreads();
+  if (fresh && threadIdx.x == 0) tickets[kTicketHeader + c.x] = 2;
   const int f4 = F / 4;
   const long long tile4 = (long long)kBlkH * f4;
   const float4* src = reinterpret_cast<const float4*>(partials) + (long long)c.y * tile4;
@@ -967,7 +1133,7 @@ static __global__ __launch_bounds__(256) void combine_partials_kernel(const int4
       sum.w += p.w;
     }
     float4* const dst = reinterpret_cast<float4*>(output + (long long)row * F) + (i % f4);
-    if (accumulate) {
+    if (accumulate && !fresh) {
       const float4 d = *dst;
       sum.x += d.x;
       sum.y += d.y;
@@ -979,12 +1145,15 @@ static __global__ __launch_bounds__(256) void combine_partials_kernel(const int4
 }
 
 inline int combine_partials(const int* cuts, int num_cuts, const float* partials, float* output, int num_nodes,
-                            int embedding_dim, int accumulate, hipStream_t stream, const int* row_map = nullptr) {
+                            int embedding_dim, int accumulate, hipStream_t stream, const int* row_map = nullptr,
+                            int* tickets = nullptr /* ticket join: the call's ticket buffer (then no row_map) */) {
+  if (tickets != nullptr && row_map != nullptr) return kErrBadShape;
   if (num_cuts < 0 || num_nodes < 0 || embedding_dim < 0 || (embedding_dim % 4) != 0) return kErrBadShape;
   if (num_cuts == 0 || num_nodes == 0 || embedding_dim == 0) return kOk;
   if (((uintptr_t)cuts & 15) || ((uintptr_t)partials & 15) || ((uintptr_t)output & 15)) return kErrBadShape;
   hipLaunchKernelGGL(combine_partials_kernel, dim3((unsigned)num_cuts), dim3(256), 0, stream,
-                     reinterpret_cast<const int4*>(cuts), partials, output, num_nodes, embedding_dim, accumulate, row_map);
+                     reinterpret_cast<const int4*>(cuts), partials, output, num_nodes, embedding_dim, accumulate, row_map,
+                     tickets);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

@@ -99,6 +99,9 @@ struct PanelTile {
   static constexpr int BLOCK_LDS = DATA_LDS + META_SLOTS * META_BYTES;
   static_assert(BLOCK_LDS <= 160 * 1024, "LDS per CU");
   static_assert(VM_PER_STEP * (DEPTH - 2) <= 63, "vmcnt is a 6-bit counter on gfx9");
+  // ticket join: after the main loop every wave transposes its tiles through its own 1 / WAVES of the ring
+  static constexpr bool TICKET_OK = DATA_LDS / WAVES >= ticket_tile_lds_bytes<FS>() && (DATA_LDS / WAVES) % 16 == 0;
+  static_assert(TICKET_OK, "a wave's slice of the ring holds four padded rows of the tile");
 };
 
 // Adjacency word -> MFMA A fragment.  Bit p (p = 4 j + r) of the word is column 2 r, bit 16 + p column 2 r + 1 of row
@@ -141,6 +144,9 @@ struct PanelArgs {
   int accumulate;              // 0: C = A_shared * B;  1: C += A_shared * B (C holds the window kernel's part, read-add-store);
                                // 2: C += A_shared * B by float atomics (C pre-zeroed, the window kernel adds its part the
                                //    same way, in any order: two addends per element, so the sum does not depend on it)
+                               // 3: ticket join (spmm_kernels.hpp): C is NOT pre-zeroed; per 16-row block of a whole panel the
+                               //    first producer stores, the second adds; pieces of cut panels go to `partials` as ever
+  int* tickets;                // accumulate == 3: the call's ticket buffer, int32 [kTicketHeader + ceil(num_nodes / 16)]
 };
 
 template <class T>
@@ -512,6 +518,37 @@ static __global__ __launch_bounds__(T::THREADS) void spmm_panel_kernel(const Pan
     return;
   }
   const int prow0 = panel * T::PANEL_ROWS + wave * (RB * 16) + 4 * (lane >> 4);
+  if (a.accumulate == 3) {   // ticket join (kernel-uniform; the launcher admits one column slab): a wave per row block
+    if constexpr (T::TICKET_OK) {
+      __syncthreads();   // every wave has read its last fragments: the ring is free, each wave transposes through its own slice
+      const unsigned tlds = data0 + (unsigned)wave * (unsigned)(T::DATA_LDS / T::WAVES);
+      // the lane id as this path's own value (v_mbcnt): nothing it needs is derived from a register that would have to stay
+      // live across the k-step loop, whose 176 registers are the budget beside the window kernel (tests/test_register_budget.py)
+      const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+      const int prow0 = panel * T::PANEL_ROWS + wave * (RB * 16) + 4 * (lane >> 4), ocol0 = fs0 + (lane & 15);
+      static_for<0, RB>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        const int brow0 = panel * T::PANEL_ROWS + wave * (RB * 16) + 16 * J;
+        if (brow0 >= a.num_nodes) return;   // wave-uniform: the tail panel's blocks past the last row have no ticket
+        const int drawn = ticket_claim(a.tickets, brow0 / 16, lane);
+        if (drawn == 0) {   // first producer: whole rows, then the ticket says so; never waits in between
+          store_tile_sc1<FS>([&](int s, int i) { return acc[J][s][i] * oscale; }, tlds, a.output, brow0, a.num_nodes, F, lane);
+          ticket_publish(a.tickets, brow0 / 16, lane);
+          return;
+        }
+        if (drawn == 1) ticket_wait(a.tickets, brow0 / 16, lane);   // the window kernel's wave is inside its stores
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int row = prow0 + 16 * J + i, col = ocol0 + 16 * s;
+            if (col < F && row < a.num_nodes) unsafeAtomicAdd(a.output + ((long long)row * F + col), acc[J][s][i] * oscale);
+          }
+        }
+      });
+    }
+    return;
+  }
   if (a.accumulate == 2) {
 #pragma unroll
     for (int j = 0; j < RB; ++j) {
@@ -555,9 +592,16 @@ static __global__ __launch_bounds__(T::THREADS) void spmm_panel_kernel(const Pan
 static __global__ __launch_bounds__(256) void combine_panel_partials_kernel(const int* __restrict__ cuts,
                                                                             const float* __restrict__ partials,
                                                                             float* __restrict__ output, int num_nodes, int F,
-                                                                            int panel_rows, int accumulate) {
+                                                                            int panel_rows, int accumulate,
+                                                                            int* __restrict__ tickets) {
   const int4_t cut = *reinterpret_cast<const int4_t*>(cuts + 4 * (long long)blockIdx.x);
   const int panel = cut[0], first = cut[1], pieces = cut[2];
+  // ticket join: a block whose ticket is still 0 was written by no kernel and by no earlier combine pass: store it (and say
+  // so).  Every thread reads the ticket before any thread sets it.
+  const long long block = (long long)panel * (panel_rows / 16) + blockIdx.y;
+  const bool fresh = tickets != nullptr && block * 16 < num_nodes && tickets[kTicketHeader + block] == 0;
+  if (tickets != nullptr) __syncthreads();
+  if (fresh && threadIdx.x == 0) tickets[kTicketHeader + block] = 2;
   const int f4 = F / 4;
   const long long tile = (long long)panel_rows * F;
   for (int e = threadIdx.x; e < 16 * f4; e += 256) {
@@ -568,17 +612,18 @@ static __global__ __launch_bounds__(256) void combine_panel_partials_kernel(cons
     float4_t sum = *reinterpret_cast<const float4_t*>(src);
     for (int j = 1; j < pieces; ++j) sum += *reinterpret_cast<const float4_t*>(src + j * tile);
     float4_t* dst = reinterpret_cast<float4_t*>(output + row * F + c);
-    *dst = accumulate ? *dst + sum : sum;
+    *dst = (accumulate && !fresh) ? *dst + sum : sum;
   }
 }
 
 inline int launch_combine_panel_partials(const int* cuts, int num_cuts, const float* partials, float* output, int num_nodes,
-                                         int embedding_dim, int panel_rows, int accumulate, hipStream_t stream) {
+                                         int embedding_dim, int panel_rows, int accumulate, hipStream_t stream,
+                                         int* tickets = nullptr /* ticket join: the call's ticket buffer */) {
   if (num_cuts < 0 || num_nodes < 0 || embedding_dim < 0 || panel_rows < 16 || panel_rows % 16 != 0) return kErrBadShape;
   if (num_cuts == 0 || num_nodes == 0 || embedding_dim == 0) return kOk;
   if (embedding_dim % 4 != 0 || cuts == nullptr || partials == nullptr || output == nullptr) return kErrBadShape;
   hipLaunchKernelGGL(combine_panel_partials_kernel, dim3((unsigned)num_cuts, (unsigned)(panel_rows / 16)), dim3(256), 0, stream,
-                     cuts, partials, output, num_nodes, embedding_dim, panel_rows, accumulate);
+                     cuts, partials, output, num_nodes, embedding_dim, panel_rows, accumulate, tickets);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 
@@ -593,8 +638,12 @@ inline int launch_spmm_panel(const int* panel_ptr, const int* panel_cols, const 
                              int slab_policy = kSlabAuto, const int* xcd_ptr = nullptr /* device int32[9] */,
                              int max_panels_per_xcd = 0 /* longest range of xcd_ptr (sizes the grid) */,
                              const int* parts = nullptr /* device int32[num_parts][4]: replaces panel_order */, int num_parts = 0,
-                             float* partials = nullptr) {
-  if (num_nodes < 0 || embedding_dim < 0 || accumulate < 0 || accumulate > 2) return kErrBadShape;
+                             float* partials = nullptr,
+                             int* tickets = nullptr /* accumulate == 3: int32 [kTicketHeader + ceil(num_nodes / 16)] */) {
+  if (num_nodes < 0 || embedding_dim < 0 || accumulate < 0 || accumulate > 3) return kErrBadShape;
+  // ticket join: one column slab, whole 16-byte pieces of C's rows
+  if (accumulate == 3 && (tickets == nullptr || embedding_dim > T::FS || embedding_dim % 4 != 0 || ((uintptr_t)output & 15)))
+    return kErrBadShape;
   if (parts != nullptr && num_parts < 1) return kErrBadShape;   // partials: required when any part carries a slot
   if (num_nodes == 0 || embedding_dim == 0) return kOk;
   if (embedding_dim % 8 != 0 || ((uintptr_t)input & 15)) return kErrBadShape;
@@ -620,6 +669,7 @@ inline int launch_spmm_panel(const int* panel_ptr, const int* panel_cols, const 
   }
   a.F = embedding_dim;
   a.accumulate = accumulate;
+  a.tickets = tickets;
   const int total_slabs = (embedding_dim + T::FS - 1) / T::FS;
   if (slab_first < 0 || slab_count < 0 || slab_first + slab_count > total_slabs) return kErrBadShape;
   if (const int group = slab_count == 0 ? slab_launch_group(total_slabs, T::ROW_BYTES,

@@ -486,9 +486,10 @@ class PendingCombine:
     """Partial tiles of cut windows that still have to be summed into the output (``spmm_kernel(..., defer_combine=True)``:
     the two-level step runs the pass after the join with the panel kernel, when the output holds that kernel's part)."""
 
-    def __init__(self, table, partials, output, num_nodes, embedding_dim, accumulate, row_map=None):
+    def __init__(self, table, partials, output, num_nodes, embedding_dim, accumulate, row_map=None, tickets=None):
         self.table, self.partials, self.output, self.row_map = table, partials, output, row_map
         self.num_nodes, self.embedding_dim, self.accumulate = num_nodes, embedding_dim, accumulate
+        self.tickets = tickets       # ticket join: blocks no kernel wrote are stored, not added to
 
     def run(self, stream=None):
         from .. import capi
@@ -496,7 +497,8 @@ class PendingCombine:
         stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
         rc = capi.launch_combine_partials(self.table, self.partials.data_ptr(), self.output.data_ptr(), self.num_nodes,
                                           self.embedding_dim, self.accumulate, stream,
-                                          self.row_map.data_ptr() if self.row_map is not None else 0)
+                                          self.row_map.data_ptr() if self.row_map is not None else 0,
+                                          tickets=self.tickets.data_ptr() if self.tickets is not None else 0)
         capi.check(rc, "voltrix_launch_combine_partials")
 
 
@@ -593,6 +595,82 @@ class _LaunchPlan:
         return None
 
 
+def tuner_keys(hspa_packed, embedding_dim: int, input, beside_panel: bool, weighted: bool = False, row_map: bool = False) -> dict:
+    """The tuner's key of a ``spmm_kernel`` call on this handle and operand."""
+    keys = {
+        "feature_hash": feature_hash(hspa_packed),
+        "embedding_dim": embedding_dim,
+        "dtype": str(input.dtype),
+        "device": torch.cuda.get_device_name(input.device),
+        "two_level": bool(beside_panel),
+        "weighted": weighted,
+    }
+    if row_map:
+        keys["row_map"] = True   # a different space (no stream points): a different choice
+    return keys
+
+
+_AOT_TILES = []
+
+
+def ticket_point(hspa_packed, embedding_dim: int, input, beside_panel: bool):
+    """The point ``spmm_kernel`` has chosen for this handle and operand (plain binary 16-bit call), when ``spmm_kernel_ticket`` can
+    run the same kernel: a tile the ahead-of-time library instantiates, in natural window order or on a unit table.  None
+    otherwise, and while this process has not made the choice (the first ``spmm_kernel`` call makes it).  Host look-ups only."""
+    memo_key = (embedding_dim, input.dtype, bool(beside_panel), getattr(hspa_packed, "hash_tag", None), jit_tuner.generation)
+    memo = getattr(hspa_packed, "_voltrix_ticket_point", None)
+    if memo is not None and memo[0] == memo_key:
+        return memo[1]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")     # an untagged handle: spmm_kernel itself has warned
+        keys = tuner_keys(hspa_packed, embedding_dim, input, beside_panel)
+    if not jit_tuner.is_tuned("spmm_kernel", keys):
+        return None
+    point = jit_tuner.tuned_point("spmm_kernel", keys)
+    if not _AOT_TILES:
+        from .. import capi
+
+        _AOT_TILES.extend(capi.tiles(True))
+    ok = (point.get("SCHED") in (0, SCHED_UNITS, SCHED_PAIRS) and point.get("EB") == 2
+          and (point.get("FS"), point.get("DEPTH"), point.get("WAVES")) in _AOT_TILES)
+    point = dict(point) if ok else None
+    try:
+        hspa_packed._voltrix_ticket_point = (memo_key, point)
+    except AttributeError:
+        pass
+    return point
+
+
+def spmm_kernel_ticket(point, blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_dim, input, output, tickets,
+                       out_scale=None, xcd_ptr=None):
+    """The window kernel of a two-level step in the TICKET join (spmm_kernels.hpp): the kernel of ``point`` (``ticket_point``: the
+    tile and schedule ``spmm_kernel`` runs this handle with) through the library's ``voltrix_launch_spmm_*_sched_ticket``, on the
+    handle's cached unit table.  ``output`` is not zero-filled; ``tickets`` is the call's zeroed ticket buffer, shared with the panel
+    kernel.  Returns the ``PendingCombine`` of the cut windows (to run after the join), or None."""
+    from .. import capi
+
+    sched = point["SCHED"]
+    table = TABLE_SCHEDULES[sched].handle_table(blk_offsets, hspa_packed, hind, num_nodes, xcd_ptr) if sched in TABLE_SCHEDULES else None
+    partials = None
+    if table is not None and table.num_slots > 0:
+        partials = torch.empty(table.num_slots * 16 * embedding_dim, dtype=torch.float32, device=input.device)
+    from ..utils import timed_launch
+
+    stream = _raw_stream(input.device)
+    # a KernelTimer sees this launch under the name it has in the other joins: the operator's window kernel, ``spmm_kernel``
+    # (the wrapper's own ``spmm`` bracket is for callers of the C-ABI launch; not both)
+    with timed_launch("spmm_kernel", stream):
+        rc = capi.launch_spmm_sched.__wrapped__(
+            blk_offsets.data_ptr(), hspa_packed.data_ptr(), hind.data_ptr(), num_nodes, num_edges, embedding_dim, input.data_ptr(),
+            output.data_ptr(), (point["FS"], point["DEPTH"], point["WAVES"]), stream, 0,
+            (out_scale if out_scale is not None else unit_scale(input.device)).data_ptr(), False, input.dtype == torch.bfloat16, table,
+            partials.data_ptr() if partials is not None else 0, 0, 2 if sched == SCHED_PAIRS else 1, tickets=tickets.data_ptr())
+    capi.check(rc, "voltrix_launch_spmm_sched_ticket")
+    if partials is None or table.num_cuts == 0:
+        return None
+    return PendingCombine(table, partials, output, num_nodes, embedding_dim, True, None, tickets=tickets)
+
+
 def spmm_kernel(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_dim, input, output, out_scale=None,
                 atomic_out=False, beside_panel=False, defer_combine=False, row_map=None, values=None, xcd_ptr=None):
     """Extensions over the reference wrapper (all default to its behaviour):
@@ -654,16 +732,7 @@ def spmm_kernel(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_
                        TWO_LEVEL_LDS_BUDGET if beside_panel else None, weighted=values is not None,
                        stream_ok=not atomic_out and row_map is None and (short_windows or tune_space_mode() == "stream"),
                        shallow_ok=short_windows)
-    keys = {
-        "feature_hash": feature_hash(hspa_packed),
-        "embedding_dim": embedding_dim,
-        "dtype": str(input.dtype),
-        "device": torch.cuda.get_device_name(input.device),
-        "two_level": bool(beside_panel),
-        "weighted": values is not None,
-    }
-    if row_map is not None:
-        keys["row_map"] = True   # a different space (no stream points): a different choice
+    keys = tuner_keys(hspa_packed, embedding_dim, input, beside_panel, weighted=values is not None, row_map=row_map is not None)
     # unit tables / partial-tile buffers: before the choice is made, those of every schedule in the space (the sweep runs
     # them all); afterwards only the chosen schedule's
     chosen = jit_tuner.tuned_point("spmm_kernel", keys).get("SCHED") if jit_tuner.is_tuned("spmm_kernel", keys) else None
