@@ -603,12 +603,15 @@ def test_partial_tiles_stale(cuda_device):
 @pytest.mark.parametrize("form", ["pair", "pair one stream", "one launch"])
 def test_two_level(cuda_device, form, monkeypatch):
     """``csr_preprocess_hybrid`` (plan builder, residual handle, XCD ranges; ``one launch``: the stage records) and ``spmm_two_level``: the
-    pair with the atomic join onto the caller's zero fill -- panels in pieces, so panel partials and both combine passes run -- the
+    pair on two streams with whichever join ``hybrid.join_mode`` picks for the run (each run's ``hybrid.LAST_JOIN["mode"]`` goes into
+    the failure message; None: the form has no join) -- panels in pieces, so panel partials and both combine passes run -- the
     one-stream form, and ``spmm_fused_kernel``.  52 columns: padded to 56."""
     monkeypatch.setenv("VOLTRIX_FUSED", "1" if form == "one launch" else "0")
     indptr, indices, n = _form_graph()
     ip, ix = torch.from_numpy(indptr), torch.from_numpy(indices)
     feat = _ints((n, 52), torch.float16, 6)
+
+    joins = []
 
     def call():
         two = voltrix.csr_preprocess_hybrid(ip, ix, n, tau=4)
@@ -616,12 +619,18 @@ def test_two_level(cuda_device, form, monkeypatch):
         if form != "one launch":
             cap = max(1, int(torch.diff(two.plan.panel_ptr).max()) // 3)
             two.plan.parts = hybrid.panel_parts(two.plan.panel_ptr, cap, two.plan.xcd_ptr)
-        return two, voltrix.spmm_two_level(two, feat, concurrent=form != "pair one stream")
+        hybrid.LAST_JOIN["mode"] = None
+        out = voltrix.spmm_two_level(two, feat, concurrent=form != "pair one stream")
+        joins.append(hybrid.LAST_JOIN["mode"])
+        return two, out
 
-    two, out = three_runs(call, f"two-level {form}")
-    assert two.plan.num_ksteps > 0 and two.plan.num_resid_edges > 0
-    assert (two.fused is not None and two.fused.num_records > 0) if form == "one launch" else (two.plan.parts.num_cuts > 0)
-    _assert_exact(out, indptr, indices, feat, n, f"two-level {form}")
+    try:
+        two, out = three_runs(call, f"two-level {form}")
+        assert two.plan.num_ksteps > 0 and two.plan.num_resid_edges > 0
+        assert (two.fused is not None and two.fused.num_records > 0) if form == "one launch" else (two.plan.parts.num_cuts > 0)
+        _assert_exact(out, indptr, indices, feat, n, f"two-level {form}")
+    except AssertionError as error:
+        raise AssertionError(f"{error} [join of each run: {joins}]") from error
 
 
 @pytest.mark.parametrize("dtype,width", [("fp16", 52), ("fp32", 50)])

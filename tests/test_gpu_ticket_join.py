@@ -5,7 +5,8 @@ float atomics.  Two addends per element, so the result is the atomic join's bit 
 difference the protocol allows.  Every case runs on a C pre-filled with NaN (a block nobody stores stays NaN and fails every check),
 is held to the fp64 bound of test_gpu_spmm.py, repeated ten times, and has to leave the sticky error word of its ticket buffer at zero.
 
-Graph: N = 1040 rows = 65 windows; 512-row panels: two full ones and a 16-row tail panel that has no shared column at all.  F = 128
+Graph (the cases of this file; test_gpu_ticket_join_matrix.py and test_gpu_ticket_join_paths.py build it at other row counts and
+panel heights through ``_build``): N = 1040 rows = 65 windows; 512-row panels: two full ones and a 16-row tail panel that has no shared column at all.  F = 128
 fp16, mean degree ~61, half of the edges in a band around the diagonal (+-64, +-96 in the second panel: shared columns at tau = 24),
 half uniform (residual).  Rows 16..31 have no edge (a window without residual edges); rows 32..47 only reach columns nobody else in
 their panel uses (a row block of a panel without a shared column).  ``hub``: row 600 reaches every column, its window is cut into
@@ -23,53 +24,74 @@ from voltrix.spmm.spmm import _operand, _run_two_level
 
 pytestmark = pytest.mark.gpu
 
-N, F, TAU = 1040, 128, 24
+N, F, TAU, TAIL_TAU = 1040, 128, 24, 8
 _CACHE = {}
 
 
-def _graph(hub: bool):
+def _graph(hub: bool, n: int = N, tail: bool = False):
+    """``tail``: the rows of the last (partial) panel all reach columns 960..999, and every other row has 4 uniform edges instead of
+    32, so that at ``TAIL_TAU`` the band and those columns are shared and the uniform edges stay residual."""
     rng = np.random.default_rng(7)
     rows = []
-    for r in range(N):
+    for r in range(n):
         if 16 <= r < 32:
             rows.append(np.zeros(0, np.int64))
             continue
         if 32 <= r < 48:
-            rows.append(np.sort(rng.choice(np.arange(960, N), 8, replace=False)))     # <= 16 < TAU references per column in panel 0
+            rows.append(np.sort(rng.choice(np.arange(960, n), 8, replace=False)))     # <= 16 < TAU references per column in panel 0
             continue
         half = 64 if r < 512 else 96     # the second panel's band is wider: more shared columns, more k-steps than the first
-        band = rng.choice(np.arange(max(0, r - half), min(N, r + half + 1)), 32 if r < 1024 else 16, replace=False)
-        far = rng.choice(900, 32 if r < 1024 else 0, replace=False)     # the tail panel's rows: a short window, not cut
+        band = rng.choice(np.arange(max(0, r - half), min(n, r + half + 1)), 32 if r < 1024 else 16, replace=False)
+        far = rng.choice(900, (4 if tail else 32) if r < 1024 else 0, replace=False)     # the tail panel's rows: a short window, not cut
+        if tail and r >= 1024:
+            band = np.r_[band, np.arange(960, 1000)]     # n - 1024 >= TAIL_TAU references each: the tail panel has k-steps
         rows.append(np.unique(np.r_[band, far]))
     if hub:
-        rows[600] = np.arange(N)         # every column: a window several times the median length, cut into units
-    indptr = np.zeros(N + 1, np.int32)
+        rows[600] = np.arange(n)         # every column: a window several times the median length, cut into units
+    indptr = np.zeros(n + 1, np.int32)
     indptr[1:] = np.cumsum([len(r) for r in rows])
     return indptr, np.concatenate(rows).astype(np.int32)
 
 
-def _case(name):
-    """(indptr, indices, handle, feat32) of a variant, built once and left unchanged."""
-    if name not in _CACHE:
-        indptr, indices = _graph(hub=name != "uncut")     # cut_panel: the hub's cut window lies in the cut panel
-        two = voltrix.csr_preprocess_hybrid(torch.from_numpy(indptr), torch.from_numpy(indices), N, tau=TAU)
-        two.hash_tag = f"ticket_join_{name}"
-        assert two.plan.num_shared_edges > 0 and two.plan.num_resid_edges > 0 and two.plan.num_panels == 3
-        nks = (two.plan.panel_ptr[1:] - two.plan.panel_ptr[:-1]).tolist()
-        assert nks[0] > 0 and nks[1] > 0 and nks[2] == 0          # the 16-row tail panel has no shared column
-        if name == "cut_panel":        # forced through the plan's piece bound: the longer panel in pieces, the shorter whole
-            cap = min(nks[0], nks[1]) if nks[0] != nks[1] else nks[0] - 1
-            two.plan.parts = hybrid.panel_parts(two.plan.panel_ptr, cap, two.plan.xcd_ptr)
-            assert two.plan.parts.num_cuts > 0
+def _build(name, n: int = N, row_blocks: int = 4, tag: str = None):
+    """(indptr, indices, handle) of a variant, a new handle under the tuner tag ``tag``.  ``n``: 1040, or 1033 = 64 * 16 + 9 (the
+    last 16-row block and the tail panel are partial); ``row_blocks``: 4 (512-row panels) or 2 (256-row panels).  Variants: ``uncut``,
+    ``hub``, ``cut_panel`` (module docstring) and ``tail``: the hub graph with few uniform edges at tau = TAIL_TAU, where the tail
+    panel has shared columns of its own, so that the panel kernel is a producer of the last block."""
+    tail = name == "tail"
+    indptr, indices = _graph(hub=name != "uncut", n=n, tail=tail)     # cut_panel: the hub's cut window lies in the cut panel
+    two = voltrix.csr_preprocess_hybrid(torch.from_numpy(indptr), torch.from_numpy(indices), n, row_blocks=row_blocks,
+                                        tau=TAIL_TAU if tail else TAU)
+    two.hash_tag = tag or f"ticket_join_{name}" + ("" if (n, row_blocks) == (N, 4) else f"_{n}_{row_blocks}")
+    panel_rows = 128 * row_blocks
+    assert two.plan.panel_rows == panel_rows and two.plan.num_panels == (n + panel_rows - 1) // panel_rows == 1024 // panel_rows + 1
+    assert two.plan.num_shared_edges > 0 and two.plan.num_resid_edges > 0
+    nks = (two.plan.panel_ptr[1:] - two.plan.panel_ptr[:-1]).tolist()
+    assert all(k > 0 for k in nks[:-1])
+    assert nks[-1] > 0 if tail else nks[-1] == 0       # the tail panel (16 or 9 rows) has a shared column only in ``tail``
+    if name == "cut_panel":        # forced through the plan's piece bound: the hub's (longest) panel in pieces, the shortest whole
+        hub_panel = 600 // panel_rows
+        assert nks[hub_panel] == max(nks)
+        cap = min(nks[:-1]) if min(nks[:-1]) < nks[hub_panel] else nks[hub_panel] - 1
+        two.plan.parts = hybrid.panel_parts(two.plan.panel_ptr, cap, two.plan.xcd_ptr)
+        assert two.plan.parts.num_cuts > 0 and hub_panel in two.plan.parts.cuts[:, 0].tolist()
+    return indptr, indices, two
+
+
+def _case(name, n: int = N, row_blocks: int = 4):
+    """(indptr, indices, handle, feat32) of ``_build``'s variant, built once and left unchanged."""
+    key = (name, n, row_blocks)
+    if key not in _CACHE:
+        built = _build(name, n, row_blocks)
         torch.manual_seed(3)
-        _CACHE[name] = (indptr, indices, two, torch.randn(N, F).half().float())
-    return _CACHE[name]
+        _CACHE[key] = built + (torch.randn(n, F).half().float(),)
+    return _CACHE[key]
 
 
 def _step(two, feat, join, monkeypatch):
     monkeypatch.setenv("VOLTRIX_TWO_LEVEL_JOIN", join)
     operand, out_scale, padded, _ = _operand(feat)
-    out = torch.full((N, padded), float("nan"), device="cuda")
+    out = torch.full((two.num_nodes, padded), float("nan"), device="cuda")
     _run_two_level(two, operand, out, out_scale)
     assert hybrid.LAST_JOIN["mode"] == join, (hybrid.LAST_JOIN["mode"], join)
     return out
