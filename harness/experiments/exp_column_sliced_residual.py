@@ -111,7 +111,7 @@ def main():
         point = [dict(p) for p in jit_tuner.tuned_keys.values()][-1]
 
         def pair():
-            hybrid.run_two_level(two.plan, feat, out, lambda atomic: run_window(atomic, True), concurrent=True)
+            hybrid.run_two_level(two.plan, feat, out, lambda join: run_window(True, True), concurrent=True)   # no window_fs: the atomic join
 
         pair()
         err_pair = float((out - ref).abs().max() / ref.abs().max())

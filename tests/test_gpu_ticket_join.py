@@ -183,3 +183,117 @@ def test_ineligible_calls_keep_the_atomic_join(cuda_device, monkeypatch):
     assert hybrid.join_mode(plan, op.float(), window_fs=128, panel_fs=128, forced="ticket") == "atomic"
     assert hybrid.join_mode(plan, op, concurrent=False, window_fs=128, panel_fs=128, forced="ticket") == "add"
     assert hybrid.join_mode(plan, op, window_fs=128, panel_fs=128, forced="atomic") == "atomic"
+
+
+# ---- the one launch path: ``spmm_kernel(..., tickets=...)`` ---------------------------------------------------------------------------
+def _chosen_kernel(two, feat, monkeypatch):
+    """After a first (atomic) step has made the choice: the residual handle's point, the library tile and unit table it names."""
+    from voltrix.jit_kernels.spmm import SCHED_PAIRS, ticket_point
+
+    _step(two, feat, "atomic", monkeypatch)
+    point = ticket_point(two.hspa_packed, feat.shape[1], feat, True)
+    assert point is not None and point["SCHED"] in (4, SCHED_PAIRS)
+    pairs = point["SCHED"] == SCHED_PAIRS
+    table = handle_unit_table(two.blk_offsets, two.hspa_packed, N, pairs=pairs, xcd_ptr=two.window_xcd_ptr)
+    return point, (point["FS"], point["DEPTH"], point["WAVES"]), table, 2 if pairs else 1
+
+
+def _window_args(two, feat, out):
+    return dict(num_nodes=N, num_edges=two.plan.num_resid_edges, embedding_dim=feat.shape[1], input=feat, output=out,
+                atomic_out=True, beside_panel=True, defer_combine=True, xcd_ptr=two.window_xcd_ptr)
+
+
+@pytest.mark.parametrize("dtype,f", [(torch.float16, 128), (torch.bfloat16, 64)], ids=["fp16-F128", "bf16-F64"])
+@pytest.mark.parametrize("name", ["hub", "uncut"])
+def test_jit_route_equals_the_library_route(cuda_device, name, dtype, f, monkeypatch):
+    """The window kernel ALONE in the ticket join, on a NaN-filled C between sentinel words with fresh tickets: through
+    ``spmm_kernel(..., tickets=...)`` and its pending combine, and through the C-ABI ticket entry points on the same cached table
+    and the chosen point's tile.  Same kernel, so the same bits in C and the same ticket words."""
+    from test_gpu_ticket_join_matrix import _assert_guards_intact, _guarded_nan
+    from voltrix.jit_kernels.spmm import spmm_kernel, unit_scale
+
+    monkeypatch.setenv("VOLTRIX_TUNE_SPACE", "none")
+    indptr, indices, two, feat32 = _case(name)
+    feat = feat32[:, :f].to(dtype).cuda()
+    point, tile, table, units_per_wave = _chosen_kernel(two, feat, monkeypatch)
+    assert (table.num_cuts > 0) == (name == "hub")
+    guard = 16 * point["FS"]
+    stream = torch.cuda.current_stream().cuda_stream
+
+    buf_jit, out_jit = _guarded_nan(N, f, guard)
+    tickets_jit = hybrid.new_tickets(N, feat.device)
+    pending = spmm_kernel(two.blk_offsets, two.hspa_packed, two.hind, tickets=tickets_jit, **_window_args(two, feat, out_jit))
+    assert (pending is not None) == (table.num_cuts > 0)
+    if pending is not None:
+        assert pending.tickets is tickets_jit
+        pending.run()
+
+    buf_lib, out_lib = _guarded_nan(N, f, guard)
+    tickets_lib = hybrid.new_tickets(N, feat.device)
+    partials = torch.empty(max(1, table.num_slots) * 16 * f, device="cuda")
+    assert capi.launch_spmm_sched(two.blk_offsets.data_ptr(), two.hspa_packed.data_ptr(), two.hind.data_ptr(), N,
+                                  two.plan.num_resid_edges, f, feat.data_ptr(), out_lib.data_ptr(), tile, stream, 0,
+                                  unit_scale(feat.device).data_ptr(), False, dtype == torch.bfloat16, table, partials.data_ptr(), 0,
+                                  units_per_wave, tickets=tickets_lib.data_ptr()) == 0
+    accumulate, _ = hybrid.Join("ticket", tickets_lib).combine
+    assert capi.launch_combine_partials(table, partials.data_ptr(), out_lib.data_ptr(), N, f, accumulate, stream,
+                                        tickets=tickets_lib.data_ptr()) == 0
+    torch.cuda.synchronize()
+    assert not torch.isnan(out_jit).any() and not torch.isnan(out_lib).any()
+    assert torch.equal(out_jit, out_lib)
+    assert torch.equal(tickets_jit, tickets_lib) and int(tickets_jit[0]) == 0
+    _assert_guards_intact(buf_jit, out_jit, guard, "JIT route")
+    _assert_guards_intact(buf_lib, out_lib, guard, "library route")
+
+
+def test_repeated_ticket_step_uses_the_launch_plan(cuda_device, monkeypatch):
+    """The first ticket step of a handle leaves a launch plan whose key carries the ticket code; the next one runs from that plan with
+    a ticket tensor of its own -- the same bits, and the first call's tickets are not written again."""
+    monkeypatch.setenv("VOLTRIX_TUNE_SPACE", "none")
+    indptr, indices, two, feat32 = _case("hub")
+    feat = feat32.half().cuda()
+    _step(two, feat, "atomic", monkeypatch)
+    first = _step(two, feat, "ticket", monkeypatch)
+    tickets_first = hybrid.LAST_JOIN["tickets"]
+    torch.cuda.synchronize()
+    kept = tickets_first.clone()
+    plans = two.hspa_packed._voltrix_plans
+    ticket_plans = {key: plan for key, plan in plans.items() if key[6] == hybrid.WINDOW_TICKET and key[3] == F}
+    assert len(ticket_plans) == 1
+    second = _step(two, feat, "ticket", monkeypatch)
+    tickets_second = hybrid.LAST_JOIN["tickets"]
+    torch.cuda.synchronize()
+    assert tickets_second is not tickets_first and tickets_second.data_ptr() != tickets_first.data_ptr()
+    assert all(plans[key] is plan for key, plan in ticket_plans.items())        # launched from the plan, not rebuilt
+    assert torch.equal(second, first) and not torch.isnan(second).any()
+    assert torch.equal(tickets_first, kept) and torch.equal(tickets_second, kept)
+    assert hybrid.join_error_word() == 0
+
+
+def test_spmm_kernel_refuses_tickets_it_cannot_serve(cuda_device, monkeypatch):
+    """A ticket buffer serves one launch: no ticket call before this process has chosen the kernel (it would sweep), none with a
+    ``row_map``.  Nothing is launched: C and the tickets stay as they were."""
+    from test_gpu_views import SENTINEL
+    from voltrix.jit_kernels.spmm import spmm_kernel
+
+    monkeypatch.setenv("VOLTRIX_TUNE_SPACE", "none")
+    feat = _case("uncut")[3].half().cuda()
+    out = torch.empty(N, F, device="cuda")
+    out.view(torch.int32).fill_(SENTINEL)
+    tickets = hybrid.new_tickets(N, feat.device)
+
+    def assert_untouched():
+        torch.cuda.synchronize()
+        assert bool((out.view(torch.int32) == SENTINEL).all()) and not tickets.any()
+
+    fresh = _build("uncut", tag="ticket_join_untuned")[2]
+    fresh.hspa_packed.hash_tag = "ticket_join_untuned/residual"
+    with pytest.raises(AssertionError):
+        spmm_kernel(fresh.blk_offsets, fresh.hspa_packed, fresh.hind, tickets=tickets, **_window_args(fresh, feat, out))
+    assert_untouched()
+    two = _case("uncut")[2]
+    _step(two, feat, "atomic", monkeypatch)           # chosen now
+    row_map = torch.arange(16 * ((N + 15) // 16), dtype=torch.int32, device="cuda")
+    with pytest.raises(AssertionError):
+        spmm_kernel(two.blk_offsets, two.hspa_packed, two.hind, tickets=tickets, row_map=row_map, **_window_args(two, feat, out))
+    assert_untouched()

@@ -1,5 +1,7 @@
 """CPU: host-side logic of the product package -- operator-API assertions, tile space, tuner key, synthetic graph
 generators, roofline accounting, row-window sharding."""
+import dataclasses
+
 import numpy as np
 import pytest
 import torch
@@ -110,7 +112,7 @@ def test_remap_columns_addresses_the_padded_gather_buffer():
 def test_launch_plan_keeps_every_table_argument_alive():
     """A cached launch plan holds the ADDRESSES of its whole argument list: it keeps alive every tensor argument but the
     operands and partial tiles every call passes anew and ``hspa_packed`` (the plan lives on it) -- also one added later."""
-    per_call = {"input", "output", "out_scale", "values", "partials", "partials_p", "partials_s", "hspa_packed"}
+    per_call = {"input", "output", "out_scale", "values", "tickets", "partials", "partials_p", "partials_s", "hspa_packed"}
     defs = spmm_mod.arg_defs_for(torch.float16) + (("new_table", torch.int32),)
     named = {name: torch.zeros(1, dtype=t) if isinstance(t, torch.dtype) else 0 for name, t in defs}
     kept = {id(t) for t in spmm_mod.plan_keepalive(named)}
@@ -260,3 +262,28 @@ def test_tile_matrix_graphs_are_adversarial():
     assert 2 <= nblk.mean() <= 6
     win_edges = np.add.reduceat(np.diff(indptr), np.arange(0, n, 16))
     assert np.array_equal(np.nonzero(win_edges == 0)[0], [600, 601, 602])   # one run of three, in the middle
+
+
+def test_join_names_the_codes_of_both_launchers():
+    """``hybrid.Join``: one value per two-level step; the window kernel's ``atomic_out`` (spmm_kernels.hpp) and the panel kernel's
+    ``accumulate`` (spmm_panel_kernels.hpp) are different encodings of the same three joins."""
+    from voltrix import hybrid
+
+    tickets = torch.zeros(8, dtype=torch.int32)
+    want = {"add": (0, 1, (0, None)), "atomic": (1, 2, (1, None)), "ticket": (2, 3, (1, tickets))}
+    assert set(want) == set(hybrid.JOIN_MODES)
+    for mode, (window, panel, combine) in want.items():
+        join = hybrid.Join(mode, tickets if mode == "ticket" else None)
+        assert (join.window_out, join.panel_accumulate) == (window, panel), mode
+        assert join.combine[0] == combine[0] and join.combine[1] is combine[1], mode
+    assert (hybrid.WINDOW_STORE, hybrid.WINDOW_ATOMIC, hybrid.WINDOW_TICKET) == (0, 1, 2)
+    assert (hybrid.PANEL_STORE, hybrid.PANEL_ADD, hybrid.PANEL_ATOMIC, hybrid.PANEL_TICKET) == (0, 1, 2, 3)
+    with pytest.raises(AssertionError):
+        hybrid.Join("ticket")                  # the ticket join without tickets
+    for mode in ("add", "atomic"):
+        with pytest.raises(AssertionError):
+            hybrid.Join(mode, tickets)         # tickets nobody would read
+    with pytest.raises(AssertionError):
+        hybrid.Join("store")
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        hybrid.Join("add").mode = "atomic"

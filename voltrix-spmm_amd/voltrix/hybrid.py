@@ -556,6 +556,27 @@ TICKET_HEADER = 4        # int32 words in front of the tickets (spmm_kernels.hpp
 # 1.358-1.374 ms (median 1.364), ticket join 1.319-1.338 ms (median 1.326): 2.8 %, every run below every run of the atomic join.
 DEFAULT_JOIN = "ticket"
 LAST_JOIN = {"mode": None, "tickets": None}   # what the last concurrent step on this process did (tests, status reads)
+# the window kernel's ``atomic_out`` (spmm_kernels.hpp, SpmmArgs::atomic_out) ...
+WINDOW_STORE, WINDOW_ATOMIC, WINDOW_TICKET = 0, 1, 2
+# ... and the panel kernel's ``accumulate`` (spmm_panel_kernels.hpp, PanelArgs::accumulate)
+PANEL_STORE, PANEL_ADD, PANEL_ATOMIC, PANEL_TICKET = 0, 1, 2, 3
+_JOIN_CODES = {"add": (WINDOW_STORE, PANEL_ADD), "atomic": (WINDOW_ATOMIC, PANEL_ATOMIC), "ticket": (WINDOW_TICKET, PANEL_TICKET)}
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class Join:
+    """How the two kernels of ONE two-level step meet in C: the mode (``join_mode``) and, in the ticket join, the call's tickets."""
+    mode: str                        # "add" | "atomic" | "ticket"
+    tickets: torch.Tensor = None     # ``new_tickets`` of this call (ticket join), else None
+
+    def __post_init__(self):
+        assert self.mode in JOIN_MODES and (self.tickets is not None) == (self.mode == "ticket"), (self.mode, self.tickets)
+
+    window_out = property(lambda self: _JOIN_CODES[self.mode][0])            # the window kernel's ``atomic_out``
+    panel_accumulate = property(lambda self: _JOIN_CODES[self.mode][1])      # the panel kernel's ``accumulate``
+    # (accumulate, tickets) of the window side's combine pass: it stores after a window kernel that stored, else adds onto what the
+    # kernels left in C (ticket join: a block nobody wrote is stored); the panel side's pass always adds
+    combine = property(lambda self: (int(self.mode != "add"), self.tickets))
 
 
 def join_mode(plan: PanelPlan, operand: torch.Tensor, concurrent: bool = True, row_map=None, window_fs: int = None,
@@ -596,53 +617,52 @@ def join_error_word() -> int:
 
 def run_two_level(plan: PanelPlan, operand: torch.Tensor, output: torch.Tensor, run_window, out_scale=None,
                   tile=None, concurrent: bool = True, window_fs: int = None) -> None:
-    """``output = A_resid @ operand + A_shared @ operand``.  ``run_window(atomic)`` enqueues the window kernel for the
-    residual handle on the current stream; with ``atomic`` it adds onto ``output``, otherwise it stores every row.  It
-    returns None or a ``PendingCombine`` (jit_kernels/spmm.py).  A caller whose window kernel is a binary 16-bit launch
-    without a row map passes ``window_fs`` (``join_mode``) and takes ``run_window(True, tickets)`` for the ticket join.
+    """``output = A_resid @ operand + A_shared @ operand``.  ``run_window(join)`` enqueues the window kernel for the residual
+    handle on the current stream as the :class:`Join` says (``join.window_out``: store every row, add with float atomics, or the
+    ticket join on ``join.tickets``) and returns None or a ``PendingCombine`` (jit_kernels/spmm.py).  Only a caller whose window
+    kernel is a binary 16-bit launch without a row map passes ``window_fs`` (``join_mode``) and can get the ticket join.
 
-    The panel kernel runs on a side stream while the window kernel runs on the caller's stream (the first is
-    matrix-core bound, the second gather bound: they overlap on the same CUs).  They meet in C through float atomics: C is
-    zero-filled, both kernels ADD their part -- two addends per element onto a zero, so the sum does not depend on who comes
-    first -- and the partial tiles of cut windows are added by the combine pass after the join (C then holds the panel's part,
-    complete).  Stream-ordered, no host sync; capturable (fork / join through events).  ``concurrent=False``: one stream, the
-    window kernel stores, the panel kernel adds onto it afterwards (read-add-store) -- for callers that cannot spare a second
-    stream; slower, same result up to fp32 summation order."""
+    The panel kernel runs on a side stream while the window kernel runs on the caller's stream (the first is matrix-core bound,
+    the second gather bound: they overlap on the same CUs).  Atomic join: C is zero-filled, both kernels ADD their part with float
+    atomics -- two addends per element onto a zero, so the sum does not depend on who comes first.  Ticket join: the call's tickets
+    are zero-filled instead; per 16-row block the first kernel stores, the second adds.  The partial tiles of cut windows are added
+    by the combine pass after the join (C then holds the panel's part, complete).  Stream-ordered, no host sync; capturable (fork /
+    join through events).  ``concurrent=False``: one stream, the window kernel stores, the panel kernel adds onto it afterwards
+    (read-add-store) -- for callers that cannot spare a second stream; slower, same result up to fp32 summation order."""
     def finish(pending):
         if pending is not None:      # cut windows of a unit-table schedule: sum their partial tiles (fixed order)
             pending.run()
 
     if plan.num_ksteps == 0:
-        finish(run_window(False))
+        finish(run_window(Join("add")))
         return
     panel_tile = tile or default_panel_tile(operand.shape[1], plan.waves, plan.row_blocks)
     mode = join_mode(plan, operand, concurrent, window_fs=window_fs, panel_fs=panel_tile[0] if panel_tile else None)
     if mode == "add":
-        finish(run_window(False))
-        launch_panel(plan, operand, output, accumulate=1, out_scale=out_scale, tile=tile)
+        join = Join(mode)
+        finish(run_window(join))
+        launch_panel(plan, operand, output, accumulate=join.panel_accumulate, out_scale=out_scale, tile=tile)
         return
     from .utils import timed_launch
 
     main = torch.cuda.current_stream()
     side = side_stream(operand.device)
-    tickets = None
-    if mode == "ticket":     # a per-call buffer: calls on different streams share no state
-        with timed_launch("zero_fill", main):        # the step's zero fill, whichever buffer it clears (KernelTimer, bench.py)
-            tickets = new_tickets(plan.num_nodes, operand.device)
-    else:
-        with timed_launch("zero_fill", main):
+    with timed_launch("zero_fill", main):        # the step's zero fill, whichever buffer it clears (KernelTimer, bench.py)
+        # tickets: a per-call buffer, calls on different streams share no state
+        join = Join(mode, new_tickets(plan.num_nodes, operand.device) if mode == "ticket" else None)
+        if join.tickets is None:
             output.zero_()
-    LAST_JOIN["mode"], LAST_JOIN["tickets"] = mode, tickets
+    LAST_JOIN["mode"], LAST_JOIN["tickets"] = join.mode, join.tickets
     fork = torch.cuda.Event()
     fork.record(main)
     side.wait_event(fork)                        # operand / out_scale / the zero fill (the tickets) were produced on `main`
-    pending_panel = launch_panel(plan, operand, output, accumulate=3 if tickets is not None else 2, out_scale=out_scale,
-                                 tile=tile, stream=side.cuda_stream, defer_combine=True, tickets=tickets)
-    join = torch.cuda.Event()
-    join.record(side)
+    pending_panel = launch_panel(plan, operand, output, accumulate=join.panel_accumulate, out_scale=out_scale, tile=tile,
+                                 stream=side.cuda_stream, defer_combine=True, tickets=join.tickets)
+    joined = torch.cuda.Event()
+    joined.record(side)
     # (enqueueing the window kernel first changes nothing: 1.374 vs 1.376 ms, profiles/r04)
-    pending = run_window(True, tickets) if tickets is not None else run_window(True)
-    main.wait_event(join)
+    pending = run_window(join)
+    main.wait_event(joined)
     finish(pending)                              # adds onto rows that now hold the panel kernel's part, complete
     finish(pending_panel)                        # pieces of cut panels, in slot order (both kernels are done with C)
 
@@ -671,8 +691,8 @@ class PendingPanelCombine:
 def launch_panel(plan: PanelPlan, feat: torch.Tensor, output: torch.Tensor, accumulate, out_scale=None,
                  tile=None, stream=None, slab_policy: int = None, defer_combine: bool = False, tickets: torch.Tensor = None):
     """``output (+)= A_shared @ feat`` for fp16 / bfloat16 ``feat`` [*, F] and float32 ``output`` [N, F].
-    ``accumulate``: 0 / False store, 1 / True read-add-store, 2 float atomics, 3 the ticket join with ``tickets`` = the
-    call's ticket buffer (include/voltrix_capi.h).
+    ``accumulate``: PANEL_STORE / False, PANEL_ADD / True (read-add-store), PANEL_ATOMIC (float atomics) or PANEL_TICKET (the ticket
+    join, with ``tickets`` = the call's ticket buffer); a ``Join`` names it as ``panel_accumulate``.
     Plans with a part table (``plan.parts``): cut panels leave partial tiles that a combine pass adds to ``output`` in
     fixed order -- right after the launch on the same stream, or, with ``defer_combine``, by the returned
     ``PendingPanelCombine`` (the atomic join runs it after both kernels are done)."""
@@ -699,7 +719,7 @@ def launch_panel(plan: PanelPlan, feat: torch.Tensor, output: torch.Tensor, accu
     capi.check(rc, "voltrix_launch_spmm_panel")
     if partials is None:
         return None
-    pending = PendingPanelCombine(plan, partials, output, f, 1 if int(accumulate) else 0, tickets=tickets)
+    pending = PendingPanelCombine(plan, partials, output, f, int(int(accumulate) != PANEL_STORE), tickets=tickets)
     if defer_combine:
         return pending
     pending.run(None if stream == torch.cuda.current_stream().cuda_stream else stream)

@@ -57,13 +57,13 @@ __return_code = voltrix::launch_spmm_tc16<voltrix::SpmmTile<{FS}, {DEPTH}, {WAVE
     {SCHED} == 4 ? units : ({SCHED} == 5 ? units_p : nullptr), {SCHED} == 5 ? unit_ptr_p : unit_ptr,
     {SCHED} == 5 ? max_units_per_xcd_p : max_units_per_xcd, {SCHED} == 5 ? partials_p : partials,
     has_row_map != 0 ? row_map : nullptr, {WEIGHTED} != 0 ? (const void*)values : nullptr, {SCHED} == 5 ? 2 : 1,
-    0, 0, input_rows, slab_policy);
+    0, 0, input_rows, slab_policy, atomic_out == 2 ? tickets : nullptr);
 if (__return_code == 0 && {SCHED} == 4 && combine_now != 0)
   __return_code = voltrix::combine_partials(cuts, num_cuts, partials, output, num_nodes, embedding_dim, atomic_out, stream,
-                                            has_row_map != 0 ? row_map : nullptr);
+                                            has_row_map != 0 ? row_map : nullptr, atomic_out == 2 ? tickets : nullptr);
 if (__return_code == 0 && {SCHED} == 5 && combine_now != 0)
   __return_code = voltrix::combine_partials(cuts_p, num_cuts_p, partials_p, output, num_nodes, embedding_dim, atomic_out,
-                                            stream, has_row_map != 0 ? row_map : nullptr);
+                                            stream, has_row_map != 0 ? row_map : nullptr, atomic_out == 2 ? tickets : nullptr);
 """
 
 # windows per length-sorted chunk of the "balance" schedule (spmm_kernels.hpp::launch_window_order) for SCHED 1/2/3.
@@ -393,6 +393,7 @@ def arg_defs_for(dtype):
         ("values", dtype),
         ("input_rows", int),
         ("slab_policy", int),
+        ("tickets", torch.int32),
         ("s_units", torch.int32),
         ("s_runs", torch.int32),
         ("s_run_ptr", torch.int32),
@@ -553,7 +554,7 @@ def _pack(arg_defs, named):
     return tuple(named[name] for name in names)
 
 
-_NOT_KEPT = frozenset(("input", "output", "out_scale", "values", "hspa_packed") + tuple(s.partials for s in TABLE_SCHEDULES.values()))
+_NOT_KEPT = frozenset(("input", "output", "out_scale", "values", "tickets", "hspa_packed")) | {s.partials for s in TABLE_SCHEDULES.values()}
 
 
 def plan_keepalive(named) -> tuple:
@@ -566,20 +567,22 @@ def plan_keepalive(named) -> tuple:
 class _LaunchPlan:
     """Everything of a ``spmm_kernel`` call that does not change between calls on one handle -- the chosen kernel's entry point,
     its argument list already marshalled to ctypes, which partial-tile buffer the schedule needs, what ``defer_combine`` returns --
-    so that a repeated call patches five pointers and launches (round 5: the wrapper cost 57 us of host time per call, more than
-    the kernel on the small graphs of the reference's evaluation set: ppi, ddi, FraudYelp).  Kept on the ``hspa_packed`` tensor
-    OBJECT (it dies with it; a copy of the tensor starts without plans)."""
+    so that a repeated call patches five pointers (six with tickets) and launches (round 5: the wrapper cost 57 us of host time per
+    call, more than the kernel on the small graphs of the reference's evaluation set: ppi, ddi, FraudYelp).  Kept on the
+    ``hspa_packed`` tensor OBJECT (it dies with it; a copy of the tensor starts without plans)."""
     __slots__ = ("fn", "cargs", "generation", "operand_index", "partials_index", "partials_floats", "combine_table", "combine_args",
                  "device", "keepalive")
-    PATCHED = ("input", "output", "out_scale", "values", "stream")   # operand_index: positions of these in ``cargs``
+    PATCHED = ("input", "output", "out_scale", "values", "tickets", "stream")   # operand_index: positions of these in ``cargs``
 
-    def launch(self, input, output, out_scale, values, defer_combine):
-        i_input, i_output, i_scale, i_values, i_stream = self.operand_index
+    def launch(self, input, output, out_scale, values, tickets, defer_combine):
+        i_input, i_output, i_scale, i_values, i_tickets, i_stream = self.operand_index
         cargs = list(self.cargs)
         cargs[i_input] = ctypes.c_void_p(input.data_ptr())
         cargs[i_output] = ctypes.c_void_p(output.data_ptr())
         cargs[i_scale] = ctypes.c_void_p(out_scale.data_ptr())
         cargs[i_values] = ctypes.c_void_p((values if values is not None else input).data_ptr())
+        if tickets is not None:      # else: the placeholder the plan was built with
+            cargs[i_tickets] = ctypes.c_void_p(tickets.data_ptr())
         partials = None
         if self.partials_index is not None:
             partials = torch.empty(self.partials_floats, dtype=torch.float32, device=input.device)
@@ -589,7 +592,7 @@ class _LaunchPlan:
         self.fn(*cargs, ctypes.byref(rc))
         assert rc.value == 0, f"spmm_kernel failed with return code {rc.value}"
         if self.combine_table is not None:
-            pending = PendingCombine(self.combine_table, partials, output, *self.combine_args)
+            pending = PendingCombine(self.combine_table, partials, output, *self.combine_args, tickets=tickets)
             if defer_combine:
                 return pending
         return None
@@ -614,8 +617,8 @@ _AOT_TILES = []
 
 
 def ticket_point(hspa_packed, embedding_dim: int, input, beside_panel: bool):
-    """The point ``spmm_kernel`` has chosen for this handle and operand (plain binary 16-bit call), when ``spmm_kernel_ticket`` can
-    run the same kernel: a tile the ahead-of-time library instantiates, in natural window order or on a unit table.  None
+    """The point ``spmm_kernel`` has chosen for this handle and operand (plain binary 16-bit call), when the ticket join can run
+    that kernel: a tile the ahead-of-time library instantiates as well, in natural window order or on a unit table.  None
     otherwise, and while this process has not made the choice (the first ``spmm_kernel`` call makes it).  Host look-ups only."""
     memo_key = (embedding_dim, input.dtype, bool(beside_panel), getattr(hspa_packed, "hash_tag", None), jit_tuner.generation)
     memo = getattr(hspa_packed, "_voltrix_ticket_point", None)
@@ -641,38 +644,8 @@ def ticket_point(hspa_packed, embedding_dim: int, input, beside_panel: bool):
     return point
 
 
-def spmm_kernel_ticket(point, blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_dim, input, output, tickets,
-                       out_scale=None, xcd_ptr=None):
-    """The window kernel of a two-level step in the TICKET join (spmm_kernels.hpp): the kernel of ``point`` (``ticket_point``: the
-    tile and schedule ``spmm_kernel`` runs this handle with) through the library's ``voltrix_launch_spmm_*_sched_ticket``, on the
-    handle's cached unit table.  ``output`` is not zero-filled; ``tickets`` is the call's zeroed ticket buffer, shared with the panel
-    kernel.  Returns the ``PendingCombine`` of the cut windows (to run after the join), or None."""
-    from .. import capi
-
-    sched = point["SCHED"]
-    table = TABLE_SCHEDULES[sched].handle_table(blk_offsets, hspa_packed, hind, num_nodes, xcd_ptr) if sched in TABLE_SCHEDULES else None
-    partials = None
-    if table is not None and table.num_slots > 0:
-        partials = torch.empty(table.num_slots * 16 * embedding_dim, dtype=torch.float32, device=input.device)
-    from ..utils import timed_launch
-
-    stream = _raw_stream(input.device)
-    # a KernelTimer sees this launch under the name it has in the other joins: the operator's window kernel, ``spmm_kernel``
-    # (the wrapper's own ``spmm`` bracket is for callers of the C-ABI launch; not both)
-    with timed_launch("spmm_kernel", stream):
-        rc = capi.launch_spmm_sched.__wrapped__(
-            blk_offsets.data_ptr(), hspa_packed.data_ptr(), hind.data_ptr(), num_nodes, num_edges, embedding_dim, input.data_ptr(),
-            output.data_ptr(), (point["FS"], point["DEPTH"], point["WAVES"]), stream, 0,
-            (out_scale if out_scale is not None else unit_scale(input.device)).data_ptr(), False, input.dtype == torch.bfloat16, table,
-            partials.data_ptr() if partials is not None else 0, 0, 2 if sched == SCHED_PAIRS else 1, tickets=tickets.data_ptr())
-    capi.check(rc, "voltrix_launch_spmm_sched_ticket")
-    if partials is None or table.num_cuts == 0:
-        return None
-    return PendingCombine(table, partials, output, num_nodes, embedding_dim, True, None, tickets=tickets)
-
-
 def spmm_kernel(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_dim, input, output, out_scale=None,
-                atomic_out=False, beside_panel=False, defer_combine=False, row_map=None, values=None, xcd_ptr=None):
+                atomic_out=False, beside_panel=False, defer_combine=False, row_map=None, values=None, xcd_ptr=None, tickets=None):
     """Extensions over the reference wrapper (all default to its behaviour):
     ``out_scale``      float32 device tensor whose first element multiplies every output element (the power-of-two
                        written by ``capi.launch_cast_f32_f16_scaled``); default 1.
@@ -690,11 +663,16 @@ def spmm_kernel(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_
                        replaces the bitmaps as the A operand.
     ``xcd_ptr``        int32 [9] device tensor: first window of every XCD's range for the unit-table schedules (the two-level
                        step passes the panel kernel's ranges); default: ranges of equal stages.
+    ``tickets``        the call's zeroed ticket buffer (``hybrid.new_tickets``), shared with the panel kernel: the TICKET join
+                       (spmm_kernels.hpp) instead of float atomics -- ``output`` is not zero-filled; the combine pass of cut windows
+                       (now or deferred) takes the tickets too.  With ``atomic_out``, a 16-bit binary operand, no ``row_map``, and only
+                       once this process has chosen the kernel (``ticket_point``): a ticket buffer serves ONE launch, a sweep makes many.
     """
     # ---- repeated call on this handle: the plan of the first one (same kernel, same tables, same bits) ----------------------
     from ..utils import KernelTimer
 
-    plan_key = (blk_offsets.data_ptr(), hind.data_ptr(), num_nodes, embedding_dim, input.dtype, input.shape[0], bool(atomic_out),
+    out_code = 2 if tickets is not None else int(bool(atomic_out))   # launch_spmm_tc16's atomic_out: 0 store, 1 atomics, 2 tickets
+    plan_key = (blk_offsets.data_ptr(), hind.data_ptr(), num_nodes, embedding_dim, input.dtype, input.shape[0], out_code,
                 bool(beside_panel), bool(defer_combine), row_map.data_ptr() if row_map is not None else 0,
                 values.data_ptr() if values is not None else 0, xcd_ptr.data_ptr() if xcd_ptr is not None else 0,
                 getattr(hspa_packed, "hash_tag", None), tune_space_mode(), SLAB_POLICY)
@@ -703,7 +681,8 @@ def spmm_kernel(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_
     if plan is not None and plan.generation == jit_tuner.generation and KernelTimer.active is None:
         assert input.is_contiguous() and output.is_contiguous() and input.shape[1] == embedding_dim
         assert output.shape[0] == num_nodes and output.shape[1] == embedding_dim and output.dtype == torch.float32
-        return plan.launch(input, output, out_scale if out_scale is not None else unit_scale(input.device), values, defer_combine)
+        return plan.launch(input, output, out_scale if out_scale is not None else unit_scale(input.device), values, tickets,
+                           defer_combine)
 
     assert blk_offsets.is_cuda and blk_offsets.dtype == torch.int32
     assert hspa_packed.is_cuda and hspa_packed.dtype == torch.uint32
@@ -736,6 +715,10 @@ def spmm_kernel(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_
     # unit tables / partial-tile buffers: before the choice is made, those of every schedule in the space (the sweep runs
     # them all); afterwards only the chosen schedule's
     chosen = jit_tuner.tuned_point("spmm_kernel", keys).get("SCHED") if jit_tuner.is_tuned("spmm_kernel", keys) else None
+    if tickets is not None:
+        assert tickets.is_cuda and tickets.dtype == torch.int32
+        assert atomic_out and row_map is None and values is None and elem_bytes == 2, "ticket join: a binary 16-bit adding call"
+        assert chosen in (0, SCHED_UNITS, SCHED_PAIRS), "ticket join: only once the kernel is chosen (no sweep): natural order / unit table"
     tables = {sched: desc.handle_table(blk_offsets, hspa_packed, hind, num_nodes, xcd_ptr) for sched, desc in TABLE_SCHEDULES.items()
               if (chosen == sched if chosen is not None else any(p["SCHED"] == sched for p in space))}
     needs_orders = chosen is None or chosen in ORDER_CHUNKS
@@ -746,7 +729,7 @@ def spmm_kernel(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_
     arg_defs = arg_defs_for(input.dtype)
     named = dict(blk_offsets=blk_offsets, hspa_packed=hspa_packed, hind=hind, num_nodes=num_nodes, num_edges=num_edges,
                  embedding_dim=embedding_dim, input=input, output=output, **orders(blk_offsets, num_nodes), out_scale=out_scale,
-                 atomic_out=int(bool(atomic_out)), combine_now=int(not defer_combine),
+                 atomic_out=out_code, tickets=tickets if tickets is not None else blk_offsets, combine_now=int(not defer_combine),
                  row_map=row_map if row_map is not None else blk_offsets, has_row_map=int(row_map is not None),
                  values=values if values is not None else input, input_rows=int(input.shape[0]), slab_policy=int(SLAB_POLICY),
                  stream=torch.cuda.current_stream())
@@ -799,7 +782,7 @@ def spmm_kernel(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_
     runtime = tune()
     rc = runtime(*args)
     signature = jit_tuner._signature("spmm_kernel", keys)
-    if rc != 0 and signature in jit_tuner.unvalidated:
+    if rc != 0 and signature in jit_tuner.unvalidated and tickets is None:
         # a persisted / bucket choice that is illegal for THESE arguments: forget it and sweep (its first launch was the
         # validation -- no extra launch is spent on choices that are fine)
         jit_tuner.forget("spmm_kernel", keys)
@@ -832,5 +815,5 @@ def spmm_kernel(blk_offsets, hspa_packed, hind, num_nodes, num_edges, embedding_
     except AttributeError:
         pass
     if combine_args is not None:
-        return PendingCombine(table, named[TABLE_SCHEDULES[sched].partials], output, *combine_args)
+        return PendingCombine(table, named[TABLE_SCHEDULES[sched].partials], output, *combine_args, tickets=tickets)
     return None

@@ -16,7 +16,7 @@ from ..jit_kernels import (
     spmm_kernel,
 )
 from .. import capi, hybrid, sidecar
-from ..jit_kernels.spmm import spmm_kernel_ticket, ticket_point
+from ..jit_kernels.spmm import ticket_point
 from ..project import CSR_PATH_FLAG, FP32_MODE_FLAG, PREPROCESS_FLAG
 from ..utils import aligned16, padded_last_dim, piece_width
 
@@ -438,16 +438,13 @@ def _run_two_level(two, operand, output, out_scale, tag_source=None, concurrent=
 
     beside = two.plan.num_ksteps > 0
 
-    # the window kernel's tile and schedule, once this process has chosen them (the first call does, on the atomic join)
+    # the window kernel's tile, once this process has chosen it (the first call does, on the atomic join): its slab width
     point = ticket_point(resid, operand.shape[1], operand, beside) if beside and concurrent else None
 
-    def run_window(atomic, tickets=None):
-        if tickets is not None:
-            return spmm_kernel_ticket(point, two.blk_offsets, resid, two.hind, two.num_nodes, two.plan.num_resid_edges,
-                                      operand.shape[1], operand, output, tickets, out_scale=out_scale, xcd_ptr=two.window_xcd_ptr)
+    def run_window(join):
         return spmm_kernel(two.blk_offsets, resid, two.hind, num_nodes=two.num_nodes,
                            num_edges=two.plan.num_resid_edges, embedding_dim=operand.shape[1], input=operand,
-                           output=output, out_scale=out_scale, atomic_out=atomic,
+                           output=output, out_scale=out_scale, atomic_out=join.window_out, tickets=join.tickets,
                            beside_panel=beside, defer_combine=True, xcd_ptr=two.window_xcd_ptr)
 
     hybrid.run_two_level(two.plan, operand, output, run_window, out_scale=out_scale, concurrent=concurrent,
