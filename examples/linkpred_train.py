@@ -10,12 +10,14 @@ offset), and samples the two-hop neighbourhood of every node involved with `volt
 `voltrix.autograd.SDDMM(batch.pairs)(h[batch.src_local], h)`: the pair pattern goes into the operator as it is, and the gradient
 reaches `h` through both operands.
 
-THE LEAK.  The sampled blocks are drawn from the full graph, so the encoder may aggregate over the very edge (and its reverse) that
-it is asked to predict; DGL removes them with `exclude="reverse_id"`.  `sample_neighbors` has no exclusion argument yet (DESIGN.md
-3.25), so the loss here is optimistic.  On the random features of this example nothing can be learnt beyond the graph's structure
-anyway: the example shows the plumbing and the cost of a step, not a result.
+THE BATCH STAYS OUT OF ITS BLOCKS.  Blocks drawn from the full graph would let the encoder aggregate over the very edge (and its
+reverse) that it is asked to predict.  `main()` passes `exclude_edges="reverse"`: `sample_edge_batch` looks up the reverse `(v, u)`
+of every positive edge `(u, v)` with `voltrix.find_edges` and samples every layer among the entries that are neither a batch edge nor
+such a reverse (DGL's `exclude="reverse_id"`).  `none` as the last command-line argument gives the blocks of the full
+graph, for comparison.  On the random features of this example nothing can be learnt beyond the graph's structure: the example shows
+the plumbing and the cost of a step, not a result.
 
-    python examples/linkpred_train.py [workload] [hidden] [steps] [batch]    # synthetic stand-in graph, random features
+    python examples/linkpred_train.py [workload] [hidden] [steps] [batch] [reverse|self|none]   # synthetic stand-in graph, random features
 """
 import os
 import sys
@@ -60,13 +62,16 @@ class LinkPredictor(torch.nn.Module):
         return SDDMM(batch.pairs)(h[batch.src_local.long()], h)
 
 
-def train_step(model, opt, indptr, indices, x, entries, seed, step, fanouts=FANOUTS, negatives=NEGATIVES, timer=None):
+def train_step(model, opt, indptr, indices, x, entries, seed, step, fanouts=FANOUTS, negatives=NEGATIVES, timer=None,
+               exclude_edges=None):
     """One optimiser step on the positive edges ``entries`` (int32 CSR entry ids); returns the loss (a device scalar).  ``timer``: a
-    list that gets the milliseconds spent in ``sample_edge_batch`` (costs a synchronisation)."""
+    list that gets the milliseconds spent in ``sample_edge_batch`` (costs a synchronisation).  ``exclude_edges``: ``sample_edge_batch``'s
+    argument -- ``None`` samples the blocks from the full graph, ``"reverse"`` keeps the batch's edges and their reverses out of them."""
     import voltrix
 
     t0 = time.perf_counter()
-    batch = voltrix.sample_edge_batch(indptr, indices, entries, negatives, fanouts, seed=seed, offset=step * len(fanouts))
+    batch = voltrix.sample_edge_batch(indptr, indices, entries, negatives, fanouts, seed=seed, offset=step * len(fanouts),
+                                      exclude_edges=exclude_edges)
     if timer is not None:
         torch.cuda.synchronize()
         timer.append((time.perf_counter() - t0) * 1e3)
@@ -85,9 +90,12 @@ def main():
     hidden = int(sys.argv[2]) if len(sys.argv) > 2 else 128
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 30
     batch = int(sys.argv[4]) if len(sys.argv) > 4 else 1024
+    exclude_edges = sys.argv[5] if len(sys.argv) > 5 else "reverse"
+    exclude_edges = None if exclude_edges == "none" else exclude_edges
     indptr, indices, _ = synth_graphs.generate(workload, device="cuda")
     n, nnz = indptr.numel() - 1, indices.numel()
-    print(f"{workload}: N={n} nnz={nnz}; batches of {batch} edges, {NEGATIVES} negatives per edge, fan-outs {FANOUTS} (input layer first)")
+    print(f"{workload}: N={n} nnz={nnz}; batches of {batch} edges, {NEGATIVES} negatives per edge, fan-outs {FANOUTS} (input layer first), "
+          f"exclude_edges={exclude_edges!r}")
     torch.manual_seed(0)
     in_feats = 128
     x = torch.randn(n, in_feats, device="cuda")
@@ -99,10 +107,10 @@ def main():
         entries = torch.randint(0, nnz, (batch,), device="cuda", generator=gen, dtype=torch.int32)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        loss = train_step(model, opt, indptr, indices, x, entries, seed=1234, step=step, timer=sampling)
+        loss = train_step(model, opt, indptr, indices, x, entries, seed=1234, step=step, timer=sampling, exclude_edges=exclude_edges)
         torch.cuda.synchronize()
         times.append((time.perf_counter() - t0) * 1e3)
-        if step in (0, 1, steps - 1):
+        if step in (0, 1, steps - 1) or step % 5 == 0:
             print(f"step {step}: loss {float(loss):.4f}, {times[-1]:.2f} ms")
     median = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
     steady, sample = (median(times[2:]), median(sampling[2:])) if len(times) > 2 else (times[-1], sampling[-1])

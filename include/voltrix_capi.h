@@ -895,6 +895,44 @@ void voltrix_launch_negative_sample(void* indptr, void* indices, int num_rows, i
 void voltrix_launch_edge_endpoints(void* indptr, void* indices, int num_rows, int64_t num_entries, void* entries, int num_ids, void* rows,
                                    void* cols, void* stream, int* return_code);
 
+/* Neighbour sampling that leaves a set of CSR entries out (voltrix/neighbor_sample_exclude_kernels.hpp): what keeps a link-prediction
+ * batch's positive edges and their reverses out of the sampled blocks (DGL's exclude="reverse_id").  No reference counterpart.
+ * THE EXCLUSION RULE.  exclude = device int32[num_exclude] CSR entry ids, STRICTLY ASCENDING (sorted, distinct), each in [0, nnz): the
+ * caller's to guarantee, not checked on the device.  For a seed row r with begin = indptr[r], end = indptr[r + 1], d = end - begin:
+ *   lo = lower_bound(exclude, begin), hi = lower_bound(exclude, end), x = hi - lo;
+ *   the excluded positions of the row are q_i = exclude[lo + i] - begin, i = 0 .. x - 1, ascending;
+ *   the candidates are the d' = d - x positions of the row not among the q_i, in CSR order;
+ *   candidate number t is position cand(t) = t + #{ i : q_i - i <= t } (q_i - i does not decrease: one binary search, O(log x)).
+ * THE SAMPLING RULE of voltrix_launch_sample_neighbors then applies unchanged with d' in place of d, every position it yields mapped
+ * through cand: replace = 0, d' <= k (and fanout = -1): every candidate in CSR order; replace = 0, d' > k: Floyd's algorithm on
+ * 0 .. d' - 1 with the same draw(r, i) and the same counter domain, output ascending; replace = 1, d' > 0: k entries at
+ * cand((uint64(draw(r, i)) * d') >> 32); d' = 0: nothing.  A row none of whose entries is excluded gets exactly the bits
+ * voltrix_launch_sample_neighbors gives it, and num_exclude == 0 (exclude may be NULL then) gives that call's bits for every row.  The
+ * result is a function of (seed, offset, r, d', k) and the row's excluded positions only; sorted rows stay sorted; s_entries holds ids
+ * into the original indices.  s_indptr = the caller's prefix sum of the per-seed counts the rule gives with d' (min(d', k); d' > 0 ? k
+ * : 0 with replace; d' for fanout = -1).  Every element of s_indices and s_entries is written then; a row never writes past its
+ * segment, and no list, however malformed, makes the kernel read outside the row.  One lane per seed, 256 per workgroup, two binary
+ * searches in exclude per row and one per output entry on top of voltrix_launch_sample_neighbors: the cost does not follow the degree
+ * (fanout = -1 and d' <= k merge the row against its slice of exclude with one lane: O(d)).  No atomics, no workspace, no host
+ * synchronisation.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: what voltrix_launch_sample_neighbors refuses, num_exclude < 0, a misaligned
+ * exclude, a null exclude with num_exclude > 0; VOLTRIX_OK without a launch for num_seeds == 0 or num_sampled == 0.  Alignment: 4 bytes
+ * everywhere. */
+void voltrix_launch_sample_neighbors_excluding(void* indptr, void* indices, int num_rows, void* seeds, int num_seeds, void* s_indptr,
+                                               int64_t num_sampled, int fanout, int replace, uint64_t seed, uint64_t offset, void* exclude,
+                                               int num_exclude, void* s_indices, void* s_entries, void* stream, int* return_code);
+
+/* (ROW, COLUMN) -> ENTRY (DGL's edge_ids / has_edges_between).  rows, cols = device int32[num_queries].  out[i] = the id of the FIRST
+ * entry of row rows[i] whose column is cols[i]; -1 if there is none or rows[i] is outside [0, num_rows).  No [nnz] key array is kept,
+ * so this is a search: assume_sorted = 1 is the PRECONDITION that every row's columns ascend (duplicates allowed): a lower bound,
+ * O(log d); assume_sorted = 0: a linear scan by the query's one lane, O(d), the slow path; on sorted input both give the same bits.
+ * out = device int32[num_queries], every element written.  One lane per query; no atomics, no workspace, no host synchronisation.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any HIP call: negative sizes, num_entries > INT_MAX, assume_sorted outside {0, 1}, a
+ * null or misaligned pointer (indices may be null where num_entries == 0); VOLTRIX_OK without a launch for num_queries == 0.
+ * Alignment: 4 bytes everywhere. */
+void voltrix_launch_find_edges(void* indptr, void* indices, int num_rows, int64_t num_entries, void* rows, void* cols, int num_queries,
+                               int assume_sorted, void* out, void* stream, int* return_code);
+
 /* Rows of a dense row-major matrix times a per-row factor: dst[i, :] = T(float(src[i, :]) * scale[i]); dst may be src.
  * dtype 0 fp32 / 1 fp16 / 2 bfloat16; a row (num_feats elements) must be a multiple of 16 bytes; scale: device float[rows].
  * What edge values of the form v_ij = r_i * c_j cost on top of the binary product (voltrix/weighted.py: B's rows times c before,

@@ -24,7 +24,7 @@ from .spmm_reduce import spmm_reduce
 from .dropout import apply_dropout_mask, dropout_mask
 from .sampling import Block, compact_block, sample_blocks, sample_neighbors
 from .subgraph import Subgraph, induced_subgraph, random_walk, sample_subgraph_rw, subgraph_csr
-from .negative import EdgeBatch, edge_endpoints, negative_sample, sample_edge_batch
+from .negative import EdgeBatch, edge_endpoints, find_edges, negative_sample, sample_edge_batch
 from .graphed import GraphedSpMM
 from . import autograd, hybrid, jit, sidecar, utils
 

@@ -115,6 +115,8 @@ SIGNATURES = {
     "voltrix_launch_random_walk": (None, [_P, _P, _I, _P, _I, _I, _U64, _U64, _P, _P, _I, _P, _RC_P]),
     "voltrix_launch_negative_sample": (None, [_P, _P, _I, _I, _L, _P, _I, _I, _I, _I, _I, _U64, _U64, _P, _P, _RC_P]),
     "voltrix_launch_edge_endpoints": (None, [_P, _P, _I, _L, _P, _I, _P, _P, _P, _RC_P]),
+    "voltrix_launch_sample_neighbors_excluding": (None, [_P, _P, _I, _P, _I, _P, _L, _I, _I, _U64, _U64, _P, _I, _P, _P, _P, _RC_P]),
+    "voltrix_launch_find_edges": (None, [_P, _P, _I, _L, _P, _P, _I, _I, _P, _P, _RC_P]),
     "voltrix_csr_preprocess_workspace_bytes": (_L, [_I, _I, _L, _I]),
     "voltrix_launch_csr_window_count": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
     "voltrix_launch_csr_fill": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
@@ -1057,6 +1059,34 @@ def launch_edge_endpoints(indptr, indices, num_rows: int, entries, rows, cols, s
     assert indptr.numel() == num_rows + 1 and rows.numel() == entries.numel() == cols.numel()
     _checked("voltrix_launch_edge_endpoints", indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), entries.data_ptr(),
              entries.numel(), rows.data_ptr(), cols.data_ptr(), stream)
+
+
+def launch_sample_neighbors_excluding(indptr, indices, num_rows: int, seeds, s_indptr, num_sampled: int, fanout: int, replace: bool,
+                                      seed: int, offset: int, exclude, s_indices, s_entries, stream) -> None:
+    """``launch_sample_neighbors`` among the entries of every seed row that are not in ``exclude`` (device int32 CSR entry ids, strictly
+    ascending), by the exclusion rule of voltrix/neighbor_sample_exclude_kernels.hpp; ``s_indptr`` is the prefix sum of the rule's
+    counts with ``d'`` in place of ``d``; see include/voltrix_capi.h."""
+    import torch
+
+    for t in (indptr, indices, seeds, s_indptr, exclude, s_indices, s_entries):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+    assert indptr.numel() == num_rows + 1 and s_indptr.numel() == seeds.numel() + 1
+    assert s_indices.numel() == num_sampled == s_entries.numel()
+    _checked("voltrix_launch_sample_neighbors_excluding", indptr.data_ptr(), indices.data_ptr(), num_rows, seeds.data_ptr(),
+             seeds.numel(), s_indptr.data_ptr(), num_sampled, int(fanout), int(bool(replace)), int(seed), int(offset),
+             exclude.data_ptr() if exclude.numel() else None, exclude.numel(), s_indices.data_ptr(), s_entries.data_ptr(), stream)
+
+
+def launch_find_edges(indptr, indices, num_rows: int, rows, cols, assume_sorted: bool, out, stream) -> None:
+    """``out[i]``: the id of the first entry of row ``rows[i]`` whose column is ``cols[i]``, ``-1`` if there is none or the row is outside
+    ``[0, num_rows)`` (a lower bound with ``assume_sorted``, a scan without); see include/voltrix_capi.h."""
+    import torch
+
+    for t in (indptr, indices, rows, cols, out):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+    assert indptr.numel() == num_rows + 1 and rows.numel() == cols.numel() == out.numel()
+    _checked("voltrix_launch_find_edges", indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), rows.data_ptr(),
+             cols.data_ptr(), rows.numel(), int(bool(assume_sorted)), out.data_ptr(), stream)
 
 
 def launch_scatter_values(values, slots, plane, stream) -> None:

@@ -33,14 +33,24 @@ slots per position, ``T = max_tries`` tries per slot, a 64-bit ``seed`` and a 64
 ENTRY -> ENDPOINTS.  The package keeps no ``[nnz]`` row-id array, so the row of CSR entry ``e`` is a search: the one ``r`` with
 ``indptr[r] <= e < indptr[r + 1]``, found as the upper bound of ``e`` in ``indptr`` minus one, which steps over runs of empty rows.
 
-Host synchronisations: one per ``negative_sample`` (the number of exhausted slots and the "a source is out of range" flag in one
-read-back), one per ``edge_endpoints`` ("an entry id is out of range"), and per ``sample_edge_batch`` those two, ``compact_block``'s
-one (the number of distinct nodes) and ``sample_blocks``' two per layer: ``3 + 2 len(fanouts)`` (plus what the ``CsrPattern``
-constructors' transposes cost, as for every ``Block``).
+(ROW, COLUMN) -> ENTRY (``find_edges``; DGL's ``edge_ids`` / ``has_edges_between``).  No ``[nnz]`` key array either, so the id of the
+FIRST entry of row ``r`` whose column is ``c`` is a search in the row: a lower bound with ``assume_sorted=True`` (the precondition
+above), a scan without; ``-1`` where there is none or the row is outside ``[0, num_rows)``.
 
-Not part of it: removing the batch's positive edges and their reverses from the sampled blocks (DGL's
-``exclude="reverse_id"``) -- the encoder sees the edges it is asked to predict; degree-weighted negatives; distinct negatives within a
-row.
+KEEPING THE BATCH OUT OF ITS BLOCKS.  ``sample_edge_batch(..., exclude_edges="reverse")`` samples the blocks with
+``sample_blocks(..., exclude=)``: the batch's own entries and, where ``find_edges(dst, src)`` finds one, the entry of every reverse
+``(v, u)``, sorted and deduplicated -- the encoder then aggregates over neither the edge the decoder is asked to predict nor its
+reverse (DGL's ``exclude="reverse_id"``).  ``"self"`` leaves out the batch's own entries only.  LIMITATION: in a CSR whose rows hold
+duplicate columns only the FIRST reverse entry is excluded.
+
+Host synchronisations: one per ``negative_sample`` (the number of exhausted slots and the "a source is out of range" flag in one
+read-back), one per ``edge_endpoints`` ("an entry id is out of range"), none in ``find_edges``, and per ``sample_edge_batch`` the first
+two, ``compact_block``'s one (the number of distinct nodes) and ``sample_blocks``' two per layer: ``3 + 2 len(fanouts)`` (plus what the
+``CsrPattern`` constructors' transposes cost, as for every ``Block``); with ``exclude_edges`` one more, ``torch.unique``'s (the length
+of the exclusion list): ``4 + 2 len(fanouts)``.
+
+Not part of it: degree-weighted negatives; distinct negatives within a row; excluding every duplicate of a
+reverse edge.
 """
 from __future__ import annotations
 
@@ -122,6 +132,32 @@ def edge_endpoints(indptr: torch.Tensor, indices: torch.Tensor, entries: torch.T
     return rows, cols
 
 
+def find_edges(indptr: torch.Tensor, indices: torch.Tensor, rows: torch.Tensor, cols: torch.Tensor, assume_sorted: bool = True):
+    """The CSR entry id of every pair ``(rows[i], cols[i])`` (device int32 ``[Q]`` each, any order, duplicates allowed) -> int32 ``[Q]``:
+    the id of the FIRST entry of row ``rows[i]`` whose column is ``cols[i]``, ``-1`` where the row holds no such column or lies outside
+    ``[0, num_rows)`` -- so ``find_edges(...) >= 0`` is DGL's ``has_edges_between`` and the ids are its ``edge_ids``.  A search by one
+    lane per pair, no ``[nnz]`` key array: ``assume_sorted=True`` requires ascending columns in every row (duplicates allowed; not
+    checked) and takes a lower bound, ``O(log d)``; ``False`` scans the row: the slow path.  On sorted rows both give the same bits.
+    Every element is written, on the current stream; NO host synchronisation."""
+    from . import capi
+    from .jit_kernels.spmm import _raw_stream
+
+    indptr, indices = _device_int32(indptr, "indptr"), _device_int32(indices, "indices")
+    rows, cols = _device_int32(rows, "rows"), _device_int32(cols, "cols")
+    num_rows = indptr.numel() - 1
+    if num_rows < 0:
+        raise ValueError("indptr is empty")
+    if rows.numel() != cols.numel():
+        raise ValueError(f"find_edges: {rows.numel()} rows for {cols.numel()} columns")
+    out = torch.empty(rows.numel(), dtype=torch.int32, device=rows.device)
+    if rows.numel():
+        capi.launch_find_edges(indptr, indices, num_rows, rows, cols, assume_sorted, out, _raw_stream(rows.device))
+    return out
+
+
+EXCLUDE_EDGES = (None, "self", "reverse")
+
+
 @dataclass
 class EdgeBatch:
     """A link-prediction mini-batch of ``B`` positive edges.  ``blocks``: the ``Block`` list of ``voltrix.sample_blocks`` whose output
@@ -141,16 +177,24 @@ class EdgeBatch:
 
 def sample_edge_batch(indptr: torch.Tensor, indices: torch.Tensor, entries: torch.Tensor, num_negatives: int, fanouts, seed: int,
                       offset: int = 0, max_tries: int = 16, exclude_self: bool = True, assume_sorted: bool = True,
-                      replace: bool = False) -> EdgeBatch:
+                      replace: bool = False, exclude_edges=None) -> EdgeBatch:
     """The mini-batch of the positive edges ``entries`` (device int32 CSR entry ids of a SQUARE CSR) -> ``EdgeBatch``.  Plumbing only:
     ``edge_endpoints``; ``negative_sample(src, num_negatives, seed, offset, ...)`` on the batch's sources; ``compact_block`` without
     seeds for the distinct nodes among sources, destinations and negatives in ascending id (the ``-1`` of an exhausted slot is not an
     id) and everybody's local id; ``sample_blocks(node_ids, fanouts, seed, offset, replace)``; a prefix sum for ``pairs``.  Layer ``l``
     of the blocks is sampled with ``offset + l`` as always; the negatives use ``offset`` itself, and their counter domain keeps them
-    apart from layer 0's draws.  ``3 + 2 len(fanouts)`` host synchronisations.  The blocks still hold the batch's positive edges: see
-    the module docstring."""
+    apart from layer 0's draws.  ``3 + 2 len(fanouts)`` host synchronisations.
+
+    ``exclude_edges``: ``None`` -- the blocks are sampled from the full graph and hold the batch's positive edges; ``"self"`` -- no
+    layer returns one of ``entries``; ``"reverse"`` -- nor the entry ``find_edges(dst, src)`` finds for the reverse ``(v, u)`` of a
+    batch edge ``(u, v)`` (a reverse that does not exist is skipped; of duplicate columns only the first entry is found).  The ids are
+    sorted and deduplicated with ``torch.unique`` -- one more host synchronisation, ``4 + 2 len(fanouts)`` -- and passed to
+    ``sample_blocks(..., exclude=)``.  Any other value is a ``ValueError`` before any tensor is looked at.  The negatives, ``pairs``,
+    ``labels``, ``src_local`` and ``node_ids`` do not depend on it; ``exclude_self`` is about the negatives, as before."""
     from .autograd import CsrPattern
 
+    if exclude_edges is not None and not (isinstance(exclude_edges, str) and exclude_edges in EXCLUDE_EDGES):
+        raise ValueError(f'exclude_edges must be None, "self" or "reverse", got {exclude_edges!r}')
     _check_negative_arguments(num_negatives, max_tries, seed, offset)
     fanouts = list(fanouts)
     for fanout in fanouts:
@@ -164,7 +208,14 @@ def sample_edge_batch(indptr: torch.Tensor, indices: torch.Tensor, entries: torc
         raise ValueError("sample_edge_batch: no entries")
     none = torch.empty(0, dtype=torch.int32, device=dev)
     node_ids, local = compact_block(none, torch.cat([src, dst, neg.view(-1)]), num_nodes)
-    blocks = sample_blocks(indptr, indices, node_ids, fanouts, seed, offset, replace)
+    exclude = None
+    if exclude_edges is not None:
+        ids = entries
+        if exclude_edges == "reverse":
+            reverse = find_edges(indptr, indices, dst, src, assume_sorted)
+            ids = torch.cat([entries, torch.where(reverse >= 0, reverse, entries)])      # no reverse: the edge itself, once more
+        exclude = torch.unique(ids)                           # sorted and distinct: the exclusion rule's precondition
+    blocks = sample_blocks(indptr, indices, node_ids, fanouts, seed, offset, replace, exclude)
     src_local = local[:count].contiguous()
     candidates = torch.cat([local[count:2 * count, None], local[2 * count:].view(count, num_negatives)], 1)      # [B, 1 + k], -1: exhausted
     total = candidates.numel() - num_exhausted

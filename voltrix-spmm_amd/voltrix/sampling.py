@@ -25,9 +25,28 @@ GLOBAL row id), fan-out ``k``, degree ``d = indptr[r + 1] - indptr[r]``, a 64-bi
 * ``replace=True``, ``d > 0``: exactly ``k`` entries; entry ``i`` is at position ``(uint64(draw(r, i)) * d) >> 32``, in draw order.  A
   row with ``d == 0`` gives none.
 
+THE EXCLUSION RULE (the contract; DESIGN.md 3.26, voltrix/neighbor_sample_exclude_kernels.hpp, ``tests/exclude_oracle.py`` is the numpy
+restatement).  ``exclude`` is a device int32 ``[X]`` of CSR entry ids, STRICTLY ASCENDING (sorted, distinct), each in ``[0, nnz)``.  For
+a seed row ``r`` with ``begin = indptr[r]``, ``end = indptr[r + 1]``, ``d = end - begin``:
+
+* ``lo = lower_bound(exclude, begin)``, ``hi = lower_bound(exclude, end)``, ``x = hi - lo``; the excluded positions of the row are
+  ``q_i = exclude[lo + i] - begin``, ``i = 0 .. x - 1``, ascending.
+* The CANDIDATES are the ``d' = d - x`` positions of the row not among the ``q_i``, in CSR order.  Candidate number ``t`` is position
+  ``cand(t) = t + #{i : q_i - i <= t}``; ``q_i - i`` does not decrease, so ``cand(t)`` is one binary search over the row's slice of
+  ``exclude``: ``O(log x)``.
+* The sampling rule above then applies UNCHANGED WITH ``d'`` IN PLACE OF ``d``, every position it yields mapped through ``cand``:
+  ``d' <= k`` without replacement (and ``fanout=None``): every candidate in CSR order; ``d' > k``: Floyd's algorithm on
+  ``0 .. d' - 1`` with the same ``draw(r, i)`` and the same counter domain, output ascending; ``replace=True``, ``d' > 0``: ``k``
+  entries at ``cand((uint64(draw(r, i)) * d') >> 32)``; ``d' = 0``: nothing.
+* So a row none of whose entries is excluded gets exactly the bits it gets without ``exclude``; the result is a function of
+  ``(seed, offset, r, d', k)`` and the row's excluded positions only; sorted rows stay sorted; ``s_entries`` still holds ids into the
+  original ``indices``.
+
 Cost: one lane per seed, ``O(k^2)`` compares and ``k`` gathers whatever the degree -- a hub row costs what a row of degree ``k + 1``
 costs (``fanout=None`` copies a row with one lane: ``O(d)``).  Host synchronisations: one per ``sample_neighbors`` (the total and the
-"a seed is out of range" flag in one read-back), one per ``compact_block`` (``num_src``): two per layer of ``sample_blocks``.
+"a seed is out of range" flag in one read-back), one per ``compact_block`` (``num_src``): two per layer of ``sample_blocks``.  With
+``exclude`` the kernel adds two binary searches in ``exclude`` per row and one per output entry -- still not a function of the degree --
+and the validity of ``exclude`` travels in the same one read-back: no further synchronisation.
 """
 from __future__ import annotations
 
@@ -54,7 +73,7 @@ def _device_int32(t: torch.Tensor, name: str) -> torch.Tensor:
 
 
 def sample_neighbors(indptr: torch.Tensor, indices: torch.Tensor, seeds: torch.Tensor, fanout, seed: int, offset: int = 0,
-                     replace: bool = False, num_rows: int = None):
+                     replace: bool = False, num_rows: int = None, exclude: torch.Tensor = None):
     """At most ``fanout`` entries of every row in ``seeds``, by the module's sampling rule -> ``(s_indptr, s_indices, s_entries)``: the
     sampled sub-CSR over the seeds (int32 ``[S + 1]``; row ``i`` belongs to ``seeds[i]``), the GLOBAL column id of every sampled entry
     and its CSR entry id in ``indices`` (int32 ``[m]``; for edge features, edge values and ``arg``-style bookkeeping).  Every element
@@ -64,12 +83,21 @@ def sample_neighbors(indptr: torch.Tensor, indices: torch.Tensor, seeds: torch.T
     row ids, duplicates allowed, any order; views are made contiguous.  ``fanout``: 1..64, or ``None`` for every entry.  The per-seed
     counts and their prefix sum are torch ops; the total ``m`` and an "any seed outside [0, num_rows)" flag come back in ONE small
     read-back, the only host synchronisation.  An out-of-range seed is a ``ValueError``; so are, before any tensor is looked at, a
-    ``fanout`` outside 1..64 that is not ``None`` and a ``seed`` or ``offset`` outside ``[0, 2^64)``."""
+    ``fanout`` outside 1..64 that is not ``None`` and a ``seed`` or ``offset`` outside ``[0, 2^64)``.
+
+    ``exclude``: ``None`` (the call as it always was), or a device int32 tensor of CSR entry ids, strictly ascending and in
+    ``[0, nnz)``, that no row may return: the module's exclusion rule, through a kernel of its own.  The degrees become ``d'`` by two
+    ``torch.searchsorted`` calls; "``exclude`` is not strictly ascending or leaves ``[0, nnz)``" is a third value of the same one
+    read-back and a ``ValueError``.  An empty ``exclude`` gives the bits of ``None``; a row without an excluded entry gets them too."""
     from . import capi
     from .jit_kernels.spmm import _raw_stream
 
     _check_rule_arguments(fanout, seed, offset)
     indptr, indices, seeds = _device_int32(indptr, "indptr"), _device_int32(indices, "indices"), _device_int32(seeds, "seeds")
+    if exclude is not None:
+        exclude = _device_int32(exclude, "exclude")
+        if exclude.numel() == 0:
+            exclude = None
     num_rows = indptr.numel() - 1 if num_rows is None else int(num_rows)
     if num_rows < 0 or indptr.numel() != num_rows + 1:
         raise ValueError(f"indptr has {indptr.numel()} elements for {num_rows} rows")
@@ -83,6 +111,11 @@ def sample_neighbors(indptr: torch.Tensor, indices: torch.Tensor, seeds: torch.T
     bad = (rows < 0) | (rows >= num_rows)
     rows = rows.clamp(0, num_rows - 1)
     degree = torch.where(bad, torch.zeros_like(rows), (indptr[rows + 1] - indptr[rows]).long())
+    bad_exclude = None
+    if exclude is not None:                          # d' = d - x, x = the entries of the row's range that `exclude` holds
+        held = torch.searchsorted(exclude, indptr[rows + 1].contiguous()) - torch.searchsorted(exclude, indptr[rows].contiguous())
+        degree = torch.where(bad, torch.zeros_like(rows), (degree - held).clamp(min=0))
+        bad_exclude = (exclude[1:] <= exclude[:-1]).any() | (exclude[0] < 0) | (exclude[-1] >= indices.numel())
     if fanout is None:
         taken = degree
     elif replace:
@@ -90,7 +123,12 @@ def sample_neighbors(indptr: torch.Tensor, indices: torch.Tensor, seeds: torch.T
     else:
         taken = degree.clamp(max=fanout)
     ends = torch.cumsum(taken, 0)
-    total, any_bad = torch.stack([ends[-1], bad.any().long()]).tolist()          # the one synchronisation
+    if exclude is None:
+        total, any_bad = torch.stack([ends[-1], bad.any().long()]).tolist()      # the one synchronisation
+    else:
+        total, any_bad, any_bad_exclude = torch.stack([ends[-1], bad.any().long(), bad_exclude.long()]).tolist()   # the one, here
+        if any_bad_exclude:
+            raise ValueError(f"sample_neighbors: exclude must be strictly ascending CSR entry ids in [0, {indices.numel()})")
     if any_bad:
         raise ValueError(f"sample_neighbors: a seed outside [0, {num_rows})")
     if total > _INT_MAX:
@@ -98,8 +136,13 @@ def sample_neighbors(indptr: torch.Tensor, indices: torch.Tensor, seeds: torch.T
     s_indptr[1:] = ends
     s_indices = torch.empty(total, dtype=torch.int32, device=dev)
     s_entries = torch.empty(total, dtype=torch.int32, device=dev)
-    capi.launch_sample_neighbors(indptr, indices, num_rows, seeds, s_indptr, total, capi.SAMPLE_ALL if fanout is None else fanout,
-                                 replace, seed, offset, s_indices, s_entries, _raw_stream(dev))
+    if exclude is None:
+        capi.launch_sample_neighbors(indptr, indices, num_rows, seeds, s_indptr, total, capi.SAMPLE_ALL if fanout is None else fanout,
+                                     replace, seed, offset, s_indices, s_entries, _raw_stream(dev))
+    else:
+        capi.launch_sample_neighbors_excluding(indptr, indices, num_rows, seeds, s_indptr, total,
+                                               capi.SAMPLE_ALL if fanout is None else fanout, replace, seed, offset, exclude, s_indices,
+                                               s_entries, _raw_stream(dev))
     return s_indptr, s_indices, s_entries
 
 
@@ -156,25 +199,28 @@ class Block:
 
 
 def sample_blocks(indptr: torch.Tensor, indices: torch.Tensor, seeds: torch.Tensor, fanouts, seed: int, offset: int = 0,
-                  replace: bool = False):
+                  replace: bool = False, exclude: torch.Tensor = None):
     """The blocks of a ``len(fanouts)``-layer mini-batch whose output nodes are ``seeds`` -> a list of ``Block``, INPUT layer first:
     ``fanouts[i]`` is the fan-out of ``blocks[i]`` (``None``: every neighbour), ``blocks[-1].dst_ids`` is ``seeds`` and the ``dst_ids``
     of every other block are the ``src_ids`` of the block after it.  Layer ``l``, counted from the OUTPUT layer as ``l = 0``, is sampled
     with ``offset + l`` (wrapping at 2^64), so the layers draw from unrelated streams and a caller that steps ``offset`` by
     ``len(fanouts)`` per batch never reuses one.  ``indptr`` / ``indices``: a square device int32 CSR (the sampled columns become the
-    next layer's rows); ``seeds``: device int32, no duplicates.  Two host synchronisations per layer."""
+    next layer's rows); ``seeds``: device int32, no duplicates.  ``exclude`` (``sample_neighbors``' argument: strictly ascending CSR entry
+    ids) is left out of EVERY layer.  Two host synchronisations per layer, with or without it."""
     from .autograd import CsrPattern
 
     fanouts = list(fanouts)
     for fanout in fanouts:
         _check_rule_arguments(fanout, seed, offset)
     indptr, indices, seeds = _device_int32(indptr, "indptr"), _device_int32(indices, "indices"), _device_int32(seeds, "seeds")
+    if exclude is not None:
+        exclude = _device_int32(exclude, "exclude")
     num_nodes = indptr.numel() - 1
     blocks = []
     dst_ids = seeds
     for layer, fanout in enumerate(reversed(fanouts)):
         s_indptr, s_indices, entries = sample_neighbors(indptr, indices, dst_ids, fanout, seed, (offset + layer) % 2 ** 64, replace,
-                                                        num_nodes)
+                                                        num_nodes, exclude)
         src_ids, local = compact_block(dst_ids, s_indices, num_nodes)
         num_dst, num_src = dst_ids.numel(), src_ids.numel()
         blocks.append(Block(CsrPattern(s_indptr, local, num_dst, num_src), src_ids, dst_ids, entries, num_dst, num_src))
