@@ -80,8 +80,8 @@ def run_graph(name, scale, steps, warmup, rounds, torch_steps, batch, extra_seed
             ms = _windows(lambda: capi.launch_sample_neighbors(indptr, indices, n, seeds, plain[0], plain[2].numel(), fanout, replace, SEED,
                                                                0, plain[1], plain[2], stream), steps, warmup, rounds, events=True)
             line.update({"plain_kernel_" + key: v for key, v in _stats(ms).items()})
-            ms = _windows(lambda: capi.launch_sample_neighbors_excluding(indptr, indices, n, seeds, mine[0], mine[2].numel(), fanout, replace,
-                                                                         SEED, 0, exclude, mine[1], mine[2], stream),
+            ms = _windows(lambda: capi.launch_sample_neighbors(indptr, indices, n, seeds, mine[0], mine[2].numel(), fanout, replace, SEED,
+                                                               0, mine[1], mine[2], stream, exclude=exclude),
                           steps, warmup, rounds, events=True)
             line.update({"kernel_" + key: v for key, v in _stats(ms).items()})
             line["call_over_plain"] = round(line["call_ms"] / line["plain_call_ms"], 3)

@@ -895,7 +895,7 @@ void voltrix_launch_negative_sample(void* indptr, void* indices, int num_rows, i
 void voltrix_launch_edge_endpoints(void* indptr, void* indices, int num_rows, int64_t num_entries, void* entries, int num_ids, void* rows,
                                    void* cols, void* stream, int* return_code);
 
-/* Neighbour sampling that leaves a set of CSR entries out (voltrix/neighbor_sample_exclude_kernels.hpp): what keeps a link-prediction
+/* Neighbour sampling that leaves a set of CSR entries out (voltrix/neighbor_sample_kernels.hpp): what keeps a link-prediction
  * batch's positive edges and their reverses out of the sampled blocks (DGL's exclude="reverse_id").  No reference counterpart.
  * THE EXCLUSION RULE.  exclude = device int32[num_exclude] CSR entry ids, STRICTLY ASCENDING (sorted, distinct), each in [0, nnz): the
  * caller's to guarantee, not checked on the device.  For a seed row r with begin = indptr[r], end = indptr[r + 1], d = end - begin:

@@ -1,4 +1,4 @@
-"""A numpy restatement of the exclusion rule (voltrix/neighbor_sample_exclude_kernels.hpp, voltrix/sampling.py) and of
+"""A numpy restatement of the exclusion rule (voltrix/neighbor_sample_kernels.hpp, voltrix/sampling.py) and of
 the (row, column) -> entry lookup, for the tests that hold the kernels to them.  The draws, Floyd's algorithm and the replacement rule
 are tests/sample_oracle.py's, unchanged: only the degree they see (d' = d - x) and the mapping of their positions (cand) are new.
 

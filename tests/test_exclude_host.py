@@ -1,12 +1,13 @@
 """CPU: the exclusion rule of the neighbour sampler, the (row, column) -> entry lookup and their plumbing.  A stand-alone
-host program runs the header's own ``exclude_row_count`` / ``exclude_cand`` / ``sample_row_excluding`` / ``find_entry`` -- the code the
+host program runs the headers' own ``exclude_row_count`` / ``exclude_cand`` / ``sample_row`` / ``find_entry`` -- the code the
 kernels run -- and agrees with the numpy restatement (tests/exclude_oracle.py): ``cand`` for every row of degree <= 10 and every subset
 of excluded positions, the known answers written out here, in the kernel header and in DESIGN.md, uniform draws among the candidates
 and never an excluded position; the two entry points are declared, bound and exported; their argument checks answer on the host before
-any HIP call; the Python layer raises before it looks at a tensor; both kernels, in all instantiations, compile for gfx950 without
-scratch, spilled registers or static LDS.  No GPU compute is called here (tests/test_gpu_exclude.py compares the kernels with the same
-oracle)."""
+any HIP call; the Python layer raises before it looks at a tensor; the lookup kernel, in both instantiations, compiles for gfx950
+without scratch, spilled registers or static LDS (the sampling kernel's report is tests/test_sample_host.py's).  No GPU compute is
+called here (tests/test_gpu_exclude.py compares the kernels with the same oracle)."""
 import ctypes
+import inspect
 import os
 import re
 import shutil
@@ -74,7 +75,8 @@ PROGRAM = r"""
 #include <cstring>
 #include <vector>
 
-#include "voltrix/neighbor_sample_exclude_kernels.hpp"
+#include "voltrix/find_edges_kernels.hpp"
+#include "voltrix/neighbor_sample_kernels.hpp"
 
 struct ArraySlots {
   std::vector<int> v;
@@ -154,11 +156,11 @@ int main(int argc, char** argv) {
       ArraySlots slot{std::vector<int>(fanout < 0 ? 0 : fanout, -1)};
       if (d > 0 && room > 0) {
         if (replace)
-          voltrix::sample_row_excluding<true>(indices.data(), exclude.data(), (int)exclude.size(), (uint32_t)r, begin, d, k, room, k0, k1,
-                                              o0, o1, slot, cols.data(), entries.data());
+          voltrix::sample_row<true>(indices.data(), exclude.data(), (int)exclude.size(), (uint32_t)r, begin, d, k, room, k0, k1, o0, o1,
+                                    slot, cols.data(), entries.data());
         else
-          voltrix::sample_row_excluding<false>(indices.data(), exclude.data(), (int)exclude.size(), (uint32_t)r, begin, d, k, room, k0, k1,
-                                               o0, o1, slot, cols.data(), entries.data());
+          voltrix::sample_row<false>(indices.data(), exclude.data(), (int)exclude.size(), (uint32_t)r, begin, d, k, room, k0, k1, o0, o1,
+                                     slot, cols.data(), entries.data());
       }
       for (int j = 0; j < room; ++j) if (cols[j] != indices.at(entries[j])) return 6;
       if (counting) {
@@ -307,8 +309,9 @@ def test_header_declares_and_binding_lists_the_entry_points():
         assert hasattr(capi.lib(), name)
     assert capi.lib().voltrix_abi_version() == 2
     assert callable(voltrix.find_edges) and voltrix.find_edges is voltrix.negative.find_edges
-    for wrapper in ("launch_sample_neighbors_excluding", "launch_find_edges"):
+    for wrapper in ("launch_sample_neighbors", "launch_find_edges"):       # the one sampling wrapper takes ``exclude=``
         assert callable(getattr(capi, wrapper)) and not hasattr(getattr(capi, wrapper), "timer_label"), wrapper
+    assert "exclude" in inspect.signature(capi.launch_sample_neighbors).parameters
 
 
 def _ptrs(names, null, offset):
@@ -417,17 +420,16 @@ def test_python_layer_rejects_bad_arguments_before_any_tensor_is_looked_at():
 
 
 SOURCE = r'''
-#include "voltrix/neighbor_sample_exclude_kernels.hpp"
-template __global__ void voltrix::sample_neighbors_excluding_kernel<false>(const voltrix::SampleExcludingArgs);
-template __global__ void voltrix::sample_neighbors_excluding_kernel<true>(const voltrix::SampleExcludingArgs);
+#include "voltrix/find_edges_kernels.hpp"
 template __global__ void voltrix::find_edges_kernel<true>(const int*, const int*, const int*, const int*, int, int, int*);
 template __global__ void voltrix::find_edges_kernel<false>(const int*, const int*, const int*, const int*, int, int, int*);
 '''
 
 
 def resource_usage(workdir):
-    """{kernel: (scratch bytes per lane, spilled SGPRs, spilled VGPRs, static LDS bytes per block)} of every new kernel, and the
-    report's remark lines (what profiles/sample_exclude/resource_usage.txt holds)."""
+    """{kernel: (scratch bytes per lane, spilled SGPRs, spilled VGPRs, static LDS bytes per block)} of the lookup kernels, and the
+    report's remark lines (what profiles/sample_exclude/resource_usage.txt holds; the sampling kernel, with and without a list, is
+    tests/test_sample_host.py's)."""
     src = os.path.join(str(workdir), "exclude.hip")
     with open(src, "w") as f:
         f.write(SOURCE)
@@ -438,17 +440,16 @@ def resource_usage(workdir):
     usage = {}
     for block in run.stderr.split("remark: Function Name: ")[1:]:
         name = block.split(" ")[0].strip()
-        if "sample_neighbors_excluding_kernel" in name or "find_edges_kernel" in name:
+        if "find_edges_kernel" in name:
             grab = lambda key: int(re.search(key + r": (\d+)", block).group(1))  # noqa: E731
             usage[name] = (grab(r"ScratchSize \[bytes/lane\]"), grab("SGPRs Spill"), grab("VGPRs Spill"), grab(r"LDS Size \[bytes/block\]"))
-    report = [line[line.index("voltrix/neighbor_sample_exclude_kernels.hpp"):] for line in run.stderr.splitlines()
-              if "remark:" in line and "voltrix/neighbor_sample_exclude_kernels.hpp" in line]
+    report = [line[line.index("voltrix/find_edges_kernels.hpp"):] for line in run.stderr.splitlines()
+              if "remark:" in line and "voltrix/find_edges_kernels.hpp" in line]
     return usage, "\n".join(report) + "\n"
 
 
 def test_every_kernel_compiles_without_scratch_spills_or_lds(tmp_path):
     usage, _ = resource_usage(tmp_path)
-    # with and without replacement, the lower bound and the scan.  The static LDS is 0 everywhere (a promoted per-lane array would show
-    # here); the dynamic LDS of the kernel without replacement is the launch's, 256 k 4 bytes
-    assert len(usage) == 4 and len([n for n in usage if "sample_neighbors_excluding_kernel" in n]) == 2, sorted(usage)
+    # the lower bound and the scan.  The static LDS is 0 (a promoted per-lane array would show here)
+    assert len(usage) == 2, sorted(usage)
     assert all(v == (0, 0, 0, 0) for v in usage.values()), usage

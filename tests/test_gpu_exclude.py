@@ -155,6 +155,33 @@ def test_an_empty_exclude_is_none_and_a_strided_view_is_its_contiguous_copy(cuda
         _assert_same(_sample(fanout, replace, tail), _want(fanout, replace), "offset")
 
 
+@pytest.mark.parametrize("replace", [0, 1])
+@pytest.mark.parametrize("fanout", [2, None])
+def test_the_two_c_symbols_write_the_same_bits_without_a_list(cuda_device, fanout, replace):
+    """``voltrix_launch_sample_neighbors`` and ``voltrix_launch_sample_neighbors_excluding`` with ``(NULL, 0)`` on the same seeds and
+    the same ``s_indptr`` (the plain rule's), into buffers poisoned with different bytes: every element equal, and the plain oracle's.
+    (An empty list takes the launch without a list; a list that holds none of a row's entries is
+    test_sample_neighbors_with_exclude_is_exactly_the_oracle's ``free`` rows.)"""
+    from voltrix import capi
+
+    g = _graph()
+    want = sample_oracle.sample_neighbors(g.indptr, g.indices, g.seeds, fanout, SEED, OFFSET, bool(replace))
+    s_indptr, total = _dev(want[0]), int(want[0][-1])
+    head = (g.d_indptr.data_ptr(), g.d_indices.data_ptr(), NUM_ROWS, g.d_seeds.data_ptr(), NUM_SEEDS, s_indptr.data_ptr(), total,
+            capi.SAMPLE_ALL if fanout is None else fanout, replace, SEED, OFFSET)
+    stream = torch.cuda.current_stream().cuda_stream
+    out = {}
+    for name, byte, middle in (("voltrix_launch_sample_neighbors", 0x00, ()), ("voltrix_launch_sample_neighbors_excluding", 0xFF, (0, 0))):
+        with poisoned(byte) as state:
+            out[name] = torch.empty(total, dtype=torch.int32, device=DEV), torch.empty(total, dtype=torch.int32, device=DEV)
+        assert state.filled == 2 and total > NUM_SEEDS
+        assert capi._call(name, *head, *middle, out[name][0].data_ptr(), out[name][1].data_ptr(), stream) == 0, name
+    torch.cuda.synchronize()
+    (plain_indices, plain_entries), (list_indices, list_entries) = out.values()
+    assert torch.equal(plain_indices, list_indices) and torch.equal(plain_entries, list_entries)
+    _assert_same((s_indptr, plain_indices, plain_entries), want, "the plain rule")
+
+
 def test_an_invalid_exclude_is_a_value_error(cuda_device):
     g = _graph()
     nnz = g.indices.size

@@ -1,8 +1,9 @@
 """CPU: the neighbour sampling rule and its plumbing.  The numpy restatement (tests/sample_oracle.py) reproduces the
-known answers and draws uniformly; a stand-alone host program runs the header's own ``sample_row_positions`` -- the code the kernel runs
--- and agrees with it line by line; the four entry points are declared, bound and exported; their argument checks answer on the host
-before any launch; the Python layer raises before it looks at a tensor; every kernel compiles for gfx950 without scratch and without
-spilled registers.  No GPU compute is called here (tests/test_gpu_sample.py compares the kernels with the same oracle)."""
+known answers and draws uniformly; a stand-alone host program runs the header's own ``sample_row`` -- the code the kernel runs, here
+the instantiation of a launch without an exclusion list (tests/test_exclude_host.py runs the other, with and without a list) -- and
+agrees with it line by line; the four entry points are declared, bound and exported; their argument checks answer on the host before
+any launch; the Python layer raises before it looks at a tensor; every kernel compiles for gfx950 without scratch and without spilled
+registers.  No GPU compute is called here (tests/test_gpu_sample.py compares the kernels with the same oracle)."""
 import ctypes
 import itertools
 import os
@@ -111,13 +112,20 @@ int main(int argc, char** argv) {
                              offset = std::strtoull(argv[i + 4], nullptr, 10);
     const int d = std::atoi(argv[i + 1]), k = std::atoi(argv[i + 2]);
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), off0 = (uint32_t)offset, off1 = (uint32_t)(offset >> 32);
+    // the row function without a list, on a row that begins at entry 0 and whose columns are its positions: entry ids = positions
+    std::vector<int> row(d), cols(k), entries(k);
+    for (int j = 0; j < d; ++j) row[j] = j;
     ArraySlots slot{std::vector<int>(k, -1)};
-    voltrix::sample_row_positions((uint32_t)r, d, k, k0, k1, off0, off1, slot);
+    voltrix::sample_row<false, false>(row.data(), nullptr, 0, (uint32_t)r, 0, d, k, k, k0, k1, off0, off1, slot, cols.data(),
+                                      entries.data());
+    if (cols != entries) return 6;
     std::printf("f");
-    for (int j = 0; j < k; ++j) std::printf(" %d", slot.get(j));
-    voltrix::SampleDraws draw{(uint32_t)r, k0, k1, off0, off1, {}};
+    for (int j = 0; j < k; ++j) std::printf(" %d", entries[j]);
+    voltrix::sample_row<true, false>(row.data(), nullptr, 0, (uint32_t)r, 0, d, k, k, k0, k1, off0, off1, slot, cols.data(),
+                                     entries.data());
+    if (cols != entries) return 6;
     std::printf("\nr");
-    for (int j = 0; j < k; ++j) std::printf(" %d", voltrix::sample_replace_position(draw(j), d));
+    for (int j = 0; j < k; ++j) std::printf(" %d", entries[j]);
     std::printf("\n");
   }
   return 0;
@@ -267,8 +275,10 @@ def test_python_layer_rejects_bad_arguments_before_any_tensor_is_looked_at():
 
 SOURCE = r'''
 #include "voltrix/neighbor_sample_kernels.hpp"
-template __global__ void voltrix::sample_neighbors_kernel<false>(const voltrix::SampleNeighborsArgs);
-template __global__ void voltrix::sample_neighbors_kernel<true>(const voltrix::SampleNeighborsArgs);
+template __global__ void voltrix::sample_neighbors_kernel<false, false>(const voltrix::SampleNeighborsArgs);
+template __global__ void voltrix::sample_neighbors_kernel<true, false>(const voltrix::SampleNeighborsArgs);
+template __global__ void voltrix::sample_neighbors_kernel<false, true>(const voltrix::SampleNeighborsArgs);
+template __global__ void voltrix::sample_neighbors_kernel<true, true>(const voltrix::SampleNeighborsArgs);
 void* the_mark() { return reinterpret_cast<void*>(&voltrix::block_mark_kernel); }
 void* the_mark_seeds() { return reinterpret_cast<void*>(&voltrix::block_mark_seeds_kernel); }
 void* the_relabel() { return reinterpret_cast<void*>(&voltrix::block_relabel_kernel); }
@@ -289,7 +299,8 @@ def test_every_kernel_compiles_without_scratch_or_spills(tmp_path):
         if any(key in name for key in keys):
             grab = lambda key: int(re.search(key + r": (\d+)", block).group(1))  # noqa: E731
             usage[name] = (grab(r"ScratchSize \[bytes/lane\]"), grab("SGPRs Spill"), grab("VGPRs Spill"), grab(r"LDS Size \[bytes/block\]"))
-    # with and without replacement, and the three relabelling kernels.  The static LDS is 0 everywhere (a promoted per-lane array would
-    # show here); the dynamic LDS of the kernel without replacement is the launch's, 256 k 4 bytes
-    assert len(usage) == 5 and len([n for n in usage if "sample_neighbors_kernel" in n]) == 2, sorted(usage)
+    # with and without replacement, each without and with an exclusion list, and the three relabelling kernels.  The static LDS is 0
+    # everywhere (a promoted per-lane array would show here); the dynamic LDS of the kernels without replacement is the launch's,
+    # 256 k 4 bytes
+    assert len(usage) == 7 and len([n for n in usage if "sample_neighbors_kernel" in n]) == 4, sorted(usage)
     assert all(v == (0, 0, 0, 0) for v in usage.values()), usage

@@ -7,13 +7,21 @@
 
 extern "C" {
 
+void voltrix_launch_sample_neighbors_excluding(void* indptr, void* indices, int num_rows, void* seeds, int num_seeds, void* s_indptr,
+                                               int64_t num_sampled, int fanout, int replace, uint64_t seed, uint64_t offset, void* exclude,
+                                               int num_exclude, void* s_indices, void* s_entries, void* stream, int* return_code) {
+  *return_code = voltrix::launch_sample_neighbors(
+      static_cast<const int*>(indptr), static_cast<const int*>(indices), num_rows, static_cast<const int*>(seeds), num_seeds,
+      static_cast<const int*>(s_indptr), (long long)num_sampled, fanout, replace, seed, offset, static_cast<const int*>(exclude),
+      num_exclude, static_cast<int*>(s_indices), static_cast<int*>(s_entries), static_cast<hipStream_t>(stream));
+}
+
+// the same launch without a list
 void voltrix_launch_sample_neighbors(void* indptr, void* indices, int num_rows, void* seeds, int num_seeds, void* s_indptr,
                                      int64_t num_sampled, int fanout, int replace, uint64_t seed, uint64_t offset, void* s_indices,
                                      void* s_entries, void* stream, int* return_code) {
-  *return_code = voltrix::launch_sample_neighbors(static_cast<const int*>(indptr), static_cast<const int*>(indices), num_rows,
-                                                  static_cast<const int*>(seeds), num_seeds, static_cast<const int*>(s_indptr),
-                                                  (long long)num_sampled, fanout, replace, seed, offset, static_cast<int*>(s_indices),
-                                                  static_cast<int*>(s_entries), static_cast<hipStream_t>(stream));
+  voltrix_launch_sample_neighbors_excluding(indptr, indices, num_rows, seeds, num_seeds, s_indptr, num_sampled, fanout, replace, seed,
+                                            offset, nullptr, 0, s_indices, s_entries, stream, return_code);
 }
 
 void voltrix_launch_block_mark(void* cols, int64_t num_sampled, int num_cols, void* table, void* stream, int* return_code) {

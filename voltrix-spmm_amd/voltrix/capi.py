@@ -944,19 +944,26 @@ SAMPLE_ALL, SAMPLE_MAX_FANOUT = -1, 64      # `fanout` of voltrix_launch_sample_
 
 
 def launch_sample_neighbors(indptr, indices, num_rows: int, seeds, s_indptr, num_sampled: int, fanout: int, replace: bool, seed: int,
-                            offset: int, s_indices, s_entries, stream) -> None:
+                            offset: int, s_indices, s_entries, stream, exclude=None) -> None:
     """At most ``fanout`` entries of every seed row of a device int32 CSR by the sampling rule of voltrix/neighbor_sample_kernels.hpp:
     ``s_indices`` / ``s_entries`` int32 [num_sampled] get the global column ids and the CSR entry ids, in the segments ``s_indptr``
-    (int32 [S + 1], the prefix sum of the rule's per-seed counts) gives; see include/voltrix_capi.h."""
+    (int32 [S + 1], the prefix sum of the rule's per-seed counts) gives.  ``exclude``: ``None``, or device int32 CSR entry ids,
+    strictly ascending, that no row returns (``s_indptr`` counts with ``d'`` then; the call goes through
+    ``voltrix_launch_sample_neighbors_excluding``, the same launch with a list); see include/voltrix_capi.h."""
     import torch
 
-    for t in (indptr, indices, seeds, s_indptr, s_indices, s_entries):
+    for t in (indptr, indices, seeds, s_indptr, s_indices, s_entries) + (() if exclude is None else (exclude,)):
         assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
     assert indptr.numel() == num_rows + 1 and s_indptr.numel() == seeds.numel() + 1
     assert s_indices.numel() == num_sampled == s_entries.numel()
-    _checked("voltrix_launch_sample_neighbors", indptr.data_ptr(), indices.data_ptr(), num_rows, seeds.data_ptr(), seeds.numel(),
-             s_indptr.data_ptr(), num_sampled, int(fanout), int(bool(replace)), int(seed), int(offset), s_indices.data_ptr(),
-             s_entries.data_ptr(), stream)
+    head = (indptr.data_ptr(), indices.data_ptr(), num_rows, seeds.data_ptr(), seeds.numel(), s_indptr.data_ptr(), num_sampled,
+            int(fanout), int(bool(replace)), int(seed), int(offset))
+    tail = (s_indices.data_ptr(), s_entries.data_ptr(), stream)
+    if exclude is None:
+        _checked("voltrix_launch_sample_neighbors", *head, *tail)
+    else:
+        _checked("voltrix_launch_sample_neighbors_excluding", *head, exclude.data_ptr() if exclude.numel() else None, exclude.numel(),
+                 *tail)
 
 
 def launch_block_mark(cols, num_cols: int, table, stream) -> None:
@@ -1059,22 +1066,6 @@ def launch_edge_endpoints(indptr, indices, num_rows: int, entries, rows, cols, s
     assert indptr.numel() == num_rows + 1 and rows.numel() == entries.numel() == cols.numel()
     _checked("voltrix_launch_edge_endpoints", indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), entries.data_ptr(),
              entries.numel(), rows.data_ptr(), cols.data_ptr(), stream)
-
-
-def launch_sample_neighbors_excluding(indptr, indices, num_rows: int, seeds, s_indptr, num_sampled: int, fanout: int, replace: bool,
-                                      seed: int, offset: int, exclude, s_indices, s_entries, stream) -> None:
-    """``launch_sample_neighbors`` among the entries of every seed row that are not in ``exclude`` (device int32 CSR entry ids, strictly
-    ascending), by the exclusion rule of voltrix/neighbor_sample_exclude_kernels.hpp; ``s_indptr`` is the prefix sum of the rule's
-    counts with ``d'`` in place of ``d``; see include/voltrix_capi.h."""
-    import torch
-
-    for t in (indptr, indices, seeds, s_indptr, exclude, s_indices, s_entries):
-        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
-    assert indptr.numel() == num_rows + 1 and s_indptr.numel() == seeds.numel() + 1
-    assert s_indices.numel() == num_sampled == s_entries.numel()
-    _checked("voltrix_launch_sample_neighbors_excluding", indptr.data_ptr(), indices.data_ptr(), num_rows, seeds.data_ptr(),
-             seeds.numel(), s_indptr.data_ptr(), num_sampled, int(fanout), int(bool(replace)), int(seed), int(offset),
-             exclude.data_ptr() if exclude.numel() else None, exclude.numel(), s_indices.data_ptr(), s_entries.data_ptr(), stream)
 
 
 def launch_find_edges(indptr, indices, num_rows: int, rows, cols, assume_sorted: bool, out, stream) -> None:

@@ -1,32 +1,55 @@
 // Voltrix-SpMM for MI355X (gfx950) -- neighbour sampling on a device CSR and the relabelling of a sampled block:
-//   (s_indices, s_entries) = for every seed row, at most `fanout` of its entries (their column ids and their CSR entry ids)
+//   (s_indices, s_entries) = for every seed row, at most `fanout` of its entries that are not in `exclude` (their column ids and their
+//                            CSR entry ids)
 //   (src_ids, local)       = the block's source nodes -- the seeds first, then the other sampled columns in ascending id -- and
 //                            every sampled column as a position in src_ids
 // What produces the rectangular [num_dst, num_src] patterns that every CSR operator here takes (spmm_csr_*, sddmm, attn_aggregate,
-// spmm_csr_reduce): GraphSAGE-style mini-batches.  No reference counterpart.
+// spmm_csr_reduce): GraphSAGE-style mini-batches; the exclusion list keeps the edges (and their reverses) a link-prediction decoder is
+// asked to predict out of the blocks its encoder aggregates over (DGL's exclude="reverse_id").  No reference counterpart.
 //
-// THE SAMPLING RULE (the contract; voltrix/sampling.py and DESIGN.md 3.23 restate it, tests/sample_oracle.py is the numpy restatement).
-// For a seed row r (its GLOBAL row id), fan-out k, degree d = indptr[r + 1] - indptr[r], a 64-bit seed and a 64-bit offset:
+// THE SAMPLING RULE (the contract; voltrix/sampling.py and DESIGN.md 3.23 / 3.26 restate it, tests/sample_oracle.py and
+// tests/exclude_oracle.py are the numpy restatements).  A seed row r (its GLOBAL row id) with begin = indptr[r], end = indptr[r + 1],
+// d = end - begin; fan-out k; a 64-bit seed and a 64-bit offset; exclude: int32 [X] CSR entry ids, STRICTLY ASCENDING (sorted,
+// distinct), each in [0, nnz).
+//   the candidates   lo = lower_bound(exclude, begin), hi = lower_bound(exclude, end), x = hi - lo.  The excluded positions of the row
+//                are q_i = exclude[lo + i] - begin, i = 0 .. x - 1, ascending; the CANDIDATES are the d' = d - x positions of the row
+//                not among them, in CSR order.  Candidate number t is position cand(t) = t + #{ i : q_i - i <= t }; q_i - i does not
+//                decrease, so cand(t) is one binary search over the row's slice of exclude: O(log x).  Everything below selects
+//                candidate NUMBERS in 0 .. d' - 1 and outputs them through cand.
+//                x = 0 -- NO LIST (null or X = 0, the plain call), or a row none of whose entries is excluded: d' = d and
+//                cand(t) = t.  Such a row gets the same bits with and without a list.
 //   draw(r, i)   word i & 3 of Philox4x32-10(counter = (r, (i >> 2) | 0x80000000, offset & 0xffffffff, offset >> 32),
 //                key = (seed & 0xffffffff, seed >> 32)).  Bit 31 of counter word 1 separates these draws from the dropout mask's
 //                (edge, h >> 2, ...) counters (dropout_mask_kernels.hpp: h >> 2 < 2^29), so one seed for both gives unrelated streams.
-//   without replacement, d <= k   every entry of the row, in CSR order; no draw is used.  "all" (fan-out kSampleAll, Python's
-//                fanout=None) means this for every row, with or without replacement.
-//   without replacement, d > k    Floyd's algorithm on entry POSITIONS 0 .. d - 1: for i = 0 .. k - 1, j = d - k + i,
-//                t = (uint64(draw(r, i)) * (j + 1)) >> 32; take t unless it is taken already, then take j.  The k positions are output
-//                in ASCENDING order: a sampled row keeps CSR order, sorted rows stay sorted.  A function of (seed, offset, r, d, k)
-//                only -- not of the other seeds of the batch, their order or the launch geometry.  Every k-subset is equally likely up
-//                to the multiply-shift's bias: t's values differ in probability by at most a relative (j + 1) / 2^32 <= d / 2^32.
-//   with replacement, d > 0       exactly k entries; entry i is at position (uint64(draw(r, i)) * d) >> 32, in draw order.  d == 0: none.
+//   without replacement, d' <= k  every candidate, in CSR order; no draw is used.  "all" (fan-out kSampleAll, Python's fanout=None)
+//                means this for every row, with or without replacement.
+//   without replacement, d' > k   Floyd's algorithm on 0 .. d' - 1: for i = 0 .. k - 1, j = d' - k + i,
+//                t = (uint64(draw(r, i)) * (j + 1)) >> 32; take t unless it is taken already, then take j.  The k numbers are output
+//                in ASCENDING order and cand ascends: a sampled row keeps CSR order, sorted rows stay sorted.  Every k-subset is equally
+//                likely up to the multiply-shift's bias: t's values differ in probability by at most a relative (j + 1) / 2^32
+//                <= d / 2^32.
+//   with replacement, d' > 0      exactly k entries; entry i is cand((uint64(draw(r, i)) * d') >> 32), in draw order.  d' == 0: none.
+// The result is a function of (seed, offset, r, d', k) and the row's excluded positions only -- not of the other seeds of the batch,
+// their order or the launch geometry; s_entries holds ids into the ORIGINAL indices.
 //
-// sample_neighbors_kernel: one lane per seed row, 256 lanes per workgroup.  Per row O(k^2) compares and k four-byte gathers from
-// `indices` -- not a function of the degree: a 67k-entry hub row costs what a row of degree k + 1 costs (no hub-row weakness, unlike the
-// row-per-group kernels).  The sorted positions of Floyd's algorithm live in dynamic LDS, slot-major: slot[j * 256 + lane] -- bank
-// lane mod 32 for every j, so lanes that insert at different depths do not conflict; 256 k 4 bytes, k <= 64 (64 KiB: two workgroups per
-// CU).  No per-lane array in registers, hence no scratch.  The replacement path and "all" use no LDS.  "all" copies a row with its one
-// lane: O(d) per lane there, the one path whose cost follows the degree.
+// sample_neighbors_kernel<REPLACE, EXCLUDE>: one lane per seed row, 256 lanes per workgroup, one body (sample_row) for every call.
+// EXCLUDE = false is what a launch without a list gets: x = 0 at compile time, so the searches and the merge fold away and the plain
+// call runs the instructions it always ran (with x = 0 only at run time its launches without replacement took 2 - 8 % longer:
+// DESIGN.md 3.26).  Per row O(k^2) compares and k four-byte gathers from `indices`, with a list two binary searches in exclude
+// (O(log X)) and one per output entry (O(log x)) on top -- not a function of the degree: a 67k-entry hub row costs what a row of
+// degree k + 1 costs (no hub-row weakness, unlike the row-per-group kernels).  The sorted numbers of Floyd's algorithm live in dynamic LDS, slot-major: slot[j * 256 + lane] -- bank lane mod 32 for every j, so lanes
+// that insert at different depths do not conflict; 256 k 4 bytes, k <= 64 (64 KiB: two workgroups per CU).  No per-lane array in
+// registers, hence no scratch.  The replacement path and "all" use no LDS.  "all" and d' <= k walk the row against its slice of exclude
+// with the row's one lane: O(d) per lane there, the one path whose cost follows the degree.
 // A seed outside [0, num_rows) has degree 0 inside the kernel (never an out-of-bounds read); a row never writes more than its segment
-// s_indptr[i + 1] - s_indptr[i] holds.
+// s_indptr[i + 1] - s_indptr[i] holds, and with d' = max(d - x, 0) and cand(t) <= t + x every read of indices stays inside the row
+// whatever exclude holds (a list that is not strictly ascending gives unspecified entries of the row, never an out-of-bounds access).
+//
+// KNOWN ANSWERS (tests/test_exclude_host.py): the ring with row v = {v + 1, v + 7, v + 31} mod 100, exclude = [0, 15] (the first entry
+// of rows 0 and 5), seeds = [0, 5, 99, 0, 42], k = 2, seed 9, offset 0.  Rows 0 and 5 have d' = 2; rows 99 and 42 have nothing
+// excluded and get the bits of the call without a list.  s_indptr = [0, 2, 4, 6, 8, 10] both times.
+//   without replacement:   s_indices [7, 31, 12, 36, 6, 30, 7, 31, 43, 49], s_entries [1, 2, 16, 17, 298, 299, 1, 2, 126, 127]
+//   with replacement:      s_indices [7, 31, 36, 36, 30, 6, 7, 31, 49, 49], s_entries [1, 2, 17, 17, 299, 298, 1, 2, 127, 127]
 //
 // Relabelling: a dense table int32 [num_cols], ZERO on entry.  block_mark: table[c] = 1 for every sampled column (plain stores of one
 // value); block_mark_seeds, a later launch on the same stream: table[seeds[i]] = -(i + 1) -- the seeds win.  The caller takes the
@@ -86,15 +109,95 @@ __host__ __device__ inline void sample_row_positions(uint32_t r, int d, int k, u
 // position i of the replacement rule
 __host__ __device__ inline int sample_replace_position(uint32_t x, int d) { return (int)(((uint64_t)x * (uint64_t)d) >> 32); }
 
+// the first index in [0, n) of the ascending list `list` whose value is not below v; n if there is none
+__host__ __device__ inline int exclude_lower_bound(const int* list, int n, int v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (list[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// x, the number of entries of the row [begin, end) that `exclude` [num_exclude] holds, and in *first the index lo of the first of
+// them: the row's slice is exclude[lo .. lo + x).  Never negative, whatever the list holds; num_exclude == 0: 0, and nothing is read.
+__host__ __device__ inline int exclude_row_count(const int* exclude, int num_exclude, int begin, int end, int* first) {
+  const int lo = exclude_lower_bound(exclude, num_exclude, begin);
+  const int hi = lo + exclude_lower_bound(exclude + lo, num_exclude - lo, end);
+  *first = lo;
+  return hi - lo;
+}
+
+// cand(t): the position in the row of candidate number t.  `slice` = the row's x excluded entry ids, ascending; begin = indptr[r].
+// q_i - i with q_i = slice[i] - begin does not decrease: the count of i with q_i - i <= t is the first i where it is above t.
+// x == 0: t, and nothing is read.
+__host__ __device__ inline int exclude_cand(const int* slice, int x, int begin, int t) {
+  int lo = 0, hi = x;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (slice[mid] - begin - mid <= t) lo = mid + 1; else hi = mid;
+  }
+  return t + lo;
+}
+
+// One seed row by the rule above: row r = entries [begin, begin + d) with d > 0, fan-out k (INT_MAX: "all"), room > 0 elements in
+// out_col / out_entry; exclude [num_exclude], (nullptr, 0) for no list.  EXCLUDE = false promises num_exclude == 0 and gives the same
+// bits as EXCLUDE = true does then.  `slot` as for sample_row_positions (used only where d' > k without replacement).  The kernel and
+// the host programs of the tests run this code.
+template <bool REPLACE, bool EXCLUDE = true, class Slots>
+__host__ __device__ inline void sample_row(const int* indices, const int* exclude, int num_exclude, uint32_t r, int begin, int d, int k,
+                                           int room, uint32_t k0, uint32_t k1, uint32_t off0, uint32_t off1, Slots& slot, int* out_col,
+                                           int* out_entry) {
+  int first = 0;
+  const int x = EXCLUDE ? exclude_row_count(exclude, num_exclude, begin, begin + d, &first) : 0;
+  const int* const slice = exclude + first;          // the row's excluded entry ids
+  const int dc = d - x;                              // d': the candidates
+  if (dc <= 0) return;
+  if (k == INT_MAX || (!REPLACE && dc <= k)) {       // every candidate, in CSR order: the row merged against its slice
+    const int count = dc < room ? dc : room;
+    int next = 0, written = 0;
+    for (int j = 0; j < d && written < count; ++j) {
+      if (next < x && slice[next] == begin + j) {
+        ++next;
+        continue;
+      }
+      out_entry[written] = begin + j;
+      out_col[written] = indices[(long long)begin + j];
+      ++written;
+    }
+    return;
+  }
+  const int count = k < room ? k : room;             // == k for an s_indptr made by the rule
+  if constexpr (REPLACE) {
+    SampleDraws draw{r, k0, k1, off0, off1, {}};
+    for (int j = 0; j < k; ++j) {
+      const int e = begin + exclude_cand(slice, x, begin, sample_replace_position(draw(j), dc));
+      if (j < count) {
+        out_entry[j] = e;
+        out_col[j] = indices[e];
+      }
+    }
+  } else {
+    sample_row_positions(r, dc, k, k0, k1, off0, off1, slot);
+    for (int j = 0; j < count; ++j) {
+      const int e = begin + exclude_cand(slice, x, begin, slot.get(j));
+      out_entry[j] = e;
+      out_col[j] = indices[e];
+    }
+  }
+}
+
 struct SampleNeighborsArgs {
   const int* indptr;     // [num_rows + 1]
   const int* indices;    // [entries]
   const int* seeds;      // [num_seeds] global row ids
   const int* s_indptr;   // [num_seeds + 1] where every seed's entries go
+  const int* exclude;    // [num_exclude] CSR entry ids, strictly ascending; may be null where num_exclude == 0
   int* s_indices;        // [num_sampled] global column ids
   int* s_entries;        // [num_sampled] CSR entry ids
   int num_rows;
   int num_seeds;
+  int num_exclude;
   int k;                 // 1 .. 64, or INT_MAX for "all"
   uint32_t k0, k1;       // seed
   uint32_t off0, off1;   // offset
@@ -106,9 +209,9 @@ struct LdsSlots {
   __device__ inline void set(int j, int v) { base[j * 256] = v; }
 };
 
-template <bool REPLACE>
+template <bool REPLACE, bool EXCLUDE>
 static __global__ __launch_bounds__(256) void sample_neighbors_kernel(const SampleNeighborsArgs a) {
-  extern __shared__ __attribute__((aligned(16))) int sample_slots[];          // [k][256], only where a row has d > k
+  extern __shared__ __attribute__((aligned(16))) int sample_slots[];          // [k][256], only where a row has d' > k
   const long long i = (long long)blockIdx.x * 256 + (int)threadIdx.x;
   if (i >= a.num_seeds) return;
   const int r = a.seeds[i];
@@ -119,59 +222,39 @@ static __global__ __launch_bounds__(256) void sample_neighbors_kernel(const Samp
   }
   const long long base = a.s_indptr[i];
   const int room = a.s_indptr[i + 1] - a.s_indptr[i];
-  int* const out_col = a.s_indices + base;
-  int* const out_entry = a.s_entries + base;
   if (d <= 0 || room <= 0) return;
-  if (a.k == INT_MAX || (!REPLACE && d <= a.k)) {    // every entry, in CSR order ("all": k = INT_MAX)
-    const int count = d < room ? d : room;
-    for (int j = 0; j < count; ++j) {
-      out_entry[j] = begin + j;
-      out_col[j] = a.indices[(long long)begin + j];
-    }
-    return;
-  }
-  const int count = a.k < room ? a.k : room;         // == k for an s_indptr made by the rule
-  if constexpr (REPLACE) {
-    SampleDraws draw{(uint32_t)r, a.k0, a.k1, a.off0, a.off1, {}};
-    for (int j = 0; j < a.k; ++j) {
-      const int e = begin + sample_replace_position(draw(j), d);
-      if (j < count) {
-        out_entry[j] = e;
-        out_col[j] = a.indices[e];
-      }
-    }
-  } else {
-    LdsSlots slot{sample_slots + (int)threadIdx.x};
-    sample_row_positions((uint32_t)r, d, a.k, a.k0, a.k1, a.off0, a.off1, slot);
-    for (int j = 0; j < count; ++j) {
-      const int e = begin + slot.get(j);
-      out_entry[j] = e;
-      out_col[j] = a.indices[e];
-    }
-  }
+  LdsSlots slot{sample_slots + (int)threadIdx.x};
+  sample_row<REPLACE, EXCLUDE>(a.indices, a.exclude, a.num_exclude, (uint32_t)r, begin, d, a.k, room, a.k0, a.k1, a.off0, a.off1, slot,
+                      a.s_indices + base, a.s_entries + base);
 }
 
-// fanout: 1 .. 64, or kSampleAll.  s_indptr must be the rule's: s_indptr[i + 1] - s_indptr[i] = min(d_i, fanout) without replacement,
-// (d_i > 0 ? fanout : 0) with it, d_i for kSampleAll, d_i = 0 for a seed outside [0, num_rows); num_sampled = s_indptr[num_seeds].
-// Every element of s_indices and s_entries is written then; neither needs initialising.  Nothing else is checked on the device.
+// fanout: 1 .. 64, or kSampleAll.  exclude = device int32 [num_exclude], strictly ascending ids in [0, entries) (not checked on the
+// device); (nullptr, 0): no list.  s_indptr must be the rule's: s_indptr[i + 1] - s_indptr[i] = min(d'_i, fanout) without
+// replacement, (d'_i > 0 ? fanout : 0) with it, d'_i for kSampleAll, d'_i = 0 for a seed outside [0, num_rows); num_sampled =
+// s_indptr[num_seeds].  Every element of s_indices and s_entries is written then; neither needs initialising.  Nothing else is checked
+// on the device.
 inline int launch_sample_neighbors(const int* indptr, const int* indices, int num_rows, const int* seeds, int num_seeds,
                                    const int* s_indptr, long long num_sampled, int fanout, int replace, uint64_t seed, uint64_t offset,
-                                   int* s_indices, int* s_entries, hipStream_t stream) {
-  if (num_rows < 0 || num_seeds < 0 || num_sampled < 0 || num_sampled > INT_MAX) return kErrBadShape;
+                                   const int* exclude, int num_exclude, int* s_indices, int* s_entries, hipStream_t stream) {
+  if (num_rows < 0 || num_seeds < 0 || num_exclude < 0 || num_sampled < 0 || num_sampled > INT_MAX) return kErrBadShape;
   if (fanout != kSampleAll && (fanout < 1 || fanout > kSampleMaxFanout)) return kErrBadShape;
   if (replace != 0 && replace != 1) return kErrBadShape;
   if (num_seeds == 0) return kOk;
   if (bad_ptr(indptr, 3) || bad_ptr(seeds, 3) || bad_ptr(s_indptr, 3)) return kErrBadShape;
+  if (num_exclude > 0 ? bad_ptr(exclude, 3) : misaligned(exclude, 3)) return kErrBadShape;
   if (num_sampled > 0 && (bad_ptr(indices, 3) || bad_ptr(s_indices, 3) || bad_ptr(s_entries, 3))) return kErrBadShape;
   if (num_sampled == 0) return kOk;                  // nothing to write
   const bool all = fanout == kSampleAll;
-  const SampleNeighborsArgs a{indptr, indices, seeds, s_indptr, s_indices, s_entries, num_rows, num_seeds, all ? INT_MAX : fanout,
-                              (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
+  const SampleNeighborsArgs a{indptr, indices, seeds, s_indptr, exclude, s_indices, s_entries, num_rows, num_seeds, num_exclude,
+                              all ? INT_MAX : fanout, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
   const dim3 grid((unsigned)(((long long)num_seeds + 255) / 256));
+  const size_t lds = (size_t)256 * fanout * sizeof(int);
   if (replace || all)
-    hipLaunchKernelGGL((sample_neighbors_kernel<true>), grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((num_exclude > 0 ? sample_neighbors_kernel<true, true> : sample_neighbors_kernel<true, false>), grid, dim3(256),
+                       0, stream, a);
   else
-    hipLaunchKernelGGL((sample_neighbors_kernel<false>), grid, dim3(256), (size_t)256 * fanout * sizeof(int), stream, a);
+    hipLaunchKernelGGL((num_exclude > 0 ? sample_neighbors_kernel<false, true> : sample_neighbors_kernel<false, false>), grid,
+                       dim3(256), lds, stream, a);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
 }
 

@@ -25,9 +25,9 @@ GLOBAL row id), fan-out ``k``, degree ``d = indptr[r + 1] - indptr[r]``, a 64-bi
 * ``replace=True``, ``d > 0``: exactly ``k`` entries; entry ``i`` is at position ``(uint64(draw(r, i)) * d) >> 32``, in draw order.  A
   row with ``d == 0`` gives none.
 
-THE EXCLUSION RULE (the contract; DESIGN.md 3.26, voltrix/neighbor_sample_exclude_kernels.hpp, ``tests/exclude_oracle.py`` is the numpy
-restatement).  ``exclude`` is a device int32 ``[X]`` of CSR entry ids, STRICTLY ASCENDING (sorted, distinct), each in ``[0, nnz)``.  For
-a seed row ``r`` with ``begin = indptr[r]``, ``end = indptr[r + 1]``, ``d = end - begin``:
+THE EXCLUSION RULE (the same contract -- the kernel header states one rule, of which the above is the case ``x = 0``; DESIGN.md 3.26,
+``tests/exclude_oracle.py`` is the numpy restatement).  ``exclude`` is a device int32 ``[X]`` of CSR entry ids, STRICTLY ASCENDING
+(sorted, distinct), each in ``[0, nnz)``.  For a seed row ``r`` with ``begin = indptr[r]``, ``end = indptr[r + 1]``, ``d = end - begin``:
 
 * ``lo = lower_bound(exclude, begin)``, ``hi = lower_bound(exclude, end)``, ``x = hi - lo``; the excluded positions of the row are
   ``q_i = exclude[lo + i] - begin``, ``i = 0 .. x - 1``, ascending.
@@ -86,7 +86,7 @@ def sample_neighbors(indptr: torch.Tensor, indices: torch.Tensor, seeds: torch.T
     ``fanout`` outside 1..64 that is not ``None`` and a ``seed`` or ``offset`` outside ``[0, 2^64)``.
 
     ``exclude``: ``None`` (the call as it always was), or a device int32 tensor of CSR entry ids, strictly ascending and in
-    ``[0, nnz)``, that no row may return: the module's exclusion rule, through a kernel of its own.  The degrees become ``d'`` by two
+    ``[0, nnz)``, that no row may return: the module's exclusion rule, through the same kernel.  The degrees become ``d'`` by two
     ``torch.searchsorted`` calls; "``exclude`` is not strictly ascending or leaves ``[0, nnz)``" is a third value of the same one
     read-back and a ``ValueError``.  An empty ``exclude`` gives the bits of ``None``; a row without an excluded entry gets them too."""
     from . import capi
@@ -111,11 +111,11 @@ def sample_neighbors(indptr: torch.Tensor, indices: torch.Tensor, seeds: torch.T
     bad = (rows < 0) | (rows >= num_rows)
     rows = rows.clamp(0, num_rows - 1)
     degree = torch.where(bad, torch.zeros_like(rows), (indptr[rows + 1] - indptr[rows]).long())
-    bad_exclude = None
+    flags = [bad.any()]                              # what the one read-back carries next to the total
     if exclude is not None:                          # d' = d - x, x = the entries of the row's range that `exclude` holds
         held = torch.searchsorted(exclude, indptr[rows + 1].contiguous()) - torch.searchsorted(exclude, indptr[rows].contiguous())
         degree = torch.where(bad, torch.zeros_like(rows), (degree - held).clamp(min=0))
-        bad_exclude = (exclude[1:] <= exclude[:-1]).any() | (exclude[0] < 0) | (exclude[-1] >= indices.numel())
+        flags.append((exclude[1:] <= exclude[:-1]).any() | (exclude[0] < 0) | (exclude[-1] >= indices.numel()))
     if fanout is None:
         taken = degree
     elif replace:
@@ -123,12 +123,9 @@ def sample_neighbors(indptr: torch.Tensor, indices: torch.Tensor, seeds: torch.T
     else:
         taken = degree.clamp(max=fanout)
     ends = torch.cumsum(taken, 0)
-    if exclude is None:
-        total, any_bad = torch.stack([ends[-1], bad.any().long()]).tolist()      # the one synchronisation
-    else:
-        total, any_bad, any_bad_exclude = torch.stack([ends[-1], bad.any().long(), bad_exclude.long()]).tolist()   # the one, here
-        if any_bad_exclude:
-            raise ValueError(f"sample_neighbors: exclude must be strictly ascending CSR entry ids in [0, {indices.numel()})")
+    total, any_bad, *any_bad_exclude = torch.stack([ends[-1]] + [flag.long() for flag in flags]).tolist()     # the one synchronisation
+    if any(any_bad_exclude):
+        raise ValueError(f"sample_neighbors: exclude must be strictly ascending CSR entry ids in [0, {indices.numel()})")
     if any_bad:
         raise ValueError(f"sample_neighbors: a seed outside [0, {num_rows})")
     if total > _INT_MAX:
@@ -136,13 +133,8 @@ def sample_neighbors(indptr: torch.Tensor, indices: torch.Tensor, seeds: torch.T
     s_indptr[1:] = ends
     s_indices = torch.empty(total, dtype=torch.int32, device=dev)
     s_entries = torch.empty(total, dtype=torch.int32, device=dev)
-    if exclude is None:
-        capi.launch_sample_neighbors(indptr, indices, num_rows, seeds, s_indptr, total, capi.SAMPLE_ALL if fanout is None else fanout,
-                                     replace, seed, offset, s_indices, s_entries, _raw_stream(dev))
-    else:
-        capi.launch_sample_neighbors_excluding(indptr, indices, num_rows, seeds, s_indptr, total,
-                                               capi.SAMPLE_ALL if fanout is None else fanout, replace, seed, offset, exclude, s_indices,
-                                               s_entries, _raw_stream(dev))
+    capi.launch_sample_neighbors(indptr, indices, num_rows, seeds, s_indptr, total, capi.SAMPLE_ALL if fanout is None else fanout,
+                                 replace, seed, offset, s_indices, s_entries, _raw_stream(dev), exclude=exclude)
     return s_indptr, s_indices, s_entries
 
 
