@@ -34,6 +34,29 @@
  *     The exceptions, each stated again where it applies, are inputs by nature: `output` of the atomic forms (atomic_out = 1,
  *     accumulate = 2: the CALLER ZERO-FILLS it) and of accumulate = 1 / combine passes with accumulate != 0 (it holds the other
  *     addend), and `level` / `rank` of the breadth-first search (the caller sets them to -1 before the first component).
+ *   - Pointers.  Every argument is checked on the host, before any launch and before any other runtime call; the first bad one is
+ *     answered with VOLTRIX_ERR_BAD_SHAPE (VOLTRIX_ERR_BAD_CONFIG / VOLTRIX_ERR_OVERFLOW where an entry point says so) and nothing is
+ *     enqueued.  A pointer is one of three kinds:
+ *       required      every valid call with non-zero sizes gives it an element -- blk_offsets, output, the plan arrays of the panel
+ *                     and fused kernels (the builders pad them), units / runs of the stream kernel, records, tickets of the ticket
+ *                     forms, every header / status / table output a builder writes, `input` of the entry points that take no
+ *                     input_rows (the operand has num_nodes rows at least).  NULL: VOLTRIX_ERR_BAD_SHAPE.
+ *       optional      NULL has the meaning its entry point documents: window_order, out_scale, units (with unit_ptr), row_map,
+ *                     xcd_ptr / panel_xcd_ptr / window_xcd_ptr, panel_order, parts of the ticket form, partials of a table without
+ *                     cut windows or cut panels, the workspace of voltrix_launch_cm_rank without a level above 1024 nodes.
+ *       may be empty  an array that has no element for some valid input, where the launcher cannot tell on the host: hspa_packed and
+ *                     hind of a graph without edges (the number of TC blocks is blk_offsets[W], on the device), edge_list / indices /
+ *                     t_indices / resid_edge_list of a CSR without entries, cuts / runs of a table without any, `input` of the entry
+ *                     points with an input_rows argument (an operator without columns), the workspace of the fused preprocess (its
+ *                     size is a function of the sizes and the path).  NULL is accepted -- hosts that pass an empty tensor's address
+ *                     pass NULL -- and nothing is read through it.
+ *     Alignment: where an entry point states one (16 bytes: input, hspa_packed, units, cuts of the unit table, runs, records,
+ *     tickets, the workspaces of the builders, of the transpose and of voltrix_launch_spmm_f32_as_f16, output of the ticket forms and of the combine pass of the unit table; 8: scale; 4: indptr / indices /
+ *     values of the CSR row-gather kernel, scale of voltrix_launch_scale_rows) an address off by less is VOLTRIX_ERR_BAD_SHAPE, for an
+ *     optional or possibly empty pointer as well.  Sizes that are "nothing to do" (num_nodes == 0, embedding_dim == 0, num_cuts == 0,
+ *     count == 0, max_runs_per_xcd == 0) answer VOLTRIX_OK without a launch and without looking at a pointer, except where an entry
+ *     point writes an output even then (the headers of the count phases, unit_ptr, run_ptr, wave_ptr[0], the padding record, the
+ *     scale of the scaled cast, pointer1[0]: those outputs stay required).  tests/core_abi_cases.py has the role of every parameter.
  */
 #ifndef VOLTRIX_CAPI_H_
 #define VOLTRIX_CAPI_H_
@@ -53,7 +76,8 @@ extern "C" {
 
 enum voltrix_rc {
   VOLTRIX_OK = 0,
-  VOLTRIX_ERR_BAD_SHAPE = 1,  /* negative sizes, embedding_dim % 8 != 0 (fp16) / % 4 (fp32), misaligned pointer */
+  VOLTRIX_ERR_BAD_SHAPE = 1,  /* negative sizes, embedding_dim % 8 != 0 (fp16) / % 4 (fp32), a misaligned pointer, a NULL pointer
+                                 that has to point at something (see "Pointers" above), an enum or a range argument outside its range */
   VOLTRIX_ERR_LAUNCH = 2,     /* hipGetLastError() after the launch */
   VOLTRIX_ERR_BAD_CONFIG = 3, /* tile (fs, depth, waves) not instantiated */
   VOLTRIX_ERR_OVERFLOW = 4,   /* total TC blocks exceed int32 (the handle stores int32 offsets) */
@@ -157,7 +181,12 @@ void voltrix_launch_spmm_bf16_tile(void* blk_offsets, void* hspa_packed, void* h
  *               written).  For handles built from a row-permuted CSR (locality reorder: rows that share columns grouped
  *               into the same 16-row windows -- the reference takes externally reordered graphs, bench/graph_gen.py:42-45):
  *               the product is written through the permutation, there is no un-permute pass, and because column ids are
- *               not relabelled `input` is the caller's B as it is. */
+ *               not relabelled `input` is the caller's B as it is.
+ * Pointers of every block-format launch (voltrix_launch_spmm, _f16, _bf16, their _tile, _sched and _sched_ticket forms and
+ * voltrix_launch_spmm_f32_as_f16): blk_offsets, input and output are required when num_nodes > 0 and embedding_dim > 0; hspa_packed and
+ * hind may be empty (a graph without edges); window_order, out_scale, units, partials and row_map are optional; unit_ptr is required
+ * with units.  A NULL required pointer, a misaligned input / hspa_packed / units (and, in the ticket form, output / tickets):
+ * VOLTRIX_ERR_BAD_SHAPE on the host, before any launch -- voltrix_launch_spmm_f32_as_f16 answers so before it enqueues the cast. */
 void voltrix_launch_spmm_f16_sched(void* blk_offsets, void* hspa_packed, void* hind, int num_nodes, int num_edges,
                                    int embedding_dim, void* input, void* output, int fs, int depth, int waves,
                                    void* window_order, void* out_scale, int atomic_out, void* units, void* unit_ptr,
@@ -463,7 +492,8 @@ void voltrix_spmm_default_tile(int embedding_dim, int is_f16, int* fs, int* dept
 int voltrix_spmm_num_tiles(int is_f16);
 void voltrix_spmm_tile_at(int is_f16, int index, int* fs, int* depth, int* waves);
 
-/* fp32 -> fp16 cast of the dense operand into a caller-provided buffer (count % 8 == 0). */
+/* fp32 -> fp16 cast of the dense operand into a caller-provided buffer (count % 8 == 0).  src and dst: 16-byte aligned, required when
+ * count > 0 (VOLTRIX_ERR_BAD_SHAPE on the host, before any launch, otherwise); count == 0: VOLTRIX_OK, nothing is launched. */
 void voltrix_launch_cast_f32_f16(void* src, void* dst, int64_t count, void* stream, int* return_code);
 
 /* Range-safe variant (what voltrix.spmm uses for fp32 features): dst = fp16(src * 2^-e) with one power-of-two scale
@@ -472,7 +502,9 @@ void voltrix_launch_cast_f32_f16(void* src, void* dst, int64_t count, void* stre
  * aligned; scale[0] <- 2^e, to be passed as `out_scale` of voltrix_launch_spmm_f16_tile (multiplied into every output
  * element in the epilogue; exact).  No host sync.  Inf / NaN in src: scale 1, they propagate as in fp32.  Neither dst nor scale
  * need be initialised: scale[1] is scratch (the bits of max |src|), the head of dst briefly holds one word per workgroup of the
- * reduction -- both are written before they are read -- and the conversion then writes every element of dst. */
+ * reduction -- both are written before they are read -- and the conversion then writes every element of dst.  src and dst: 16-byte
+ * aligned, required when count > 0; scale: always required (count == 0 still writes scale[0] = 1); anything else is
+ * VOLTRIX_ERR_BAD_SHAPE on the host, before any launch. */
 void voltrix_launch_cast_f32_f16_scaled(void* src, void* dst, int64_t count, void* scale, void* stream,
                                         int* return_code);
 
@@ -994,7 +1026,11 @@ void voltrix_launch_csr_fill(void* node_pointer, void* edge_list, int num_nodes,
  *   voltrix_launch_cm_rank: orders every level's queue segment (levels <= 1024 nodes: one workgroup walks runs of them,
  *       LDS bitonic; larger: keys + radix sort, workspace voltrix_cm_rank_workspace_bytes(largest level above 1024) bytes)
  *       and writes rank[v] = base + position (rank int32[num_nodes]).  level_off_host: HOST copy of level_off[0 .. levels].
- *       tie int32[num_nodes].  Afterwards queue[0 .. nodes) is the component's order. */
+ *       tie int32[num_nodes].  Afterwards queue[0 .. nodes) is the component's order.
+ * Pointers: indices / t_indices may be empty (no entries); the transpose needs indptr, indices, t_indices and its workspace only when
+ * num_edges > 0, t_indptr always; everything else is required, level_off_host (read on the HOST) included; the workspace of
+ * voltrix_launch_cm_rank is optional (no level above 1024 nodes).  A NULL required pointer, a misaligned transpose workspace, start
+ * outside [0, num_nodes), num_nodes <= 0 in the search: VOLTRIX_ERR_BAD_SHAPE on the host, before any launch. */
 int64_t voltrix_csr_transpose_workspace_bytes(int64_t num_edges);
 void voltrix_launch_csr_transpose(void* indptr, void* indices, int num_rows, int num_cols, int64_t num_edges, void* workspace,
                                   void* t_indptr, void* t_indices, void* stream, int* return_code);
@@ -1011,7 +1047,9 @@ void voltrix_launch_cm_rank(void* indptr, void* indices, void* t_indptr, void* t
 /* out = inv(chol(gram + eps trace(gram) I))^T for a k x k symmetric positive semi-definite gram (float32, row-major,
  * k <= 64), float32 [k][k]: the small factor of a Cholesky QR (X <- X out has orthonormal columns), on the device so that
  * the spectral row order's subspace iteration (voltrix/reorder.py) has no host sync per step.  One workgroup, double
- * arithmetic.  VOLTRIX_ERR_BAD_SHAPE for k outside 1..64.  Every element of out is written. */
+ * arithmetic.  VOLTRIX_ERR_BAD_SHAPE for k outside 1..64 or a NULL gram / out, on the host, before any launch.  Every element of out is
+ * written (the elements below the diagonal as 0).  gram need not be exactly symmetric: 0.5 (gram + gram^T) is what is factored.  A
+ * pivot that is not positive (a rank-deficient subspace) is replaced by eps trace(gram), or by 1e-300 when that is not positive. */
 void voltrix_launch_chol_inv_transposed(void* gram, int k, double eps, void* out, void* stream, int* return_code);
 
 #ifdef __cplusplus

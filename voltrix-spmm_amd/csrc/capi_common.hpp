@@ -61,6 +61,8 @@ inline int launch_if_ok(const int* blk_offsets, const uint32_t* hspa_packed, con
                         int max_units_per_xcd, float* partials, const int* row_map, int units_per_wave,
                         int* tickets) {
   if constexpr (tile_ok<FS, D, W, EB>()) {
+    // the C-ABI's block-format entry points take no input_rows: the operand has num_nodes rows at least, so it has an element
+    if (num_nodes > 0 && embedding_dim > 0 && input == nullptr) return voltrix::kErrBadShape;
     return voltrix::launch_spmm_tc16<voltrix::SpmmTile<FS, D, W, EB, BF16>>(blk_offsets, hspa_packed, hind, num_nodes,
                                                                        embedding_dim, input, output, stream, order,
                                                                        out_scale, atomic_out, units, unit_ptr,

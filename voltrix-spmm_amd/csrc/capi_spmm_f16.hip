@@ -84,7 +84,9 @@ int64_t voltrix_spmm_f32_workspace_bytes(int64_t input_rows, int embedding_dim) 
 void voltrix_launch_spmm_f32_as_f16(void* blk_offsets, void* hspa_packed, void* hind, int num_nodes, int num_edges,
                                     int embedding_dim, void* input, int64_t input_rows, void* output, void* workspace,
                                     void* stream, int* return_code) {
-  if (input_rows < 0 || workspace == nullptr || ((uintptr_t)workspace & 15) || embedding_dim % 8 != 0) {
+  if (input_rows < 0 || workspace == nullptr || ((uintptr_t)workspace & 15) || embedding_dim % 8 != 0 || num_nodes < 0 ||
+      embedding_dim < 0 || ((uintptr_t)hspa_packed & 15) ||   // what the product would refuse, before the cast is enqueued
+      (num_nodes > 0 && embedding_dim > 0 && (blk_offsets == nullptr || output == nullptr))) {
     *return_code = voltrix::kErrBadShape;
     return;
   }

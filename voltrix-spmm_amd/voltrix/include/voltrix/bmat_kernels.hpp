@@ -39,6 +39,8 @@ inline int preprocess(const int32_t* edgeList, const int32_t* nodePointer, int n
                       int blockSize_w, int32_t* blockPartition, int32_t* edgeToColumn, int32_t* edgeToRow,
                       int32_t* Pointer1) {
   if (num_nodes < 0 || blockSize_h != kBlkH || blockSize_w != kBlkW) return kErrBadShape;
+  // host arrays: Pointer1[0] is always written; the per-edge arrays are empty for a graph without edges
+  if (Pointer1 == nullptr || (num_nodes > 0 && (nodePointer == nullptr || blockPartition == nullptr))) return kErrBadShape;
   const int64_t num_windows = ((int64_t)num_nodes + kBlkH - 1) / kBlkH;
   unsigned hw = std::thread::hardware_concurrency();
   const int64_t num_edges = num_nodes > 0 ? nodePointer[num_nodes] : 0;
@@ -130,6 +132,8 @@ inline int hmat_hip(const int32_t* nodePointer, const int32_t* edgeList, const i
   if (num_row_windows < 0 || num_nodes < 0 || num_edges < 0) return kErrBadShape;
   if (num_row_windows == 0) return kOk;
   if (((uintptr_t)hspa & 15) || ((uintptr_t)hind & 15)) return kErrBadShape;
+  if (Pointer1 == nullptr || hspa == nullptr || hind == nullptr) return kErrBadShape;   // a window has a TC block: never empty
+  if (num_edges > 0 && (edgeList == nullptr || edgeToColumn == nullptr || edgeToRow == nullptr)) return kErrBadShape;
   hipLaunchKernelGGL(hmat_zero_kernel, dim3(256 * 8), dim3(256), 0, stream, Pointer1, (int)num_row_windows, hspa, hind);
   if (num_edges > 0) {
     const int threads = 256;
@@ -183,6 +187,7 @@ inline int hmat_packed_swizzle_hip(int32_t num_row_windows, const int32_t* Point
   if (num_row_windows < 0) return kErrBadShape;
   if (num_row_windows == 0) return kOk;
   if ((uintptr_t)hspa_packed & 15) return kErrBadShape;
+  if (Pointer1 == nullptr || hspa == nullptr || hspa_packed == nullptr) return kErrBadShape;
   hipLaunchKernelGGL(hmat_pack_swizzle_kernel, dim3(256 * 16), dim3(256), 0, stream, Pointer1, (int)num_row_windows,
                      hspa, hspa_packed);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;

@@ -1300,7 +1300,9 @@ inline int csr_window_count(const int* indptr, const int* indices, int num_nodes
                             void* workspace, int* block_partition, int* pointer1, int* status, hipStream_t stream,
                             int forced_path = kCsrAuto) {
   if (int rc = csr_check(num_nodes, num_edges)) return rc;
-  if (((uintptr_t)workspace & 15) || status == nullptr || num_cols > (1 << 28)) return kErrBadShape;
+  if (((uintptr_t)workspace & 15) || status == nullptr || pointer1 == nullptr || num_cols > (1 << 28)) return kErrBadShape;
+  // indices: empty without entries; workspace: its size is the caller's business (a size function of the sizes and the path)
+  if (num_nodes > 0 && (indptr == nullptr || block_partition == nullptr)) return kErrBadShape;
   const int W = (num_nodes + kBlkH - 1) / kBlkH;
   if (hipMemsetAsync(status, 0, sizeof(int), stream) != hipSuccess) return kErrLaunch;
   if (W == 0) {
@@ -1361,6 +1363,7 @@ inline int csr_fill(const int* indptr, const int* indices, int num_nodes, int nu
                     int forced_path = kCsrAuto) {
   if (int rc = csr_check(num_nodes, num_edges)) return rc;
   if (((uintptr_t)workspace & 15) || ((uintptr_t)hspa_packed & 15) || ((uintptr_t)hind & 15)) return kErrBadShape;
+  if (num_nodes > 0 && (indptr == nullptr || pointer1 == nullptr)) return kErrBadShape;
   const int W = (num_nodes + kBlkH - 1) / kBlkH;
   if (W == 0) return kOk;
   const CsrPath path = csr_path(num_nodes, num_cols, num_edges, forced_path);

@@ -118,7 +118,8 @@ inline long long fused_records_workspace_bytes(int num_nodes) {
 // Phase 1: wave_ptr int32 [8 NP + 1]; the caller reads R = wave_ptr[8 NP] and allocates records uint32 [(R + 1) * 64].
 inline int fused_records_count(const int* blk_offsets, const uint32_t* hspa_packed, int num_nodes, void* workspace,
                                int* wave_ptr, hipStream_t stream) {
-  if (num_nodes < 0 || ((uintptr_t)workspace & 15) || ((uintptr_t)hspa_packed & 15)) return kErrBadShape;
+  if (num_nodes < 0 || ((uintptr_t)workspace & 15) || ((uintptr_t)hspa_packed & 15) || wave_ptr == nullptr) return kErrBadShape;
+  if (num_nodes > 0 && (blk_offsets == nullptr || workspace == nullptr)) return kErrBadShape;   // hspa_packed: may be empty
   const int num_windows = (num_nodes + kBlkH - 1) / kBlkH;
   const int num_waves = kFusedWaves * ((num_nodes + kFusedPanelRows - 1) / kFusedPanelRows);
   if (hipMemsetAsync(wave_ptr, 0, sizeof(int), stream) != hipSuccess) return kErrLaunch;
@@ -137,7 +138,9 @@ inline int fused_records_count(const int* blk_offsets, const uint32_t* hspa_pack
 // Phase 2: every word of records [(R + 1) * 64] is written (the padding record is zero).
 inline int fused_records_fill(const int* blk_offsets, const uint32_t* hspa_packed, const int* hind, int num_nodes,
                               const int* wave_ptr, long long num_records, uint32_t* records, hipStream_t stream) {
-  if (num_nodes < 0 || num_records < 0 || ((uintptr_t)records & 15) || ((uintptr_t)hspa_packed & 15)) return kErrBadShape;
+  if (num_nodes < 0 || num_records < 0 || ((uintptr_t)records & 15) || ((uintptr_t)hspa_packed & 15) || records == nullptr)
+    return kErrBadShape;   // records: the padding record is always written
+  if (num_nodes > 0 && num_records > 0 && (blk_offsets == nullptr || wave_ptr == nullptr)) return kErrBadShape;
   if (hipMemsetAsync(records + num_records * kRecordWords, 0, kRecordBytes, stream) != hipSuccess) return kErrLaunch;
   const int num_windows = (num_nodes + kBlkH - 1) / kBlkH;
   const int num_waves = kFusedWaves * ((num_nodes + kFusedPanelRows - 1) / kFusedPanelRows);

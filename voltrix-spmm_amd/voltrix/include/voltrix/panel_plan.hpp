@@ -345,6 +345,7 @@ inline int panel_order(const int* panel_ptr, int num_panels, int group, int* ord
                        const int* xcd_ptr = nullptr) {
   if (num_panels < 0 || group < 1) return kErrBadShape;
   if (num_panels == 0) return kOk;
+  if (panel_ptr == nullptr || order_out == nullptr) return kErrBadShape;
   const int per_xcd = (num_panels + kNumXcd - 1) / kNumXcd;
   hipLaunchKernelGGL(panel_order_kernel, dim3((num_panels + 255) / 256), dim3(256), 0, stream, panel_ptr, num_panels,
                      per_xcd, group, xcd_ptr, order_out);
@@ -385,7 +386,8 @@ inline int panel_plan_count(const int* indptr, const int* indices, int num_nodes
                             int waves, int row_blocks, int tau, void* workspace, int* panel_ptr, int* resid_indptr,
                             int* status, hipStream_t stream) {
   if (int rc = plan_check(num_nodes, num_cols, num_edges, waves, row_blocks, tau)) return rc;
-  if (((uintptr_t)workspace & 15) || status == nullptr) return kErrBadShape;
+  if (((uintptr_t)workspace & 15) || status == nullptr || panel_ptr == nullptr || resid_indptr == nullptr) return kErrBadShape;
+  if (num_nodes > 0 && (indptr == nullptr || workspace == nullptr)) return kErrBadShape;   // indices: empty without entries
   const int panel_rows = waves * row_blocks * 16;
   const int np = (num_nodes + panel_rows - 1) / panel_rows;
   if (hipMemsetAsync(status, 0, sizeof(int), stream) != hipSuccess) return kErrLaunch;
@@ -417,7 +419,10 @@ inline int panel_plan_fill(const int* indptr, const int* indices, int num_nodes,
                            const int* resid_indptr, long long total_ksteps, int* resid_indices, int* panel_cols,
                            uint32_t* panel_bits, hipStream_t stream) {
   if (int rc = plan_check(num_nodes, num_cols, num_edges, waves, row_blocks, tau)) return rc;
-  if (((uintptr_t)workspace & 15) || total_ksteps < 0) return kErrBadShape;
+  if (((uintptr_t)workspace & 15) || total_ksteps < 0 || panel_cols == nullptr || panel_bits == nullptr) return kErrBadShape;
+  if (num_nodes > 0 &&   // indices / resid_indices: empty without (residual) entries
+      (indptr == nullptr || workspace == nullptr || panel_ptr == nullptr || resid_indptr == nullptr))
+    return kErrBadShape;
   const int panel_rows = waves * row_blocks * 16;
   const int np = (num_nodes + panel_rows - 1) / panel_rows;
   if (hipMemsetAsync(panel_bits, 0, (size_t)(total_ksteps + 1) * waves * kWave * 4, stream) != hipSuccess) return kErrLaunch;

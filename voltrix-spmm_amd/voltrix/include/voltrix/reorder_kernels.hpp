@@ -242,6 +242,7 @@ inline int bfs_grid(int n) {
 
 inline int bfs_seed(int start, int n, int* level, int* queue, int* ctrl, int* level_off, hipStream_t stream) {
   if (start < 0 || start >= n) return 1;
+  if (level == nullptr || queue == nullptr || ctrl == nullptr || level_off == nullptr) return 1;
   hipLaunchKernelGGL(bfs_seed_kernel, dim3(1), dim3(64), 0, stream, start, level, queue, ctrl, level_off);
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
@@ -251,6 +252,9 @@ inline int bfs_seed(int start, int n, int* level, int* queue, int* ctrl, int* le
 inline int bfs_levels(const BfsGraph& g, int* level, int* queue, int* ctrl, int* level_off, int wide_levels,
                       hipStream_t stream) {
   if (g.n <= 0 || g.t_rows < 0 || wide_levels < 0) return 1;
+  // indices / t_indices: empty without entries; t_indptr has t_rows + 1 elements
+  if (g.indptr == nullptr || g.t_indptr == nullptr || level == nullptr || queue == nullptr || ctrl == nullptr || level_off == nullptr)
+    return 1;
   hipLaunchKernelGGL(bfs_narrow_kernel, dim3(1), dim3(kBfsNarrowThreads), 0, stream, g, level, queue, ctrl, level_off,
                      kBfsNarrowMax);
   const int grid = bfs_grid(g.n);
@@ -296,7 +300,11 @@ inline long long cm_rank_workspace_bytes(long long max_level) { return cm_worksp
 // rank[v] = base + position.  `workspace` sized for the largest level above kCmSmallLevel (0 bytes if there is none).
 inline int cm_rank(const BfsGraph& g, const int* level, int* rank, const int* tie, int* queue, const int* level_off,
                    const int* level_off_host, int num_levels, int base, void* workspace, hipStream_t stream) {
-  if (g.n <= 0 || num_levels < 1 || level_off_host[0] != 0 || level_off_host[1] != 1) return 1;
+  if (g.n <= 0 || g.t_rows < 0 || num_levels < 1 || level_off_host == nullptr) return 1;
+  if (g.indptr == nullptr || g.t_indptr == nullptr || level == nullptr || rank == nullptr || tie == nullptr || queue == nullptr ||
+      level_off == nullptr)
+    return 1;
+  if (level_off_host[0] != 0 || level_off_host[1] != 1) return 1;
   long long max_level = 0;
   for (int d = 1; d < num_levels; ++d) {
     const long long m = level_off_host[d + 1] - level_off_host[d];
@@ -386,6 +394,8 @@ inline long long csr_transpose_workspace_bytes(long long nnz) { return transpose
 inline int csr_transpose(const int* indptr, const int* indices, int num_rows, int num_cols, long long nnz, void* workspace,
                          int* t_indptr, int* t_indices, hipStream_t stream) {
   if (num_rows < 0 || num_cols < 0 || nnz < 0 || nnz > 0x7fffffffll) return 1;
+  if (((uintptr_t)workspace & 15) || t_indptr == nullptr) return 1;     // t_indptr has num_cols + 1 elements
+  if (nnz > 0 && (indptr == nullptr || indices == nullptr || workspace == nullptr || t_indices == nullptr)) return 1;
   TransposeWorkspace ws = transpose_workspace(workspace, nnz);
   if (nnz > 0) {
     hipLaunchKernelGGL(csr_expand_rows_kernel, dim3(bfs_grid(num_rows)), dim3(256), 0, stream, indptr, num_rows, ws.rows);

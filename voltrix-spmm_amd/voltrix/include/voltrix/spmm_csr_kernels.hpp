@@ -153,6 +153,7 @@ inline int launch_spmm_csr_rows(const int* indptr, const int* indices, int num_r
   if (num_rows == 0 || embedding_dim == 0) return kOk;
   const int v = piece_elems(dtype);
   if (embedding_dim % v || indptr == nullptr || bad_ptr(input, 15) || bad_ptr(output, 15)) return kErrBadShape;
+  if (((uintptr_t)indptr & 3) || ((uintptr_t)indices & 3) || ((uintptr_t)values & 3)) return kErrBadShape;   // 4-byte loads
   const int pieces = embedding_dim / v;                  // 16-byte pieces per row
   const int slab_pieces = pieces < 64 ? pieces : 64;
   int lanes = 1;

@@ -594,6 +594,10 @@ inline int launch_spmm_fused(const int* panel_ptr, const int* panel_cols, const 
   if (num_nodes < 0 || embedding_dim < 0) return kErrBadShape;
   if (num_nodes == 0 || embedding_dim == 0) return kOk;
   if (embedding_dim % 8 != 0 || ((uintptr_t)input & 15) || ((uintptr_t)records & 15)) return kErrBadShape;
+  // plan arrays and records are padded by their builders (never empty); a square operator: input has num_nodes rows
+  if (panel_ptr == nullptr || panel_cols == nullptr || panel_bits == nullptr || wave_ptr == nullptr || records == nullptr ||
+      input == nullptr || output == nullptr)
+    return kErrBadShape;
   FusedArgs<T> a;
   a.panel_ptr = panel_ptr;
   a.panel_cols = panel_cols;

@@ -1015,11 +1015,14 @@ inline int launch_spmm_tc16(const int* blk_offsets, const uint32_t* hspa_packed,
   if (embedding_dim % (16 / T::EB) != 0) return kErrBadShape;  // 16-byte row chunks
   if (atomic_out == 2) {   // ticket join: one column slab of a 16-bit binary operand, rows of C as they are, 16-byte stores
     if (T::EB != 2 || T::WEIGHTED || tickets == nullptr || row_map != nullptr || embedding_dim > T::FS || embedding_dim % 4 != 0 ||
-        ((uintptr_t)output & 15))
+        ((uintptr_t)output & 15) || ((uintptr_t)tickets & 15))
       return kErrBadShape;
     static_assert(T::EB != 2 || ticket_tile_lds_bytes<T::FS>() <= T::WAVE_LDS, "the tile transpose uses the wave's own ring");
   }
   if (((uintptr_t)input & 15) || ((uintptr_t)hspa_packed & 15)) return kErrBadShape;
+  // blk_offsets [windows + 1] and output [num_nodes][embedding_dim] have an element here; hspa_packed / hind are empty for a graph
+  // without edges and input for an operator without columns (callers pass data_ptr() = 0 then): not refused
+  if (blk_offsets == nullptr || output == nullptr) return kErrBadShape;
   SpmmArgs<T> a;
   a.blk_offsets = blk_offsets;
   a.hspa_packed = hspa_packed;
@@ -1150,7 +1153,8 @@ inline int combine_partials(const int* cuts, int num_cuts, const float* partials
   if (tickets != nullptr && row_map != nullptr) return kErrBadShape;
   if (num_cuts < 0 || num_nodes < 0 || embedding_dim < 0 || (embedding_dim % 4) != 0) return kErrBadShape;
   if (num_cuts == 0 || num_nodes == 0 || embedding_dim == 0) return kOk;
-  if (((uintptr_t)cuts & 15) || ((uintptr_t)partials & 15) || ((uintptr_t)output & 15)) return kErrBadShape;
+  if (((uintptr_t)cuts & 15) || ((uintptr_t)partials & 15) || ((uintptr_t)output & 15) || ((uintptr_t)tickets & 15)) return kErrBadShape;
+  if (cuts == nullptr || partials == nullptr || output == nullptr) return kErrBadShape;
   hipLaunchKernelGGL(combine_partials_kernel, dim3((unsigned)num_cuts), dim3(256), 0, stream,
                      reinterpret_cast<const int4*>(cuts), partials, output, num_nodes, embedding_dim, accumulate, row_map,
                      tickets);
@@ -1211,6 +1215,7 @@ inline int launch_window_order(const int* blk_offsets, int num_nodes, int chunk,
   if (num_nodes < 0 || chunk < 1 || chunk > kOrderMaxChunk) return kErrBadShape;
   const int num_windows = (num_nodes + kBlkH - 1) / kBlkH;
   if (num_windows == 0) return kOk;
+  if (blk_offsets == nullptr || order == nullptr) return kErrBadShape;
   const int windows_per_xcd = (num_windows + kNumXcd - 1) / kNumXcd;  // must match launch_spmm_tc16
   const int chunks_per_xcd = (windows_per_xcd + chunk - 1) / chunk;
   hipLaunchKernelGGL(window_order_kernel, dim3(kNumXcd * chunks_per_xcd), dim3(256), 0, stream, blk_offsets, num_windows,
@@ -1236,6 +1241,7 @@ static __global__ __launch_bounds__(256) void cast_f32_to_f16_kernel(const float
 inline int cast_f32_to_f16(const float* src, _Float16* dst, long long n, hipStream_t stream) {
   if (n < 0 || (n % 8) != 0 || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return kErrBadShape;
   if (n == 0) return kOk;
+  if (src == nullptr || dst == nullptr) return kErrBadShape;
   const long long n8 = n / 8;
   const int blocks = (int)(n8 / 256 + 1 < 256 * 16 ? n8 / 256 + 1 : 256 * 16);
   hipLaunchKernelGGL(cast_f32_to_f16_kernel, dim3(blocks), dim3(256), 0, stream, src, dst, n8);
@@ -1281,7 +1287,8 @@ inline int scale_rows(const void* src, const float* scale, void* dst, long long 
   const int per_chunk = dtype == 0 ? 4 : 8;
   if (rows < 0 || num_feats < 0 || dtype < 0 || dtype > 2 || num_feats % per_chunk) return kErrBadShape;
   if (rows == 0 || num_feats == 0) return kOk;
-  if (src == nullptr || dst == nullptr || scale == nullptr || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return kErrBadShape;
+  if (src == nullptr || dst == nullptr || scale == nullptr || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15) || ((uintptr_t)scale & 3))
+    return kErrBadShape;
   const int cpr = num_feats / per_chunk;
   const long long chunks = rows * cpr;
   const int blocks = (int)(chunks / 256 + 1 < 256 * 16 ? chunks / 256 + 1 : 256 * 16);
@@ -1391,6 +1398,7 @@ inline int cast_f32_to_f16_scaled(const float* src, _Float16* dst, long long n, 
   if (n < 0 || (n % 8) != 0 || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15) || scale == nullptr ||
       ((uintptr_t)scale & 7))
     return kErrBadShape;
+  if (n > 0 && (src == nullptr || dst == nullptr)) return kErrBadShape;   // n == 0: only the scale is written
   const long long n8 = n / 8;
   const int blocks = (int)(n8 / 256 + 1 < 256 * 16 ? n8 / 256 + 1 : 256 * 16);
   // three kernels of one stream (kernel nodes are strictly ordered, also inside a captured graph): workgroup maxima into the

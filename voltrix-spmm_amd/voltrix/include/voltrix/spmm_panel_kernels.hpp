@@ -621,7 +621,8 @@ inline int launch_combine_panel_partials(const int* cuts, int num_cuts, const fl
                                          int* tickets = nullptr /* ticket join: the call's ticket buffer */) {
   if (num_cuts < 0 || num_nodes < 0 || embedding_dim < 0 || panel_rows < 16 || panel_rows % 16 != 0) return kErrBadShape;
   if (num_cuts == 0 || num_nodes == 0 || embedding_dim == 0) return kOk;
-  if (embedding_dim % 4 != 0 || cuts == nullptr || partials == nullptr || output == nullptr) return kErrBadShape;
+  if (embedding_dim % 4 != 0 || cuts == nullptr || partials == nullptr || output == nullptr || ((uintptr_t)tickets & 15))
+    return kErrBadShape;
   hipLaunchKernelGGL(combine_panel_partials_kernel, dim3((unsigned)num_cuts, (unsigned)(panel_rows / 16)), dim3(256), 0, stream,
                      cuts, partials, output, num_nodes, embedding_dim, panel_rows, accumulate, tickets);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;
@@ -642,11 +643,14 @@ inline int launch_spmm_panel(const int* panel_ptr, const int* panel_cols, const 
                              int* tickets = nullptr /* accumulate == 3: int32 [kTicketHeader + ceil(num_nodes / 16)] */) {
   if (num_nodes < 0 || embedding_dim < 0 || accumulate < 0 || accumulate > 3) return kErrBadShape;
   // ticket join: one column slab, whole 16-byte pieces of C's rows
-  if (accumulate == 3 && (tickets == nullptr || embedding_dim > T::FS || embedding_dim % 4 != 0 || ((uintptr_t)output & 15)))
+  if (accumulate == 3 && (tickets == nullptr || ((uintptr_t)tickets & 15) || embedding_dim > T::FS || embedding_dim % 4 != 0 ||
+                          ((uintptr_t)output & 15)))
     return kErrBadShape;
   if (parts != nullptr && num_parts < 1) return kErrBadShape;   // partials: required when any part carries a slot
   if (num_nodes == 0 || embedding_dim == 0) return kOk;
   if (embedding_dim % 8 != 0 || ((uintptr_t)input & 15)) return kErrBadShape;
+  // the plan arrays are padded by their builder, so none is empty; input is (an operator without columns: data_ptr() = 0)
+  if (panel_ptr == nullptr || panel_cols == nullptr || panel_bits == nullptr || output == nullptr) return kErrBadShape;
   PanelArgs<T> a;
   a.panel_ptr = panel_ptr;
   a.panel_cols = panel_cols;

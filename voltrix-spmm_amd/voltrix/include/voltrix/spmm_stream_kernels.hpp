@@ -602,6 +602,8 @@ inline int launch_spmm_stream(const uint32_t* hspa_packed, const int* hind, int 
   if (((uintptr_t)input & 15) || ((uintptr_t)hspa_packed & 15) || ((uintptr_t)units & 15) || ((uintptr_t)runs & 15) ||
       ((uintptr_t)output & 15) || ((uintptr_t)partials & 15) || run_ptr == nullptr)
     return kErrBadShape;
+  // max_runs_per_xcd > 0: there is a run and a unit; hspa_packed / hind / input may be empty, partials is NULL without cut windows
+  if (output == nullptr || units == nullptr || runs == nullptr) return kErrBadShape;
   const int total_slabs = (embedding_dim + T::FS - 1) / T::FS;
   if (slab_first < 0 || slab_count < 0 || slab_first + slab_count > total_slabs) return kErrBadShape;
   if (const int group = slab_count == 0 ? slab_launch_group(total_slabs, T::FS * T::EB,

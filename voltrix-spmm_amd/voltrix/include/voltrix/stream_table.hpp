@@ -188,6 +188,7 @@ inline int stream_table_count(const int* blk_offsets, const uint32_t* hspa_packe
   if (int rc = unit_table_check(num_nodes)) return rc;
   if (((uintptr_t)workspace & 15) || header == nullptr || run_cost > 128 || ((uintptr_t)hind & 15) || ((uintptr_t)hspa_packed & 15))
     return kErrBadShape;
+  if (num_nodes > 0 && (blk_offsets == nullptr || workspace == nullptr)) return kErrBadShape;   // hspa_packed / hind: may be empty
   if (hipMemsetAsync(header, 0, 8 * sizeof(int), stream) != hipSuccess) return kErrLaunch;
   const int W = (num_nodes + kBlkH - 1) / kBlkH;
   if (W == 0) return kOk;
@@ -343,6 +344,9 @@ inline int stream_table_fill(const int* blk_offsets, int num_nodes, void* worksp
   if (((uintptr_t)workspace & 15) || ((uintptr_t)fill_workspace & 15) || ((uintptr_t)units & 15) || ((uintptr_t)runs & 15) ||
       ((uintptr_t)cuts & 15) || run_ptr == nullptr || header2 == nullptr || num_units < 0 || run_bound < 0 || run_cost < 2 ||
       run_cost > 128)   // > 128: runs of more than 64 units -- the kernel keeps a run's unit table one unit per lane (as the count phase)
+    return kErrBadShape;
+  if (num_nodes > 0 && num_units > 0 &&   // cuts / runs: empty without a cut window / with run_bound == 0
+      (blk_offsets == nullptr || workspace == nullptr || fill_workspace == nullptr || units == nullptr))
     return kErrBadShape;
   const int W = (num_nodes + kBlkH - 1) / kBlkH;
   if (hipMemsetAsync(run_ptr, 0, 9 * sizeof(int), stream) != hipSuccess) return kErrLaunch;

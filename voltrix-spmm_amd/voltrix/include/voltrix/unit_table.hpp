@@ -249,6 +249,7 @@ inline int unit_table_count(const int* blk_offsets, int num_nodes, int max_stage
                             hipStream_t stream, const int* xcd_ptr = nullptr /* device int32[9] or NULL: equal split */) {
   if (int rc = unit_table_check(num_nodes)) return rc;
   if (((uintptr_t)workspace & 15) || header == nullptr) return kErrBadShape;
+  if (num_nodes > 0 && (blk_offsets == nullptr || workspace == nullptr)) return kErrBadShape;
   if (hipMemsetAsync(header, 0, kUtHeaderInts * sizeof(int), stream) != hipSuccess) return kErrLaunch;
   const int W = (num_nodes + kBlkH - 1) / kBlkH;
   if (W == 0) return kOk;
@@ -326,7 +327,10 @@ inline int unit_table_fill(const int* blk_offsets, int num_nodes, void* workspac
   if (int rc = unit_table_check(num_nodes)) return rc;
   if (((uintptr_t)workspace & 15) || ((uintptr_t)fill_workspace & 15) || num_units < 0 || num_cuts < 0 || top < 0)
     return kErrBadShape;
-  if (((uintptr_t)units & 15) || ((uintptr_t)cuts & 15)) return kErrBadShape;
+  if (((uintptr_t)units & 15) || ((uintptr_t)cuts & 15) || unit_ptr == nullptr) return kErrBadShape;
+  if (num_nodes > 0 && num_units > 0 &&   // cuts: empty for a table without a cut window
+      (blk_offsets == nullptr || workspace == nullptr || fill_workspace == nullptr || units == nullptr))
+    return kErrBadShape;
   const int W = (num_nodes + kBlkH - 1) / kBlkH;
   if (W == 0 || num_units == 0)
     return hipMemsetAsync(unit_ptr, 0, (kNumXcd + 1) * sizeof(int), stream) == hipSuccess ? kOk : kErrLaunch;
