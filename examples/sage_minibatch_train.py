@@ -7,7 +7,11 @@ per row, a dense-table relabel; the same blocks on every run for the same seed a
 rectangular patterns with `voltrix.autograd.SpMMReduce(block.pattern)`.  A block's source nodes start with its destination nodes, so
 the self term is `h[:block.num_dst]`.  The full graph never enters a kernel: a step touches the sampled rows only.
 
-    python examples/sage_minibatch_train.py [workload] [hidden] [steps] [max|mean] [batch]    # synthetic stand-in graph, random data
+    python examples/sage_minibatch_train.py [workload] [hidden] [steps] [max|mean] [batch] [uniform|inverse_degree]
+                                                                                              # synthetic stand-in graph, random data
+
+The last argument chooses the neighbour draws: `uniform` (the default), or `inverse_degree` -- every neighbour j weighted by
+1 / in_degree(j) through `voltrix.sampling_weights` and `sample_blocks(prob=)`.
 """
 import os
 import sys
@@ -52,11 +56,21 @@ class BlockSAGE(torch.nn.Module):
         return self.l2(blocks[1], torch.relu(self.l1(blocks[0], x)))
 
 
-def train_step(model, opt, indptr, indices, x, y, batch_nodes, seed, step, fanouts=FANOUTS):
-    """One optimiser step on the mini-batch of the int32 output nodes ``batch_nodes``; returns the loss (a device scalar)."""
+def inverse_degree_weights(indptr, indices):
+    """The table of ``voltrix.sampling_weights`` for ``prob[e] = 1 / in_degree(indices[e])``: neighbours that many nodes share are
+    drawn less often (importance sampling by inverse degree).  Built once per graph."""
     import voltrix
 
-    blocks = voltrix.sample_blocks(indptr, indices, batch_nodes, fanouts, seed=seed, offset=step * len(fanouts))
+    in_degree = torch.bincount(indices.long(), minlength=indptr.numel() - 1).clamp(min=1)
+    return voltrix.sampling_weights(indptr, (1.0 / in_degree.float())[indices.long()])
+
+
+def train_step(model, opt, indptr, indices, x, y, batch_nodes, seed, step, fanouts=FANOUTS, prob=None):
+    """One optimiser step on the mini-batch of the int32 output nodes ``batch_nodes``; returns the loss (a device scalar).  ``prob``:
+    ``None`` (uniform neighbour draws) or a ``voltrix.SamplingWeights`` of the graph (weighted draws)."""
+    import voltrix
+
+    blocks = voltrix.sample_blocks(indptr, indices, batch_nodes, fanouts, seed=seed, offset=step * len(fanouts), prob=prob)
     opt.zero_grad(set_to_none=True)
     logits = model(blocks, x[blocks[0].src_ids.long()])
     loss = torch.nn.functional.cross_entropy(logits, y[batch_nodes.long()])
@@ -73,11 +87,16 @@ def main():
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 30
     reduce = sys.argv[4] if len(sys.argv) > 4 else "max"
     batch = int(sys.argv[5]) if len(sys.argv) > 5 else 1024
+    sampler = sys.argv[6] if len(sys.argv) > 6 else "uniform"
     if reduce not in ("max", "mean"):
         raise SystemExit(f"aggregator must be max or mean, got {reduce!r}")
+    if sampler not in ("uniform", "inverse_degree"):
+        raise SystemExit(f"sampler must be uniform or inverse_degree, got {sampler!r}")
     indptr, indices, _ = synth_graphs.generate(workload, device="cuda")
     n = indptr.numel() - 1
-    print(f"{workload}: N={n} nnz={indices.numel()}; batches of {batch} nodes, fan-outs {FANOUTS} (input layer first); aggregator: {reduce}")
+    prob = inverse_degree_weights(indptr, indices) if sampler == "inverse_degree" else None
+    print(f"{workload}: N={n} nnz={indices.numel()}; batches of {batch} nodes, fan-outs {FANOUTS} (input layer first); aggregator: {reduce}; "
+          f"neighbour draws: {sampler}")
     torch.manual_seed(0)
     in_feats, classes = 128, 48
     x = torch.randn(n, in_feats, device="cuda")
@@ -91,7 +110,7 @@ def main():
         nodes = order[first:first + batch]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        loss = train_step(model, opt, indptr, indices, x, y, nodes, seed=1234, step=step)
+        loss = train_step(model, opt, indptr, indices, x, y, nodes, seed=1234, step=step, prob=prob)
         torch.cuda.synchronize()
         times.append((time.perf_counter() - t0) * 1e3)
         if step in (0, 1, steps - 1):

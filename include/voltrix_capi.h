@@ -954,6 +954,45 @@ void voltrix_launch_sample_neighbors_excluding(void* indptr, void* indices, int 
                                                int64_t num_sampled, int fanout, int replace, uint64_t seed, uint64_t offset, void* exclude,
                                                int num_exclude, void* s_indices, void* s_entries, void* stream, int* return_code);
 
+/* Weighted neighbour sampling on integer cumulative weights (voltrix/weighted_sample_kernels.hpp): DGL's sample_neighbors(prob=) --
+ * importance sampling, edge-weight-biased GraphSAGE, masking entries with zero weights.  No reference counterpart.  (Not a
+ * voltrix_launch_ name: it joins the launchers' host-contract table when that table is next opened.)
+ * THE WEIGHT TABLE.  For an entry e of row r with weight w_e >= 0 (finite) and m_r = the largest weight of the row, in float64:
+ *   q_e = 0 where w_e == 0 or m_r == 0, otherwise q_e = max(1, floor((w_e / m_r) * 2^30))
+ * (one correctly rounded division, an exact multiplication, an exact floor): 0 <= q_e <= 2^30, a positive weight stays positive, a zero
+ * weight is never sampled, q_e / 2^30 is within 2^-30 of w_e / m_r.  cum = device int64[nnz], the inclusive prefix sum of q over the
+ * whole entry array (at most nnz 2^30 < 2^61), 8 bytes per entry: the caller builds it (voltrix.sampling_weights does).
+ * THE SAMPLING RULE.  Row r with begin = indptr[r], d = indptr[r + 1] - begin, fan-out k = fanout:
+ *   base = begin > 0 ? cum[begin - 1] : 0 (cum[-1] is never read); c(j) = cum[begin + j] - base; T = c(d - 1); p = the number of
+ *   entries of the row with q > 0;
+ *   draw(r, n) = word n & 3 of Philox4x32-10(counter = (r, (n >> 2) | 0xA0000000, offset & 0xffffffff, offset >> 32),
+ *                key = (seed & 0xffffffff, seed >> 32)), n < 128: bits 31 and 29 of counter word 1, a part of
+ *                voltrix_launch_sample_neighbors' domain that its own draws (0x80000000 | (i >> 2), i < 64) never enter;
+ *   x_i = (uint64(draw(r, 2 i)) << 32) | draw(r, 2 i + 1); a uniform integer below R is umulhi64(x_i, R) = (x_i R) >> 64: an entry's
+ *                probability differs from q_e / R by less than 2^-63;
+ *   replace = 0, p <= k: every entry with q > 0, in CSR order, no draw used.  fanout = -1 (VOLTRIX_SAMPLE_ALL) means this for every row,
+ *                whatever replace is.
+ *   replace = 0, p > k:  successive sampling: for i = 0 .. k - 1, R_i = T - (the sum of q over the entries chosen so far),
+ *                t = umulhi64(x_i, R_i); choose the smallest position j with g(j) > t, g(j) = c(j) - (the sum of q_s over chosen
+ *                s <= j).  g does not decrease and is flat at chosen positions and zero weights, so j is new and has q > 0.  The k
+ *                positions are output in ascending order (sorted rows stay sorted).
+ *   replace = 1, T > 0:  exactly k entries, entry i at the smallest j with c(j) > umulhi64(x_i, T), in draw order; T == 0: none.
+ * A function of (seed, offset, r, k) and the row's q values only; equal weights do NOT give voltrix_launch_sample_neighbors' bits.
+ * seeds, s_indices, s_entries as for voltrix_launch_sample_neighbors; a seed outside [0, num_rows) has degree 0 inside the kernel.
+ * s_indptr = device int32[num_seeds + 1], the caller's prefix sum of the per-seed counts the rule gives (min(p, k); T > 0 ? k : 0 with
+ * replace; p for fanout = -1); num_sampled = s_indptr[num_seeds].  It is how the kernel learns p: a segment shorter than k gets every
+ * positive entry, a segment of k is drawn.  Every element of s_indices and s_entries is written when s_indptr is the rule's; a row never
+ * writes past its segment, and every read of cum and indices stays inside the row whatever cum and s_indptr hold.  One lane per seed,
+ * 256 per workgroup; the chosen positions live sorted in 256 k 4 bytes of dynamic LDS (replace = 0 only); per row O(k (k + log d))
+ * loads of cum whatever the degree, no loop whose trip count depends on a draw (fanout = -1 is O(d) at worst); no atomics, no
+ * workspace, no host synchronisation, the same bits on every call.
+ * VOLTRIX_ERR_BAD_SHAPE, on the host and before any HIP call: negative sizes, num_sampled > INT_MAX, fanout outside 1 .. 64 and not -1,
+ * replace outside {0, 1}, a null or misaligned pointer (indices, cum, s_indices, s_entries only where num_sampled > 0); VOLTRIX_OK
+ * without a launch for num_seeds == 0 or num_sampled == 0.  Alignment: cum 8 bytes, 4 bytes everywhere else. */
+void voltrix_sample_neighbors_weighted(void* indptr, void* indices, void* cum, int num_rows, void* seeds, int num_seeds, void* s_indptr,
+                                       int64_t num_sampled, int fanout, int replace, uint64_t seed, uint64_t offset, void* s_indices,
+                                       void* s_entries, void* stream, int* return_code);
+
 /* (ROW, COLUMN) -> ENTRY (DGL's edge_ids / has_edges_between).  rows, cols = device int32[num_queries].  out[i] = the id of the FIRST
  * entry of row rows[i] whose column is cols[i]; -1 if there is none or rows[i] is outside [0, num_rows).  No [nnz] key array is kept,
  * so this is a search: assume_sorted = 1 is the PRECONDITION that every row's columns ascend (duplicates allowed): a lower bound,

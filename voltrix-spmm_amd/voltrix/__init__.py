@@ -22,7 +22,7 @@ from .gatv2_score import gatv2_score
 from .attn_aggregate import attn_aggregate
 from .spmm_reduce import spmm_reduce
 from .dropout import apply_dropout_mask, dropout_mask
-from .sampling import Block, compact_block, sample_blocks, sample_neighbors
+from .sampling import Block, SamplingWeights, compact_block, sample_blocks, sample_neighbors, sampling_weights
 from .subgraph import Subgraph, induced_subgraph, random_walk, sample_subgraph_rw, subgraph_csr
 from .negative import EdgeBatch, edge_endpoints, find_edges, negative_sample, sample_edge_batch
 from .graphed import GraphedSpMM

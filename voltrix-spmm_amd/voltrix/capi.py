@@ -116,6 +116,7 @@ SIGNATURES = {
     "voltrix_launch_negative_sample": (None, [_P, _P, _I, _I, _L, _P, _I, _I, _I, _I, _I, _U64, _U64, _P, _P, _RC_P]),
     "voltrix_launch_edge_endpoints": (None, [_P, _P, _I, _L, _P, _I, _P, _P, _P, _RC_P]),
     "voltrix_launch_sample_neighbors_excluding": (None, [_P, _P, _I, _P, _I, _P, _L, _I, _I, _U64, _U64, _P, _I, _P, _P, _P, _RC_P]),
+    "voltrix_sample_neighbors_weighted": (None, [_P, _P, _P, _I, _P, _I, _P, _L, _I, _I, _U64, _U64, _P, _P, _P, _RC_P]),
     "voltrix_launch_find_edges": (None, [_P, _P, _I, _L, _P, _P, _I, _I, _P, _P, _RC_P]),
     "voltrix_csr_preprocess_workspace_bytes": (_L, [_I, _I, _L, _I]),
     "voltrix_launch_csr_window_count": (None, [_P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _RC_P]),
@@ -964,6 +965,24 @@ def launch_sample_neighbors(indptr, indices, num_rows: int, seeds, s_indptr, num
     else:
         _checked("voltrix_launch_sample_neighbors_excluding", *head, exclude.data_ptr() if exclude.numel() else None, exclude.numel(),
                  *tail)
+
+
+def sample_neighbors_weighted(indptr, indices, cum, num_rows: int, seeds, s_indptr, num_sampled: int, fanout: int, replace: bool,
+                              seed: int, offset: int, s_indices, s_entries, stream) -> None:
+    """At most ``fanout`` entries of every seed row of a device int32 CSR, drawn by weight: the rule of
+    voltrix/weighted_sample_kernels.hpp on ``cum``, device int64 [nnz], the inclusive prefix sum of the quantised weights
+    (``voltrix.sampling_weights``).  ``s_indptr`` is the prefix sum of the rule's per-seed counts (with the rows' positive entries in
+    place of their degrees); the other arguments are ``launch_sample_neighbors``'; see include/voltrix_capi.h."""
+    import torch
+
+    for t in (indptr, indices, seeds, s_indptr, s_indices, s_entries):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+    assert cum.dtype == torch.int64 and cum.is_contiguous() and cum.is_cuda and cum.numel() == indices.numel()
+    assert indptr.numel() == num_rows + 1 and s_indptr.numel() == seeds.numel() + 1
+    assert s_indices.numel() == num_sampled == s_entries.numel()
+    _checked("voltrix_sample_neighbors_weighted", indptr.data_ptr(), indices.data_ptr(), cum.data_ptr(), num_rows, seeds.data_ptr(),
+             seeds.numel(), s_indptr.data_ptr(), num_sampled, int(fanout), int(bool(replace)), int(seed), int(offset),
+             s_indices.data_ptr(), s_entries.data_ptr(), stream)
 
 
 def launch_block_mark(cols, num_cols: int, table, stream) -> None:
