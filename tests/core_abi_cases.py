@@ -1,7 +1,8 @@
-"""The host-side argument contract of the core entry points of libvoltrix_hip.so (include/voltrix_capi.h), as ONE table: a row per
-``voltrix_launch_*`` symbol that has no ``tests/test_*_host.py`` of its own, a role per parameter, and the bad calls derived from the
-roles (``cases()``).  ``tests/test_core_abi_host.py`` sends the cases through ``tests/core_abi_worker.py`` -- a child process that
-cannot see a device -- and compares every return code; no torch, no GPU.
+"""The host-side argument contract of every entry point of libvoltrix_hip.so that launches (include/voltrix_capi.h), as ONE table: a
+row per symbol of the binding that returns nothing and takes a stream and a return-code slot -- every ``voltrix_launch_*`` and
+``voltrix_sample_neighbors_weighted`` --, a role per parameter, and the bad calls derived from the roles (``cases()``).
+``tests/test_core_abi_host.py`` sends the cases through ``tests/core_abi_worker.py`` -- a child process that cannot see a device -- and
+compares every return code; no torch, no GPU, and no test calls one of these symbols in its own process.
 
 A row's ``params`` follow ``capi.SIGNATURES[name]`` one to one.  The roles:
 
@@ -19,9 +20,9 @@ A row's ``params`` follow ``capi.SIGNATURES[name]`` one to one.  The roles:
     ST, RC         the stream (NULL: the null stream) and the return-code slot
 
 ``zero``: the "nothing to do" calls and what they answer; ``extra``: everything else the launcher's code refuses -- widths off the
-grid, tiles that are not instantiated, combinations -- and, pinned as the per-operator host tests pin it, whether a bad width or enum is
-refused before or after "nothing to do".  Every override is ``{parameter: value}``; for a pointer the value is ``NULL``, ``SET`` (its
-aligned buffer) or ``("off", bytes)``.
+grid, tiles that are not instantiated, floats that are not finite, products beyond INT_MAX, combinations -- and whether a bad width,
+enum or float is refused before or after "nothing to do".  Every override is ``{parameter: value}``; for a pointer the value is
+``NULL``, ``SET`` (its aligned buffer), ``("off", bytes)`` or ``("same", other pointer)``.
 
 The baseline of a row -- valid, non-zero sizes, pointers into zeroed 16-byte-aligned HOST buffers -- passes every check and reaches
 the first HIP runtime call, which fails in a process without a device: VOLTRIX_ERR_LAUNCH.  ``baseline=`` names the rows that answer
@@ -452,23 +453,332 @@ row("voltrix_launch_chol_inv_transposed",
     [("gram", P()), ("k", R(8, 1, 64)), ("eps", V(1e-10)), ("out", P()), ("stream", ST), ("return_code", RC)],
     extra=[("k_64", {"k": 64}, LAUNCH), ("k_1", {"k": 1}, LAUNCH)])
 
-# ---- the entry points with a tests/test_*_host.py of their own -----------------------------------------------------------------------
-COVERED_ELSEWHERE = (
-    "voltrix_launch_sddmm_csr",
-    "voltrix_launch_spmm_csr_reduce", "voltrix_launch_spmm_csr_reduce_backward",
-    "voltrix_launch_sample_neighbors", "voltrix_launch_sample_neighbors_excluding",
-    "voltrix_launch_block_mark", "voltrix_launch_block_mark_seeds", "voltrix_launch_block_relabel",
-    "voltrix_launch_subgraph_count", "voltrix_launch_subgraph_fill", "voltrix_launch_random_walk",
-    "voltrix_launch_negative_sample", "voltrix_launch_edge_endpoints", "voltrix_launch_find_edges",
-    "voltrix_launch_edge_softmax_csr", "voltrix_launch_edge_softmax_backward_csr",
-    "voltrix_launch_sddmm_heads_csr", "voltrix_launch_edge_softmax_heads_csr", "voltrix_launch_edge_softmax_heads_backward_csr",
-    "voltrix_launch_spmm_csr_heads",
-    "voltrix_launch_gat_score_csr", "voltrix_launch_gat_score_rowsum_csr",
-    "voltrix_launch_gatv2_score_csr", "voltrix_launch_gatv2_rowsum_csr",
-    "voltrix_launch_attn_aggregate_csr", "voltrix_launch_attn_aggregate_grad_scores_csr", "voltrix_launch_attn_aggregate_grad_feat_csr",
-    "voltrix_launch_dropout_mask", "voltrix_launch_attn_aggregate_dropout_csr", "voltrix_launch_attn_aggregate_dropout_grad_scores_csr",
-    "voltrix_launch_attn_aggregate_dropout_grad_feat_csr",
-)
+# ==== the operators on a device CSR: attention, max / min / mean, sampling ===========================================================
+# These launchers check in one order: sizes, enums, widths and floats first, then "nothing to do", then the pointers the sizes make the
+# launch touch.  So a bad size or float is refused with nothing to do as well, and NULL is accepted exactly where nothing reads it.
+# Baselines: 4 rows, 6 entries, 2 heads.  An edge tensor and an index array need 4 bytes, a gathered node tensor 16.
+F32, F16, BF16 = 0, 1, 2
+INF, NAN = float("inf"), float("nan")
+NOT_FINITE = (INF, -INF, NAN)
+_END = [("stream", ST), ("return_code", RC)]
+
+
+def _nulls(params, but=()):
+    return {p: NULL for p, role in params if role.kind == "pointer" and p not in but}
+
+
+def _refused(param, values, nothing, alone=True):
+    """Values of ``param`` that no role derives (a float, a list of widths): refused alone, and refused with ``nothing`` -- the
+    overrides of a call with nothing to do -- as well: the check comes first.  ``alone=False``: the role derives the first already."""
+    return [case for v in values for case in ([(f"{param}={v!r}", {param: v}, BAD)] if alone else []) +
+            [(f"{param}={v!r},before_nothing_to_do", {param: v, **nothing}, BAD)]]
+
+
+def _transposed(cases):
+    """The cases of an entry point on the CSR for the one on the transposed CSR: its rows are the pattern's columns."""
+    return [(what, {("num_cols" if k == "num_rows" else k): v for k, v in o.items()}, code) for what, o, code in cases]
+
+
+def _off(names, bytes_off):
+    return [(f"{p}+{bytes_off}", {p: ("off", bytes_off)}, BAD) for p in names]
+
+
+_NNZ = ("nnz", N(6, INT_MAX))
+
+
+def _beyond(**others):
+    """nnz = 2^31 next to arguments other than the baseline's (the derived ``nnz=2147483648`` has the baseline's)."""
+    return [("nnz=2147483648," + ",".join(f"{k}={v!r}" for k, v in others.items()), {"nnz": 2 ** 31, **others}, BAD)]
+
+
+_NO_ROW = ("entries_but_no_row", {"num_rows": 0}, BAD)
+# 16 bytes of the gathered operand: 8 elements when it is 16-bit, 4 when fp32
+_PAIRS_REFUSED = [(f"pair_{x}_{y}", {"x_dtype": x, "y_dtype": y}, BAD) for x, y in ((F16, F32), (F16, BF16), (BF16, F16))]
+_PAIRS = [(f"pair_{x}_{y}", {"x_dtype": x, "y_dtype": y}, LAUNCH) for x, y in ((F32, F32), (F32, BF16), (F16, F16), (BF16, BF16))]
+
+# ---- sampled dense-dense product (sddmm_kernels.hpp, sddmm_heads_kernels.hpp) --------------------------------------------------------
+_SDDMM = [("indptr", P(4)), ("indices", P(4)), ("num_rows", N(4)), _NNZ, ("embedding_dim", N(16)), ("x", P(16)), ("x_dtype", R(F32, 0, 2)),
+          ("y", P(16)), ("y_dtype", R(F16, 0, 2)), ("out", P(4))] + _END
+row("voltrix_launch_sddmm_csr", _SDDMM,
+    zero=[({"nnz": 0}, OK), ({"nnz": 0, "out": NULL}, OK), ({"embedding_dim": 0}, OK), ({"nnz": 0, **_nulls(_SDDMM)}, OK)],
+    extra=_PAIRS_REFUSED + _PAIRS + [
+        _NO_ROW, ("width_16_bit_y", {"embedding_dim": 12}, BAD), ("width_16_bit", {"embedding_dim": 12, "x_dtype": F16}, BAD),
+        ("width_fp32", {"embedding_dim": 6, "y_dtype": F32}, BAD), ("width_negative", {"embedding_dim": -8}, BAD),
+        ("width_before_nothing_to_do", {"embedding_dim": 12, "nnz": 0}, BAD)] + _beyond(x_dtype=F16))
+_SDDMM_HEADS = _SDDMM[:4] + [("heads", R(2, 1, None)), ("head_dim", N(16))] + _SDDMM[5:]
+# heads * head_dim <= INT_MAX; heads and the sizes are checked before "nothing to do"
+_HEADS_EXTRA = [("heads_negative", {"heads": -2}, BAD), ("heads_times_head_dim_above_int_max", {"heads": 2 ** 20, "head_dim": 2 ** 12}, BAD),
+                ("head_dim_negative", {"head_dim": -8}, BAD)]
+row("voltrix_launch_sddmm_heads_csr", _SDDMM_HEADS,
+    zero=[({"nnz": 0}, OK), ({"nnz": 0, "out": NULL}, OK), ({"head_dim": 0}, OK), ({"nnz": 0, **_nulls(_SDDMM_HEADS)}, OK)],
+    extra=_PAIRS_REFUSED + _PAIRS + _HEADS_EXTRA + [
+        _NO_ROW, ("heads_before_nothing_to_do", {"heads": 0, "nnz": 0}, BAD), ("width_16_bit_y", {"head_dim": 12}, BAD),
+        ("width_16_bit", {"head_dim": 20, "x_dtype": F16}, BAD), ("width_fp32", {"head_dim": 6, "y_dtype": F32}, BAD)] + _beyond(x_dtype=F16))
+
+# ---- edge softmax (edge_softmax_kernels.hpp, edge_softmax_heads_kernels.hpp) ---------------------------------------------------------
+# scale: any finite float (negative: +inf masks); the workspace is the one 16-byte pointer
+_SOFTMAX_ZERO = [({"nnz": 0}, OK), ({"nnz": 0, "out": NULL}, OK), ({"nnz": 0, "num_rows": 0}, OK)]
+_SOFTMAX_EXTRA = [_NO_ROW, ("scale_negative", {"scale": -1.5}, LAUNCH), ("scale_zero", {"scale": 0.0}, LAUNCH)] + \
+    _refused("scale", NOT_FINITE, {"nnz": 0})
+for _name, _heads, _in in (("voltrix_launch_edge_softmax_csr", [], [("scores", P(4))]),
+                           ("voltrix_launch_edge_softmax_backward_csr", [], [("alpha", P(4)), ("grad_alpha", P(4))]),
+                           ("voltrix_launch_edge_softmax_heads_csr", [("heads", R(2, 1, 65535))], [("scores", P(4))]),
+                           ("voltrix_launch_edge_softmax_heads_backward_csr", [("heads", R(2, 1, 65535))],
+                            [("alpha", P(4)), ("grad_alpha", P(4))])):
+    _params = [("indptr", P(4)), ("num_rows", N(4)), _NNZ] + _heads + _in + [("scale", V(1.0)), ("out", P(4)), ("workspace", P(16))] + _END
+    row(_name, _params, zero=_SOFTMAX_ZERO + [({"nnz": 0, **_nulls(_params)}, OK)],
+        extra=_SOFTMAX_EXTRA + ([("heads_negative", {"heads": -1}, BAD),
+                                 ("heads_before_nothing_to_do", {"heads": 0, "nnz": 0}, BAD)] if _heads else []))
+
+# ---- multi-head aggregation (spmm_csr_heads_kernels.hpp): the entry count is the device's, so indices and values are required -------
+_WIDTHS = [("width_fp16", {"head_dim": 12, "dtype": F16}, BAD), ("width_bf16", {"head_dim": 20, "dtype": BF16}, BAD),
+           ("width_fp32", {"head_dim": 6, "dtype": F32}, BAD)]
+_AGG_HEADS = [("indptr", P(4)), ("indices", P(4)), ("values", P(4)), ("num_rows", N(4)), ("heads", R(2, 1, None)), ("head_dim", N(16)),
+              ("input", P(16)), ("dtype", R(F16, 0, 2)), ("output", P(16))] + _END
+row("voltrix_launch_spmm_csr_heads", _AGG_HEADS,
+    zero=[({"num_rows": 0}, OK), ({"num_rows": 0, "output": NULL}, OK), ({"head_dim": 0}, OK), ({"num_rows": 0, **_nulls(_AGG_HEADS)}, OK)],
+    extra=_HEADS_EXTRA + _WIDTHS + [("heads=-1", {"heads": -1}, BAD), ("heads_before_nothing_to_do", {"heads": 0, "num_rows": 0}, BAD),
+                                    ("width_before_nothing_to_do", {"head_dim": 12, "num_rows": 0}, BAD)])
+
+# ---- GAT and GATv2 scores and the row sums of their backward (gat_score_kernels.hpp, gatv2_score_kernels.hpp) -----------------------
+# slope: any finite float.  order: NULL has a meaning (the entries in CSR order) -- for the cases that is E: set at the baseline, NULL
+# accepted, misaligned refused.  The row sums zero-fill out for nnz == 0: with rows that is a launch and needs out.
+_EMPTY = {"nnz": 0, "num_rows": 0}
+_GAT_EXTRA = [("heads_negative", {"heads": -3}, BAD), ("heads_before_nothing_to_do", {"heads": 0, "nnz": 0}, BAD), _NO_ROW,
+              ("heads_times_num_rows_above_int_max", {"num_rows": 2 ** 20, "heads": 2 ** 12}, BAD)] + _refused("slope", NOT_FINITE, _EMPTY)
+_GAT = [("indptr", P(4)), ("indices", P(4)), ("num_rows", N(4)), _NNZ, ("heads", R(2, 1, 65535)), ("el", P(4)), ("er", P(4)),
+        ("slope", V(0.2)), ("out", P(4))] + _END
+row("voltrix_launch_gat_score_csr", _GAT,
+    zero=[(_EMPTY, OK), ({"nnz": 0}, OK), ({"nnz": 0, "out": NULL}, OK), ({"nnz": 0, **_nulls(_GAT)}, OK)],
+    extra=_GAT_EXTRA + [("slope_negative", {"slope": -0.5}, LAUNCH), ("four_heads", {"heads": 4}, LAUNCH)])
+_GAT_ROWSUM = [("indptr", P(4)), ("indices", P(4)), ("order", E(4)), ("num_rows", N(4)), _NNZ, ("heads", R(2, 1, 65535)), ("a", P(4)),
+               ("b", P(4)), ("grad", P(4)), ("slope", V(0.2)), ("out", P(4)), ("workspace", P(16))] + _END
+row("voltrix_launch_gat_score_rowsum_csr", _GAT_ROWSUM,
+    zero=[(_EMPTY, OK), ({**_EMPTY, "out": NULL}, OK), ({**_EMPTY, **_nulls(_GAT_ROWSUM)}, OK), ({"nnz": 0}, LAUNCH),
+          ({"nnz": 0, **_nulls(_GAT_ROWSUM, but=("out",))}, LAUNCH)],
+    extra=_GAT_EXTRA + [("rows_to_zero_fill_but_nowhere_to_write", {"nnz": 0, "out": NULL}, BAD)])
+
+# a head is a whole number of 16-byte pieces of xl / xr; dtype, width and slope are refused before "nothing to do"
+_GATV2_WIDTHS = [(F16, 4), (F16, 12), (BF16, 20), (F32, 2), (F32, 6)]
+_GATV2_EXTRA = [("heads_negative", {"heads": -3}, BAD), ("heads_before_nothing_to_do", {"heads": 0, **_EMPTY}, BAD), _NO_ROW,
+                ("head_dim_negative", {"head_dim": -8}, BAD),
+                ("heads_times_head_dim_above_int_max", {"heads": 2 ** 16, "head_dim": 2 ** 15}, BAD)] + \
+    [case for d, w in _GATV2_WIDTHS for case in ((f"width_{d}_{w}", {"dtype": d, "head_dim": w}, BAD),
+                                                 (f"width_{d}_{w},before_nothing_to_do", {"dtype": d, "head_dim": w, **_EMPTY}, BAD))] + \
+    _refused("dtype", (-1, 3), _EMPTY, alone=False) + _refused("dtype", (7,), _EMPTY) + _refused("slope", NOT_FINITE, _EMPTY)
+_GATV2_ZERO = [(_EMPTY, OK), ({**_EMPTY, "head_dim": 0}, OK)]
+_GATV2 = [("indptr", P(4)), ("indices", P(4)), ("num_rows", N(4)), _NNZ, ("heads", R(2, 1, None)), ("head_dim", N(8)), ("xl", P(16)),
+          ("xr", P(16)), ("dtype", R(F16, 0, 2)), ("a", P(16)), ("slope", V(0.2)), ("out", P(4))] + _END
+row("voltrix_launch_gatv2_score_csr", _GATV2,
+    zero=_GATV2_ZERO + [case for d in (F32, F16, BF16) for case in (({"nnz": 0, "dtype": d}, OK), ({"nnz": 0, "dtype": d, "out": NULL}, OK),
+                                                                    ({"head_dim": 0, "dtype": d, "a": NULL}, OK))] +
+    [({"nnz": 0, **_nulls(_GATV2)}, OK)],
+    extra=_GATV2_EXTRA + _off(("xl", "xr", "a"), 2) + [("fp32_rows", {"dtype": F32}, LAUNCH), ("bf16_rows", {"dtype": BF16}, LAUNCH)] +
+    _beyond(head_dim=16))
+# with nnz == 0 every row is zero-filled and indices, q, grad are not read
+_GATV2_ROWSUM = [("indptr", P(4)), ("indices", P(4)), ("order", E(4)), ("num_rows", N(4)), _NNZ, ("heads", R(2, 1, None)),
+                 ("head_dim", N(8)), ("p", P(16)), ("q", P(16)), ("dtype", R(F16, 0, 2)), ("grad", P(4)), ("slope", V(0.2)),
+                 ("out", P(16))] + _END
+row("voltrix_launch_gatv2_rowsum_csr", _GATV2_ROWSUM,
+    zero=_GATV2_ZERO + [({**_EMPTY, "out": NULL}, OK), ({"head_dim": 0, "out": NULL}, OK), ({**_EMPTY, **_nulls(_GATV2_ROWSUM)}, OK),
+                        ({"nnz": 0}, LAUNCH), ({"nnz": 0, "indices": NULL, "order": NULL, "q": NULL, "grad": NULL}, LAUNCH)],
+    extra=_GATV2_EXTRA + _off(("p", "q", "out"), 2) + [("rows_to_zero_fill_but_nowhere_to_write", {"nnz": 0, "out": NULL}, BAD)] +
+    _beyond(head_dim=16))
+
+# ---- edge softmax and aggregation in one launch, its two gradients, and the three with a keep mask (attn_aggregate_kernels.hpp,
+# ---- attn_aggregate_dropout.hpp, dropout_mask_kernels.hpp) ---------------------------------------------------------------------------
+# heads, the sizes, the width, dtype, scale and keep_scale are checked before "nothing to do".  keep_scale: finite and not negative
+# (-2^-140 is a negative fp32 subnormal).  The mask is read where an edge is: required when nnz > 0 and the call has something to do.
+_ATTN_EXTRA = _HEADS_EXTRA + _WIDTHS + [("heads_before_nothing_to_do", {"heads": 0, **_EMPTY}, BAD)] + _refused("scale", NOT_FINITE, _EMPTY)
+_KEEP = _refused("keep_scale", NOT_FINITE + (-1.0, -2.0 ** -140), _EMPTY)
+_KEEP_ZERO = [({"keep_scale": 0.0, **_EMPTY}, OK)]
+_SIZES = [("num_rows", N(4)), _NNZ, ("heads", R(2, 1, None)), ("head_dim", N(16))]
+_MASK = [("mask", P(4)), ("keep_scale", V(2.5))]
+
+_FORWARD = [("indptr", P(4)), ("indices", P(4)), ("scores", P(4))] + _SIZES + [("feat", P(16)), ("dtype", R(F16, 0, 2)), ("scale", V(1.0)),
+                                                                               ("out", P(16)), ("m", P(4)), ("l", P(4))]
+_GRAD_SCORES = [("indptr", P(4)), ("indices", P(4))] + _SIZES + [
+    ("grad_out", P(16)), ("feat", P(16)), ("dtype", R(F16, 0, 2)), ("scores", P(4)), ("m", P(4)), ("l", P(4)), ("delta", P(4)),
+    ("scale", V(1.0)), ("grad_scores", P(4))]
+# on the transposed CSR: its rows are the pattern's columns
+_GRAD_FEAT = [("t_indptr", P(4)), ("t_indices", P(4)), ("order", P(4)), ("num_cols", N(4))] + _SIZES[1:] + [
+    ("grad_out", P(16)), ("dtype", R(F32, 0, 2)), ("scores", P(4)), ("m", P(4)), ("l", P(4)), ("scale", V(1.0)), ("grad_feat", P(16))]
+for _name, _drop in (("voltrix_launch_attn_aggregate_csr", []), ("voltrix_launch_attn_aggregate_dropout_csr", _MASK)):
+    _params = _FORWARD + _drop + _END
+    # nnz == 0 with rows still zero-fills out and l: the outputs (and indptr) must be valid, the operands of the edges need not be
+    row(_name, _params,
+        zero=[(_EMPTY, OK), ({**_EMPTY, **_nulls(_params)}, OK), ({"head_dim": 0}, OK), ({"head_dim": 0, **_nulls(_params)}, OK),
+              ({"nnz": 0}, LAUNCH), ({"nnz": 0, **_nulls(_params, but=("indptr", "out", "m", "l"))}, LAUNCH)] + (_KEEP_ZERO if _drop else []),
+        extra=_ATTN_EXTRA + (_KEEP + _beyond(keep_scale=1.0) if _drop else []) +
+        [_NO_ROW, ("nnz_0_out+8", {"nnz": 0, "out": ("off", 8)}, BAD)] +
+        [(f"nnz_0_{p}=NULL", {"nnz": 0, p: NULL}, BAD) for p in ("indptr", "out", "m", "l")])
+for _name, _drop in (("voltrix_launch_attn_aggregate_grad_scores_csr", []), ("voltrix_launch_attn_aggregate_dropout_grad_scores_csr", _MASK)):
+    _params = _GRAD_SCORES + _drop + _END
+    row(_name, _params,
+        zero=[({"nnz": 0}, OK), ({"nnz": 0, **_nulls(_params)}, OK), (_EMPTY, OK), ({"head_dim": 0}, OK),
+              ({"head_dim": 0, **_nulls(_params)}, OK)] + (_KEEP_ZERO if _drop else []),
+        extra=_ATTN_EXTRA + (_KEEP + _beyond(keep_scale=1.0) if _drop else []) + [_NO_ROW])
+_EMPTY_T = {"nnz": 0, "num_cols": 0}
+for _name, _drop in (("voltrix_launch_attn_aggregate_grad_feat_csr", []), ("voltrix_launch_attn_aggregate_dropout_grad_feat_csr", _MASK)):
+    _params = _GRAD_FEAT + _drop + _END
+    # nnz == 0 with rows zero-fills grad_feat and reads nothing but t_indptr
+    row(_name, _params,
+        zero=[(_EMPTY_T, OK), ({**_EMPTY_T, **_nulls(_params)}, OK), ({"head_dim": 0}, OK), ({"head_dim": 0, **_nulls(_params)}, OK),
+              ({"nnz": 0}, LAUNCH), ({"nnz": 0, **_nulls(_params, but=("t_indptr", "grad_feat"))}, LAUNCH)] +
+        ([({"keep_scale": 0.0, **_EMPTY_T}, OK)] if _drop else []),
+        extra=_transposed(_ATTN_EXTRA + (_KEEP if _drop else []) + [_NO_ROW]) + _beyond(dtype=F16, **({"keep_scale": 1.0} if _drop else {})) +
+        [(f"nnz_0_{p}=NULL", {"nnz": 0, p: NULL}, BAD) for p in ("t_indptr", "grad_feat")])
+
+_DROPOUT = [_NNZ, ("heads", R(2, 1, None)), ("threshold", V(5)), ("seed", V(2 ** 63 + 1)), ("offset", V(2 ** 40)), ("mask", P(4))] + _END
+row("voltrix_launch_dropout_mask", _DROPOUT, zero=[({"nnz": 0}, OK), ({"nnz": 0, "mask": NULL}, OK)],
+    extra=[("heads_negative", {"heads": -1}, BAD), ("heads_before_nothing_to_do", {"heads": 0, "nnz": 0}, BAD),
+           ("mask+1", {"mask": ("off", 1)}, BAD),
+           ("threshold_and_counters_at_their_ends", {"threshold": 2 ** 32 - 1, "seed": 2 ** 64 - 1, "offset": 2 ** 64 - 1}, LAUNCH),
+           ("33_heads", {"heads": 33}, LAUNCH)] + _beyond(seed=7, offset=9))
+
+# ---- max / min / mean aggregation and the backward of max / min (spmm_csr_reduce_kernels.hpp) ----------------------------------------
+# arg: NULL = not computed, and it must be NULL for the mean.  The width, op, dtype and "the mean has no arg" come before "nothing to
+# do".  The forward's entry count is the device's: indices and input are required.  The backward with nnz == 0 reads t_indptr alone.
+_REDUCE = [("indptr", P(4)), ("indices", P(4)), ("num_rows", N(4)), ("embedding_dim", N(8)), ("input", P(16)), ("dtype", R(F32, 0, 2)),
+           ("op", R(0, 0, 2)), ("output", P(16)), ("arg", O(16))] + _END
+row("voltrix_launch_spmm_csr_reduce", _REDUCE,
+    zero=[({"num_rows": 0}, OK), ({"embedding_dim": 0}, OK), ({"num_rows": 0, **_nulls(_REDUCE)}, OK)],
+    extra=[("width_negative", {"embedding_dim": -4}, BAD), ("width_fp32", {"embedding_dim": 6}, BAD),
+           ("width_fp16", {"embedding_dim": 12, "dtype": F16}, BAD), ("width_bf16", {"embedding_dim": 12, "dtype": BF16}, BAD),
+           ("width_before_nothing_to_do", {"embedding_dim": 6, "num_rows": 0}, BAD), ("mean", {"op": 2}, LAUNCH),
+           ("min_with_arg", {"op": 1, "arg": SET}, LAUNCH), ("the_mean_has_no_arg", {"op": 2, "arg": SET}, BAD),
+           ("the_mean_has_no_arg,before_nothing_to_do", {"op": 2, "arg": SET, "num_rows": 0}, BAD)] +
+    [(f"{p}+4,with_arg", {p: ("off", 4), "arg": SET}, BAD) for p in ("input", "output")])
+_REDUCE_BACKWARD = [("t_indptr", P(4)), ("t_indices", P(4)), ("t_order", P(4)), ("num_cols", N(4)), ("num_entries", N(6, INT_MAX)),
+                    ("embedding_dim", N(8)), ("grad_out", P(16)), ("arg", P(16)), ("output", P(16))] + _END
+row("voltrix_launch_spmm_csr_reduce_backward", _REDUCE_BACKWARD,
+    zero=[({"num_cols": 0}, OK), ({"embedding_dim": 0}, OK), ({"num_cols": 0, **_nulls(_REDUCE_BACKWARD)}, OK), ({"num_entries": 0}, LAUNCH),
+          ({"num_entries": 0, **_nulls(_REDUCE_BACKWARD, but=("t_indptr", "output"))}, LAUNCH)],
+    extra=[("width_negative", {"embedding_dim": -4}, BAD), ("a_lane_owns_4_features", {"embedding_dim": 6}, BAD),
+           ("width_before_nothing_to_do", {"embedding_dim": 6, "num_cols": 0}, BAD),
+           ("no_entries_null_output", {"num_entries": 0, "output": NULL}, BAD)])
+
+# ---- neighbour sampling: the plain rule, with an exclusion list, on cumulative weights (neighbor_sample_kernels.hpp,
+# ---- weighted_sample_kernels.hpp) ------------------------------------------------------------------------------------------------------
+# fanout: 1 .. 64 or -1 (all); sizes, fanout and replace are checked before "nothing to do" (no seeds).  indices, the weights and the
+# outputs are looked at only where num_sampled > 0; an empty exclusion list may be NULL, but not misaligned.
+_NO_SEEDS = {"num_seeds": 0}
+_SAMPLE_TAIL = [("fanout", R(2, 1, 64)), ("replace", R(0, 0, 1)), ("seed", V(2 ** 63 + 1)), ("offset", V(2 ** 40))]
+_SAMPLE = [("indptr", P(4)), ("indices", P(4)), ("num_rows", N(4)), ("seeds", P(4)), ("num_seeds", N(3)), ("s_indptr", P(4)),
+           ("num_sampled", N(6, INT_MAX))] + _SAMPLE_TAIL
+_SAMPLE_OUT = [("s_indices", P(4)), ("s_entries", P(4))]
+_SAMPLE_EXTRA = _refused("fanout", (-2, INT_MAX, 2 ** 20), _NO_SEEDS) + _refused("fanout", (0, 65), _NO_SEEDS, alone=False) + \
+    _refused("replace", (-1, 2), _NO_SEEDS, alone=False) + _refused("num_rows", (-1,), _NO_SEEDS, alone=False) + \
+    _refused("num_sampled", (-1, 2 ** 31), _NO_SEEDS, alone=False) + [
+    ("fanout_all", {"fanout": -1}, LAUNCH), ("with_replacement", {"replace": 1}, LAUNCH), ("fanout_64", {"fanout": 64}, LAUNCH),
+    ("nothing_sampled_null_seeds", {"num_sampled": 0, "seeds": NULL}, BAD),
+    ("nothing_sampled_null_indptr", {"num_sampled": 0, "indptr": NULL}, BAD)]
+
+
+def _sample_zero(params, unread):
+    return [(_NO_SEEDS, OK), ({**_NO_SEEDS, **_nulls(params)}, OK)] + \
+        [({**_NO_SEEDS, "fanout": f, "replace": r}, OK) for f in (1, 64, -1) for r in (0, 1)] + \
+        [({**_NO_SEEDS, "fanout": f, "replace": r, **_nulls(params)}, OK) for f in (1, 64, -1) for r in (0, 1)] + \
+        [({"num_sampled": 0, "fanout": f, "replace": r, **{p: NULL for p in unread}}, OK) for f in (2, 1, 64, -1) for r in (0, 1)]
+
+
+_params = _SAMPLE + _SAMPLE_OUT + _END
+row("voltrix_launch_sample_neighbors", _params, zero=_sample_zero(_params, ("indices", "s_indices", "s_entries")), extra=_SAMPLE_EXTRA)
+_params = _SAMPLE + [("exclude", P(4)), ("num_exclude", N(2))] + _SAMPLE_OUT + _END
+row("voltrix_launch_sample_neighbors_excluding", _params, zero=_sample_zero(_params, ("indices", "s_indices", "s_entries")),
+    extra=_SAMPLE_EXTRA + _refused("num_exclude", (-1,), _NO_SEEDS, alone=False) + [
+        ("empty_list", {"num_exclude": 0}, LAUNCH), ("empty_list_may_be_null", {"num_exclude": 0, "exclude": NULL}, LAUNCH),
+        ("empty_list_misaligned", {"num_exclude": 0, "exclude": ("off", 2)}, BAD),
+        ("nothing_sampled_list_misaligned", {"num_sampled": 0, "exclude": ("off", 2)}, BAD),
+        ("nothing_sampled_empty_list_null", {"num_sampled": 0, "num_exclude": 0, "exclude": NULL, "indices": NULL, "s_indices": NULL,
+                                             "s_entries": NULL}, OK),
+        ("nothing_sampled_list_null", {"num_sampled": 0, "num_exclude": 1, "exclude": NULL}, BAD),
+        ("nothing_sampled_empty_list_misaligned", {"num_sampled": 0, "num_exclude": 0, "exclude": ("off", 2)}, BAD)])
+# cum is int64: 8 bytes
+_params = _SAMPLE[:2] + [("cum", P(8))] + _SAMPLE[2:] + _SAMPLE_OUT + _END
+row("voltrix_sample_neighbors_weighted", _params, zero=_sample_zero(_params, ("indices", "cum", "s_indices", "s_entries")),
+    extra=_SAMPLE_EXTRA + _off(("cum",), 2))
+
+# ---- relabelling a sampled block (neighbor_sample_kernels.hpp): sizes before "nothing to do" -------------------------------------------
+_params = [("cols", P(4)), ("num_sampled", N(6, INT_MAX)), ("num_cols", N(9)), ("table", P(4))] + _END
+row("voltrix_launch_block_mark", _params,
+    zero=[({"num_sampled": 0}, OK), ({"num_sampled": 0, **_nulls(_params)}, OK), ({"num_cols": 0}, OK),
+          ({"num_cols": 0, **_nulls(_params)}, OK)],
+    extra=[("size_before_nothing_to_do", {"num_sampled": -1, "num_cols": 0}, BAD)])
+_params = [("seeds", P(4)), ("num_seeds", N(3)), ("num_cols", N(9)), ("table", P(4))] + _END
+row("voltrix_launch_block_mark_seeds", _params,
+    zero=[({"num_seeds": 0}, OK), ({"num_seeds": 0, **_nulls(_params)}, OK), ({"num_cols": 0}, OK), ({"num_cols": 0, **_nulls(_params)}, OK)],
+    extra=[("size_before_nothing_to_do", {"num_seeds": -1, "num_cols": 0}, BAD)])
+_params = [("cols", P(4)), ("num_sampled", N(6, INT_MAX)), ("seeds", P(4)), ("num_seeds", N(3)), ("table", P(4)), ("rank", P(4)),
+           ("num_cols", N(9)), ("num_src", N(5)), ("local", P(4)), ("src_ids", P(4))] + _END
+_NO_BLOCK = {"num_sampled": 0, "num_seeds": 0, "num_src": 0}
+row("voltrix_launch_block_relabel", _params, zero=[(_NO_BLOCK, OK), ({**_NO_BLOCK, **_nulls(_params)}, OK)],
+    extra=[("fewer_sources_than_seeds", {"num_src": 2}, BAD), ("as_many_sources_as_seeds", {"num_src": 3}, LAUNCH),
+           ("seeds_alone", {"num_sampled": 0, "cols": NULL, "table": NULL, "rank": NULL, "local": NULL}, LAUNCH)])
+
+# ---- induced subgraphs and random walks (induced_subgraph_kernels.hpp) ---------------------------------------------------------------
+# group: one of the five widths, checked with the sizes before "nothing to do" (no rows).  The fill looks at s_local and s_entries only
+# where num_selected > 0.  Walks: length <= 2^20 and num_walkers * (length + 1) <= INT_MAX; indices and entries only where length > 0.
+GROUPS = (4, 8, 16, 32, 64)
+_NO_ROWS = {"num_sub_rows": 0}
+_SUBGRAPH = [("indptr", P(4)), ("indices", P(4)), ("num_rows", N(4)), ("rows", P(4)), ("num_sub_rows", N(3)), ("table", P(4)),
+             ("num_cols", N(9)), ("group", V(8))]
+_SUBGRAPH_EXTRA = _refused("group", (0, 1, 2, 3, 5, 12, 24, 48, 63, 65, 128, -4, -64), _NO_ROWS) + \
+    _refused("num_rows", (-1,), _NO_ROWS, alone=False) + \
+    [(f"group={g}", {"group": g}, LAUNCH) for g in GROUPS if g != 8]
+for _name, _tail in (("voltrix_launch_subgraph_count", [("counts", P(4))]),
+                     ("voltrix_launch_subgraph_fill",
+                      [("s_indptr", P(4)), ("num_selected", N(6, INT_MAX)), ("s_local", P(4)), ("s_entries", P(4))])):
+    _params = _SUBGRAPH + _tail + _END
+    _fill = len(_tail) > 1
+    row(_name, _params,
+        zero=[case for g in GROUPS for case in (({**_NO_ROWS, "group": g}, OK), ({**_NO_ROWS, "group": g, **_nulls(_params)}, OK))] +
+        ([({"num_selected": 0}, OK), ({"num_selected": 0, "s_local": NULL, "s_entries": NULL}, OK)] if _fill else []),   # nothing kept
+        extra=_SUBGRAPH_EXTRA + ([("num_selected_before_nothing_to_do", {"num_selected": 2 ** 31, **_NO_ROWS}, BAD),
+                                  ("nothing_kept_null_s_indptr", {"num_selected": 0, "s_indptr": NULL}, BAD)] if _fill else []))
+_params = [("indptr", P(4)), ("indices", P(4)), ("num_rows", N(4)), ("starts", P(4)), ("num_walkers", N(3)), ("length", N(5, 2 ** 20)),
+           ("seed", V(2 ** 63 + 1)), ("offset", V(2 ** 40)), ("nodes", P(4)), ("entries", P(4)), ("step_major", R(0, 0, 1))] + _END
+_NO_WALKERS = {"num_walkers": 0}
+row("voltrix_launch_random_walk", _params,
+    zero=[(_NO_WALKERS, OK), ({**_NO_WALKERS, **_nulls(_params)}, OK), ({**_NO_WALKERS, "length": 2 ** 20}, OK),
+          ({**_NO_WALKERS, "step_major": 1}, OK), ({"length": 0}, LAUNCH), ({"length": 0, "indices": NULL, "entries": NULL}, LAUNCH)],
+    extra=[("length_before_nothing_to_do", {"length": 2 ** 20 + 1, **_NO_WALKERS}, BAD),
+           ("walkers_times_steps_above_int_max", {"length": 2 ** 20, "num_walkers": 2048}, BAD),
+           ("walkers_times_steps_above_int_max_short", {"num_walkers": 2 ** 30, "length": 1}, BAD),
+           ("step_major", {"step_major": 1}, LAUNCH)])
+
+# ---- negative sampling, entry -> endpoints, (row, column) -> entry (negative_sample_kernels.hpp, find_edges_kernels.hpp) -------------
+# k: 1 .. 1024, max_tries: 1 .. 256, num_src * k <= INT_MAX; everything but the pointers is checked before "nothing to do".  indices
+# may be NULL (not misaligned) where num_entries == 0.
+_ENTRIES = ("num_entries", N(6, INT_MAX))
+_NO_INDICES = [("no_entries", {"num_entries": 0}, LAUNCH), ("no_entries_null_indices", {"num_entries": 0, "indices": NULL}, LAUNCH),
+               ("no_entries_misaligned_indices", {"num_entries": 0, "indices": ("off", 2)}, BAD)]
+_NO_SRC = {"num_src": 0}
+_params = [("indptr", P(4)), ("indices", P(4)), ("num_rows", N(4)), ("num_cols", N(9)), _ENTRIES, ("src", P(4)), ("num_src", N(3)),
+           ("k", R(5, 1, 1024)), ("max_tries", R(16, 1, 256)), ("exclude_self", R(0, 0, 1)), ("assume_sorted", R(1, 0, 1)),
+           ("seed", V(2 ** 63 + 1)), ("offset", V(2 ** 40)), ("neg", P(4))] + _END
+row("voltrix_launch_negative_sample", _params,
+    zero=[({**_NO_SRC, "assume_sorted": s, **nulls}, OK) for s in (1, 0) for nulls in ({}, _nulls(_params))] +
+    [({**_NO_SRC, "k": 1024, "max_tries": 256}, OK)],
+    extra=_NO_INDICES + [case for p, top in (("k", 1025), ("max_tries", 257)) for case in
+                         _refused(p, (-1, 2 ** 20), _NO_SRC) + _refused(p, (0, top), _NO_SRC, alone=False)] +
+    [case for p in ("num_rows", "num_cols", "num_entries") for case in _refused(p, (-1,), _NO_SRC, alone=False)] + [
+        ("slots_above_int_max", {"num_src": 2 ** 21, "k": 1024}, BAD), ("slots_above_int_max_k_2", {"num_src": INT_MAX, "k": 2}, BAD),
+        ("k_1024_tries_256", {"k": 1024, "max_tries": 256}, LAUNCH), ("exclude_self", {"exclude_self": 1}, LAUNCH),
+        ("unsorted", {"assume_sorted": 0}, LAUNCH)])
+_NO_IDS = {"num_ids": 0}
+_params = [("indptr", P(4)), ("indices", P(4)), ("num_rows", N(4)), _ENTRIES, ("entries", P(4)), ("num_ids", N(3)), ("rows", P(4)),
+           ("cols", P(4))] + _END
+row("voltrix_launch_edge_endpoints", _params, zero=[(_NO_IDS, OK), ({**_NO_IDS, **_nulls(_params)}, OK)],
+    extra=_NO_INDICES + _refused("num_rows", (-1,), _NO_IDS, alone=False) + _refused("num_entries", (2 ** 31,), _NO_IDS, alone=False))
+_NO_QUERIES = {"num_queries": 0}
+_params = [("indptr", P(4)), ("indices", P(4)), ("num_rows", N(4)), _ENTRIES, ("rows", P(4)), ("cols", P(4)), ("num_queries", N(3)),
+           ("assume_sorted", R(1, 0, 1)), ("out", P(4))] + _END
+row("voltrix_launch_find_edges", _params,
+    zero=[({**_NO_QUERIES, "assume_sorted": s, **nulls}, OK) for s in (1, 0) for nulls in ({}, _nulls(_params))],
+    extra=_NO_INDICES + _refused("num_rows", (-1,), _NO_QUERIES, alone=False) +
+    _refused("num_entries", (-1, 2 ** 31), _NO_QUERIES, alone=False) + _refused("assume_sorted", (2, -1), _NO_QUERIES, alone=False) +
+    [("unsorted", {"assume_sorted": 0}, LAUNCH)])
 
 # ---- the size functions: (name, arguments) -> the documented answer; ALIGNED: a multiple of 16 (the workspace is 16-byte aligned) ---
 ALIGNED = "a multiple of 16"

@@ -5,6 +5,9 @@ first library call and makes none unless that count is zero (exit code 3).
 
     python core_abi_worker.py
 
+A value goes through the binding's own argument types (``capi.SIGNATURES``): a Python float becomes the C float, seeds and offsets the
+64-bit unsigned words, a threshold the 32-bit one.
+
 Prints ``{"devices": n}`` first, then one JSON line ``{"id": ..., "rc": ...}`` per case as it returns (so that a crash names the case
 it happened in: the first one without a line), then ``{"done": count}``.  No torch, no package import: voltrix/capi.py is loaded by path.
 """

@@ -1,23 +1,19 @@
 """CPU: attention dropout's packed keep mask and the masked entry points of attn_aggregate.  A numpy restatement of
 Philox4x32-10 proves itself on the known-answer vectors and on the kept fraction; the four new C-ABI entry points are declared, bound
-and exported; their argument checks answer on the host before any launch; every new instantiation compiles for gfx950 without scratch
+and exported; their argument checks are rows of tests/core_abi_cases.py; every new instantiation compiles for gfx950 without scratch
 or LDS.  No GPU compute is called here (tests/test_gpu_attn_dropout.py compares the generator kernel with ``keep_bits`` / ``pack``)."""
-import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import REPO
 
-import test_attn_aggregate_host as base
+from kernel_resources import resource_usage
 from voltrix import capi
 
 HEADER = os.path.join(REPO, "include", "voltrix_capi.h")
-OK, BAD = base.VOLTRIX_OK, base.VOLTRIX_ERR_BAD_SHAPE
-F32, F16, BF16 = base.F32, base.F16, base.BF16
 NAMES = ("voltrix_launch_dropout_mask", "voltrix_launch_attn_aggregate_dropout_csr",
          "voltrix_launch_attn_aggregate_dropout_grad_scores_csr", "voltrix_launch_attn_aggregate_dropout_grad_feat_csr")
 
@@ -106,91 +102,6 @@ def test_header_declares_and_binding_lists_the_entry_points():
     assert callable(voltrix.dropout_mask) and callable(voltrix.apply_dropout_mask)
 
 
-def _mask_call(nnz=6, heads=2, threshold=5, seed=2 ** 63 + 1, offset=2 ** 40, null=False, offset_bytes=0):
-    buf = np.zeros(4096 + 16, np.uint8)
-    ptr = None if null else ctypes.c_void_p(buf.ctypes.data + (-buf.ctypes.data) % 16 + offset_bytes)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_dropout_mask(ctypes.c_int64(nnz), ctypes.c_int(heads), ctypes.c_uint32(threshold), ctypes.c_uint64(seed),
-                                           ctypes.c_uint64(offset), ptr, None, ctypes.byref(rc))
-    return rc.value
-
-
-def test_generator_argument_validation_on_the_host():
-    assert _mask_call(heads=0) == BAD and _mask_call(heads=-1) == BAD
-    assert _mask_call(heads=0, nnz=0) == BAD                                             # heads is checked before "nothing to do"
-    assert _mask_call(nnz=-1) == BAD and _mask_call(nnz=2 ** 31) == BAD
-    assert _mask_call(null=True) == BAD and _mask_call(offset_bytes=2) == BAD and _mask_call(offset_bytes=1) == BAD
-    assert _mask_call(nnz=0) == OK and _mask_call(nnz=0, null=True) == OK                # nothing to do: no launch
-
-
-FORWARD = base.FORWARD + ("mask",)
-GRAD_SCORES = base.GRAD_SCORES + ("mask",)
-GRAD_FEAT = base.GRAD_FEAT + ("mask",)
-
-
-def _forward(num_rows=4, nnz=6, heads=2, head_dim=16, dtype=F16, scale=1.0, null=None, offset=None, keep_scale=2.5):
-    bufs, p = base._ptrs(FORWARD, base._nulls(null), offset)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_attn_aggregate_dropout_csr(p["indptr"], p["indices"], p["scores"], ctypes.c_int(num_rows),
-                                                         ctypes.c_int64(nnz), ctypes.c_int(heads), ctypes.c_int(head_dim), p["feat"],
-                                                         ctypes.c_int(dtype), ctypes.c_float(scale), p["out"], p["m"], p["l"], p["mask"],
-                                                         ctypes.c_float(keep_scale), None, ctypes.byref(rc))
-    return rc.value
-
-
-def _grad_scores(num_rows=4, nnz=6, heads=2, head_dim=16, dtype=F16, scale=1.0, null=None, offset=None, keep_scale=2.5):
-    bufs, p = base._ptrs(GRAD_SCORES, base._nulls(null), offset)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_attn_aggregate_dropout_grad_scores_csr(
-        p["indptr"], p["indices"], ctypes.c_int(num_rows), ctypes.c_int64(nnz), ctypes.c_int(heads), ctypes.c_int(head_dim),
-        p["grad_out"], p["feat"], ctypes.c_int(dtype), p["scores"], p["m"], p["l"], p["delta"], ctypes.c_float(scale), p["out"],
-        p["mask"], ctypes.c_float(keep_scale), None, ctypes.byref(rc))
-    return rc.value
-
-
-def _grad_feat(num_rows=4, nnz=6, heads=2, head_dim=16, dtype=F32, scale=1.0, null=None, offset=None, keep_scale=2.5):
-    bufs, p = base._ptrs(GRAD_FEAT, base._nulls(null), offset)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_attn_aggregate_dropout_grad_feat_csr(
-        p["indptr"], p["indices"], p["order"], ctypes.c_int(num_rows), ctypes.c_int64(nnz), ctypes.c_int(heads), ctypes.c_int(head_dim),
-        p["grad_out"], ctypes.c_int(dtype), p["scores"], p["m"], p["l"], ctypes.c_float(scale), p["out"], p["mask"],
-        ctypes.c_float(keep_scale), None, ctypes.byref(rc))
-    return rc.value
-
-
-def _keep_scale_checks(call):
-    for bad in (float("inf"), float("-inf"), float("nan"), -1.0, -2.0 ** -140):
-        assert call(keep_scale=bad) == BAD, bad
-        assert call(keep_scale=bad, nnz=0, num_rows=0) == BAD, bad                       # before "nothing to do", like scale
-    assert call(keep_scale=0.0, nnz=0, num_rows=0) == OK
-
-
-def test_forward_argument_validation_on_the_host():
-    base._shared_checks(_forward, FORWARD, base.ALIGN16["forward"])                      # the mask: null, and 2 bytes off
-    _keep_scale_checks(_forward)
-    assert _forward(num_rows=0, nnz=0) == OK and _forward(num_rows=0, nnz=0, null=FORWARD) == OK
-    assert _forward(head_dim=0) == OK and _forward(head_dim=0, null=FORWARD) == OK
-    for name in ("indptr", "out", "m", "l"):
-        assert _forward(nnz=0, null=name) == BAD, name
-    assert _forward(nnz=0, offset=("out", 8)) == BAD
-
-
-def test_grad_scores_argument_validation_on_the_host():
-    base._shared_checks(_grad_scores, GRAD_SCORES, base.ALIGN16["grad_scores"])
-    _keep_scale_checks(_grad_scores)
-    assert _grad_scores(nnz=0) == OK and _grad_scores(nnz=0, null=GRAD_SCORES) == OK and _grad_scores(nnz=0, num_rows=0) == OK
-    assert _grad_scores(head_dim=0) == OK and _grad_scores(head_dim=0, null=GRAD_SCORES) == OK
-
-
-def test_grad_feat_argument_validation_on_the_host():
-    base._shared_checks(_grad_feat, GRAD_FEAT, base.ALIGN16["grad_feat"])
-    _keep_scale_checks(_grad_feat)
-    assert _grad_feat(num_rows=0, nnz=0) == OK and _grad_feat(num_rows=0, nnz=0, null=GRAD_FEAT) == OK
-    assert _grad_feat(head_dim=0) == OK and _grad_feat(head_dim=0, null=GRAD_FEAT) == OK
-    for name in ("indptr", "out"):
-        assert _grad_feat(nnz=0, null=name) == BAD, name
-
-
 def test_python_layer_rejects_bad_arguments_before_any_launch():
     import torch
 
@@ -252,22 +163,9 @@ void* the_generator() { return reinterpret_cast<void*>(&voltrix::dropout_mask_ke
 
 
 def test_every_new_instantiation_compiles_without_scratch_or_lds(tmp_path):
-    src = tmp_path / "attn_dropout.hip"
-    src.write_text(SOURCE)
-    inc = os.path.join(REPO, "voltrix-spmm_amd", "voltrix", "include")
-    run = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", inc,
-                          "-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o", str(tmp_path / "attn_dropout.o")],
-                         capture_output=True, text=True, timeout=900)
-    assert run.returncode == 0, run.stderr[-3000:]
     # the masked instantiations carry the template argument `true` (Lb1 in the mangled name); the generator is not a template
     keys = ("attn_aggregate_csr_kernel", "attn_aggregate_grad_scores_kernel", "attn_aggregate_grad_feat_kernel", "dropout_mask_kernel")
-    usage = {key: {} for key in keys}
-    for block in run.stderr.split("remark: Function Name: ")[1:]:
-        name = block.split(" ")[0].strip()
-        for key in keys:
-            if key in name and (key == "dropout_mask_kernel" or "Lb1" in name):
-                usage[key][name] = (int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", block).group(1)),
-                                    int(re.search(r"LDS Size \[bytes/block\]: (\d+)", block).group(1)))
-    assert [len(usage[key]) for key in keys] == [3, 6, 3, 1], {k: sorted(v) for k, v in usage.items()}
-    for group in usage.values():
-        assert all(v == (0, 0) for v in group.values()), group
+    usage, _ = resource_usage(SOURCE, tmp_path, "attn_dropout", keys)
+    usage = {n: v for n, v in usage.items() if "dropout_mask_kernel" in n or "Lb1" in n}
+    assert [len([n for n in usage if key in n]) for key in keys] == [3, 6, 3, 1], sorted(usage)
+    assert all((v[0], v[3]) == (0, 0) for v in usage.values()), usage

@@ -1,12 +1,14 @@
-"""CPU: the host-side argument contract of the core SpMM entry points -- the block-format, stream, panel and fused launchers with their
-combine passes, the CSR row-gather kernel, the table and plan builders and the helpers (tests/core_abi_cases.py has a row per entry
-point).  Every bad argument is answered on the host, before any launch: a null or misaligned pointer, a size below zero or beyond its
-limit, an enum outside its range and a width off the grid with VOLTRIX_ERR_BAD_SHAPE (VOLTRIX_ERR_OVERFLOW / _BAD_CONFIG where the
-header says so), "nothing to do" with VOLTRIX_OK.
+"""CPU: the host-side argument contract of EVERY entry point of the C ABI that launches -- the block-format, stream, panel and fused
+launchers with their combine passes, the CSR row-gather kernel, the table and plan builders and the helpers, and the operators on a
+device CSR: attention, max / min / mean, sampling (tests/core_abi_cases.py has a row per entry point).  Every bad argument is answered
+on the host, before any launch: a null or misaligned pointer, a size below zero or beyond its limit, an enum outside its range, a
+float that is not finite and a width off the grid with VOLTRIX_ERR_BAD_SHAPE (VOLTRIX_ERR_OVERFLOW / _BAD_CONFIG where the header
+says so), "nothing to do" with VOLTRIX_OK.
 
 The calls are made by ONE child process that cannot see a device (tests/core_abi_worker.py; HIP_VISIBLE_DEVICES=-1 on top of this
 process's own environment): where a check is missing the call ends at the runtime's "no device" (VOLTRIX_ERR_LAUNCH) instead of in a
 kernel on host pointers -- on a machine with a GPU as well.  A child that still sees a device makes no call and the tests FAIL."""
+import ctypes
 import json
 import os
 import subprocess
@@ -43,24 +45,33 @@ def answers():
 
 
 def test_every_launch_symbol_has_a_contract_test():
-    """In-process, no library call: a ``voltrix_launch_*`` symbol is a row of the table or one of the entry points that a per-operator
-    host test covers -- a new entry point without either fails here."""
-    launchers = {name for name in capi.SYMBOLS if name.startswith("voltrix_launch_")}
-    rows, elsewhere = set(table.ROWS), set(table.COVERED_ELSEWHERE)
-    assert not rows & elsewhere, sorted(rows & elsewhere)
-    assert not (rows | elsewhere) - launchers, f"not in capi.SYMBOLS: {sorted((rows | elsewhere) - launchers)}"
-    assert not launchers - rows - elsewhere, f"entry points without a host-side contract test: {sorted(launchers - rows - elsewhere)}"
-    host_tests = "".join(open(os.path.join(REPO, "tests", f)).read() for f in sorted(os.listdir(os.path.join(REPO, "tests")))
-                         if f.startswith("test_") and f.endswith("_host.py") and f != os.path.basename(__file__))
-    for name in elsewhere:
-        assert name in host_tests, f"{name}: listed as covered by a per-operator host test, but none names it"
+    """In-process, no library call: the table's rows are the symbols of the binding that return nothing and end in a stream and the
+    return-code slot (or, for the reference's host preprocess, a pointer and the slot) -- by their shape, not by their name.  Today
+    that is every ``voltrix_launch_*`` and the weighted sampler; a symbol that breaks the rule fails here instead of being left out."""
+    launching = {name for name, (restype, argtypes) in capi.SIGNATURES.items()
+                 if restype is None and argtypes[-2:] == [ctypes.c_void_p, capi._RC_P]}
+    rows = set(table.ROWS)
+    assert not launching - rows, f"entry points without a row in tests/core_abi_cases.py: {sorted(launching - rows)}"
+    assert not rows - launching, f"rows that are no launching symbol of capi.SIGNATURES: {sorted(rows - launching)}"
+    assert launching == {name for name in capi.SYMBOLS if name.startswith("voltrix_launch_")} | {"voltrix_sample_neighbors_weighted"}
+
+
+def test_every_launcher_with_nnz_refuses_two_to_the_31_on_the_host(answers):
+    """Every launcher the header declares with an ``int64_t nnz`` has a row whose ``nnz`` is limited to INT_MAX, and no other row has:
+    a new launcher that takes nnz belongs there.  The derived call with nnz = 2^31 is refused on the host, before any HIP call."""
+    from capi_header import prototypes
+
+    with_nnz = {name for name, (returns, params) in prototypes().items() if returns is None and (ctypes.c_int64, "nnz") in params}
+    limited = {name for name, r in table.ROWS.items()
+               if any(p == "nnz" and isinstance(role, table.N) and role.hi == table.INT_MAX for p, role in r["params"])}
+    assert with_nnz == limited and len(limited) == 17, sorted(with_nnz ^ limited)
+    for name in sorted(limited):
+        assert answers[f"{name}::nnz={2 ** 31}"] == table.BAD, name
 
 
 def test_rows_follow_the_binding():
     """A row has one role per parameter of ``capi.SIGNATURES``: pointer roles on ``void*`` (or the typed host pointer), the return-code
     slot last, values elsewhere; and the baseline of a required pointer is set, of an optional one NULL."""
-    import ctypes
-
     for name, r in table.ROWS.items():
         restype, argtypes = capi.SIGNATURES[name]
         assert restype is None and len(argtypes) == len(r["params"]), name
@@ -69,6 +80,9 @@ def test_rows_follow_the_binding():
         for (pname, role), ctype in zip(r["params"][:-1], argtypes[:-1]):
             pointer = ctype in (ctypes.c_void_p, capi._RC_P)
             assert pointer == (role.kind in ("pointer", "stream")), (name, pname)
+            if role.kind == "value":      # the value arrives as the binding's type: a float as a float, an integer inside its range
+                assert isinstance(role.value, float) == (ctype in (ctypes.c_float, ctypes.c_double)), (name, pname)
+                assert isinstance(role.value, float) or ctype(role.value).value == role.value, (name, pname)
             if role.kind == "pointer":
                 assert role.value == (table.NULL if isinstance(role, table.O) else table.SET), (name, pname)
                 assert role.align in (None, 4, 8, 16), (name, pname)
@@ -105,7 +119,14 @@ def test_the_table_derives_the_cases_the_contract_names():
     assert ids[f"voltrix_launch_csr_fill::num_edges={2 ** 31 - 2}"]["expect"] == 4           # num_edges + windows beyond int32
     assert ids[f"voltrix_launch_panel_plan_count::num_cols={2 ** 22 + 1}"]["expect"] == 3    # the two-level format is not built for it
     assert ids["voltrix_launch_chol_inv_transposed::k=0"]["expect"] == 1 and ids["voltrix_launch_chol_inv_transposed::k=65"]["expect"] == 1
-    assert len(ids) > 1000
+    assert ids[f"voltrix_launch_sddmm_csr::nnz={2 ** 31 - 1}(the limit)"]["expect"] == 2      # an entry count limited to INT_MAX ...
+    assert ids[f"voltrix_launch_sddmm_csr::nnz={2 ** 31}"]["expect"] == 1                     # ... and the first value beyond it
+    assert ids["voltrix_sample_neighbors_weighted::cum+4"]["expect"] == 1                    # int64 weights: 8 bytes wanted
+    for what in ("scale=inf", "scale=-inf", "scale=nan", "keep_scale=-1.0", f"keep_scale={-2.0 ** -140!r}"):   # floats, named by repr
+        assert ids[f"voltrix_launch_attn_aggregate_dropout_csr::{what}"]["expect"] == 1, what
+    assert ids["voltrix_launch_subgraph_count::group=12"]["expect"] == 1 and ids["voltrix_launch_subgraph_count::group=16"]["expect"] == 2
+    # the 1,163 cases of the table before it held every entry point, and the 1,069 distinct calls the per-operator host tests made
+    assert len(ids) >= 1163 + 1069
 
 
 def test_size_functions(answers):

@@ -2,11 +2,10 @@
 host program runs the headers' own ``exclude_row_count`` / ``exclude_cand`` / ``sample_row`` / ``find_entry`` -- the code the
 kernels run -- and agrees with the numpy restatement (tests/exclude_oracle.py): ``cand`` for every row of degree <= 10 and every subset
 of excluded positions, the known answers written out here, in the kernel header and in DESIGN.md, uniform draws among the candidates
-and never an excluded position; the two entry points are declared, bound and exported; their argument checks answer on the host before
-any HIP call; the Python layer raises before it looks at a tensor; the lookup kernel, in both instantiations, compiles for gfx950
+and never an excluded position; the two entry points are declared, bound and exported; their argument checks are rows of
+tests/core_abi_cases.py; the Python layer raises before it looks at a tensor; the lookup kernel, in both instantiations, compiles for gfx950
 without scratch, spilled registers or static LDS (the sampling kernel's report is tests/test_sample_host.py's).  No GPU compute is
 called here (tests/test_gpu_exclude.py compares the kernels with the same oracle)."""
-import ctypes
 import inspect
 import os
 import re
@@ -20,11 +19,11 @@ from conftest import REPO
 
 import exclude_oracle as oracle
 import sample_oracle
+from kernel_resources import resource_usage
 from voltrix import capi
 
 HEADER = os.path.join(REPO, "include", "voltrix_capi.h")
 INCLUDE = os.path.join(REPO, "voltrix-spmm_amd", "voltrix", "include")
-OK, BAD = 0, 1
 NAMES = ("voltrix_launch_sample_neighbors_excluding", "voltrix_launch_find_edges")
 
 
@@ -314,75 +313,6 @@ def test_header_declares_and_binding_lists_the_entry_points():
     assert "exclude" in inspect.signature(capi.launch_sample_neighbors).parameters
 
 
-def _ptrs(names, null, offset):
-    # host buffers: every call below is refused (or has nothing to do) before a pointer is dereferenced or a kernel launched
-    bufs = {k: np.zeros(4096 + 16, np.uint8) for k in names}
-    base = {k: b.ctypes.data + (-b.ctypes.data) % 16 for k, b in bufs.items()}
-    ptrs = {k: None if k in null else ctypes.c_void_p(base[k] + (offset[1] if offset and offset[0] == k else 0)) for k in names}
-    return bufs, ptrs
-
-
-SAMPLE = ("indptr", "indices", "seeds", "s_indptr", "exclude", "s_indices", "s_entries")
-FIND = ("indptr", "indices", "rows", "cols", "out")
-
-
-def _sample(num_rows=4, num_seeds=3, num_sampled=6, fanout=2, replace=0, seed=2 ** 63 + 1, offset=2 ** 40, num_exclude=2, null=(), at=None):
-    bufs, p = _ptrs(SAMPLE, null, at)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_sample_neighbors_excluding(p["indptr"], p["indices"], num_rows, p["seeds"], num_seeds, p["s_indptr"],
-                                                         num_sampled, fanout, replace, seed, offset, p["exclude"], num_exclude,
-                                                         p["s_indices"], p["s_entries"], None, ctypes.byref(rc))
-    return rc.value
-
-
-def _find(num_rows=4, num_entries=6, num_queries=3, assume_sorted=1, null=(), at=None):
-    bufs, p = _ptrs(FIND, null, at)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_find_edges(p["indptr"], p["indices"], num_rows, num_entries, p["rows"], p["cols"], num_queries,
-                                         assume_sorted, p["out"], None, ctypes.byref(rc))
-    return rc.value
-
-
-def test_sample_neighbors_excluding_argument_validation_on_the_host():
-    for name in SAMPLE:
-        assert _sample(null=(name,)) == BAD, name                                         # a null pointer
-        assert _sample(at=(name, 2)) == BAD, name                                         # 4 bytes wanted, off by 2
-    for size in ("num_rows", "num_seeds", "num_sampled", "num_exclude"):
-        assert _sample(**{size: -1}) == BAD, size
-    for size in ("num_rows", "num_sampled", "num_exclude"):
-        assert _sample(**{size: -1}, num_seeds=0) == BAD, size                            # sizes are checked before "nothing to do"
-    assert _sample(num_sampled=2 ** 31) == BAD and _sample(num_sampled=2 ** 31, num_seeds=0) == BAD
-    for fanout in (0, -2, 65, 2 ** 20):
-        assert _sample(fanout=fanout) == BAD and _sample(fanout=fanout, num_seeds=0) == BAD, fanout
-    for flag in (2, -1):
-        assert _sample(replace=flag) == BAD and _sample(replace=flag, num_seeds=0) == BAD
-    # nothing to do: no seeds (no pointer is looked at), or nothing sampled (the outputs and indices may be null then)
-    for fanout in (1, 64, -1):
-        for replace in (0, 1):
-            assert _sample(num_seeds=0, fanout=fanout, replace=replace) == OK
-            assert _sample(num_seeds=0, fanout=fanout, replace=replace, null=SAMPLE) == OK
-            assert _sample(num_sampled=0, fanout=fanout, replace=replace, null=("indices", "s_indices", "s_entries")) == OK
-    assert _sample(num_sampled=0, null=("indptr",)) == BAD and _sample(num_sampled=0, at=("exclude", 2)) == BAD
-    # an empty list may be null, a list with entries may not; a misaligned one is refused either way
-    assert _sample(num_sampled=0, num_exclude=0, null=("exclude", "indices", "s_indices", "s_entries")) == OK
-    assert _sample(num_sampled=0, num_exclude=1, null=("exclude",)) == BAD
-    assert _sample(num_sampled=0, num_exclude=0, at=("exclude", 2)) == BAD
-
-
-def test_find_edges_argument_validation_on_the_host():
-    for name in FIND:
-        assert _find(null=(name,)) == BAD, name
-        assert _find(at=(name, 2)) == BAD, name
-    for size in ("num_rows", "num_entries", "num_queries"):
-        assert _find(**{size: -1}) == BAD, size
-    assert _find(num_rows=-1, num_queries=0) == BAD and _find(num_entries=-1, num_queries=0) == BAD
-    assert _find(num_entries=2 ** 31) == BAD and _find(num_entries=2 ** 31, num_queries=0) == BAD
-    for flag in (2, -1):
-        assert _find(assume_sorted=flag) == BAD and _find(assume_sorted=flag, num_queries=0) == BAD
-    for flag in (0, 1):
-        assert _find(num_queries=0, assume_sorted=flag) == OK and _find(num_queries=0, assume_sorted=flag, null=FIND) == OK
-
-
 def test_python_layer_rejects_bad_arguments_before_any_tensor_is_looked_at():
     import torch
     import voltrix
@@ -426,30 +356,10 @@ template __global__ void voltrix::find_edges_kernel<false>(const int*, const int
 '''
 
 
-def resource_usage(workdir):
-    """{kernel: (scratch bytes per lane, spilled SGPRs, spilled VGPRs, static LDS bytes per block)} of the lookup kernels, and the
-    report's remark lines (what profiles/sample_exclude/resource_usage.txt holds; the sampling kernel, with and without a list, is
-    tests/test_sample_host.py's)."""
-    src = os.path.join(str(workdir), "exclude.hip")
-    with open(src, "w") as f:
-        f.write(SOURCE)
-    run = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", INCLUDE,
-                          "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(str(workdir), "exclude.o")],
-                         capture_output=True, text=True, timeout=900)
-    assert run.returncode == 0, run.stderr[-3000:]
-    usage = {}
-    for block in run.stderr.split("remark: Function Name: ")[1:]:
-        name = block.split(" ")[0].strip()
-        if "find_edges_kernel" in name:
-            grab = lambda key: int(re.search(key + r": (\d+)", block).group(1))  # noqa: E731
-            usage[name] = (grab(r"ScratchSize \[bytes/lane\]"), grab("SGPRs Spill"), grab("VGPRs Spill"), grab(r"LDS Size \[bytes/block\]"))
-    report = [line[line.index("voltrix/find_edges_kernels.hpp"):] for line in run.stderr.splitlines()
-              if "remark:" in line and "voltrix/find_edges_kernels.hpp" in line]
-    return usage, "\n".join(report) + "\n"
-
-
 def test_every_kernel_compiles_without_scratch_spills_or_lds(tmp_path):
-    usage, _ = resource_usage(tmp_path)
+    # the report's remark lines are what profiles/sample_exclude/resource_usage.txt holds; the sampling kernel, with and without a
+    # list, is tests/test_sample_host.py's
+    usage, _ = resource_usage(SOURCE, tmp_path, "exclude", ("find_edges_kernel",))
     # the lower bound and the scan.  The static LDS is 0 (a promoted per-lane array would show here)
     assert len(usage) == 2, sorted(usage)
     assert all(v == (0, 0, 0, 0) for v in usage.values()), usage

@@ -2,10 +2,8 @@
 and 2^12 in the place of 2^31 -- against the whole small problem worked out directly, so that the GPU run tests the kernels and not
 the test: the periodic pattern is a CSR and its transpose by periods is the stable sort of the whole pattern; the period's and the
 tail's float64 references, tiled, are the references of the whole problem; the slab-wise comparison visits every element and sees a
-single wrong one; the generators put entries on both sides of every boundary.  And every launcher of the attention family that takes
-``nnz`` refuses 2^31 on the host (``VOLTRIX_ERR_BAD_SHAPE``, nothing launched)."""
-import ctypes
-
+single wrong one; the generators put entries on both sides of every boundary.  (That every launcher which takes ``nnz`` refuses 2^31 on the
+host is tests/test_core_abi_host.py's.)"""
 import numpy as np
 import pytest
 import torch
@@ -230,56 +228,3 @@ def test_cast_bound_and_unpack_keep():
     assert torch.equal(keep, unpack_mask(mask, 33))
     words = torch.tensor([0, 1, -1, 5, -2 ** 31, 0x5A5A5A5A], dtype=torch.int32)
     assert loc.popcount32(words).tolist() == [0, 1, 32, 2, 1, 16]
-
-
-# ---- every launcher of the family that takes nnz refuses 2^31 on the host
-P, NNZ = "pointer", "nnz"
-F16 = 1
-# name -> the arguments of include/voltrix_capi.h in order, without the stream and the return code: P a 16-byte aligned host buffer,
-# NNZ the edge count under test, numbers as they are (4 rows or columns, 2 heads of 16 columns, fp16 operands, scale / slope / keep_scale)
-LAUNCHERS_WITH_NNZ = {
-    "voltrix_launch_sddmm_csr": (P, P, 4, NNZ, 16, P, F16, P, F16, P),
-    "voltrix_launch_edge_softmax_csr": (P, 4, NNZ, P, 1.0, P, P),
-    "voltrix_launch_edge_softmax_backward_csr": (P, 4, NNZ, P, P, 1.0, P, P),
-    "voltrix_launch_sddmm_heads_csr": (P, P, 4, NNZ, 2, 16, P, F16, P, F16, P),
-    "voltrix_launch_edge_softmax_heads_csr": (P, 4, NNZ, 2, P, 1.0, P, P),
-    "voltrix_launch_edge_softmax_heads_backward_csr": (P, 4, NNZ, 2, P, P, 1.0, P, P),
-    "voltrix_launch_gat_score_csr": (P, P, 4, NNZ, 2, P, P, 0.2, P),
-    "voltrix_launch_gat_score_rowsum_csr": (P, P, P, 4, NNZ, 2, P, P, P, 0.2, P, P),
-    "voltrix_launch_gatv2_score_csr": (P, P, 4, NNZ, 2, 16, P, P, F16, P, 0.2, P),
-    "voltrix_launch_gatv2_rowsum_csr": (P, P, P, 4, NNZ, 2, 16, P, P, F16, P, 0.2, P),
-    "voltrix_launch_attn_aggregate_csr": (P, P, P, 4, NNZ, 2, 16, P, F16, 1.0, P, P, P),
-    "voltrix_launch_attn_aggregate_grad_scores_csr": (P, P, 4, NNZ, 2, 16, P, P, F16, P, P, P, P, 1.0, P),
-    "voltrix_launch_attn_aggregate_grad_feat_csr": (P, P, P, 4, NNZ, 2, 16, P, F16, P, P, P, 1.0, P),
-    "voltrix_launch_dropout_mask": (NNZ, 2, 5, 7, 9, P),
-    "voltrix_launch_attn_aggregate_dropout_csr": (P, P, P, 4, NNZ, 2, 16, P, F16, 1.0, P, P, P, P, 1.0),
-    "voltrix_launch_attn_aggregate_dropout_grad_scores_csr": (P, P, 4, NNZ, 2, 16, P, P, F16, P, P, P, P, 1.0, P, P, 1.0),
-    "voltrix_launch_attn_aggregate_dropout_grad_feat_csr": (P, P, P, 4, NNZ, 2, 16, P, F16, P, P, P, 1.0, P, P, 1.0),
-}
-
-
-def _launch_on_the_host(name, nnz):
-    """The launcher's return code for the table's arguments with ``nnz`` edges, through the binding's own argument types."""
-    from voltrix import capi
-
-    buf = np.zeros(4096 + 16, np.uint8)
-    aligned = buf.ctypes.data + (-buf.ctypes.data) % 16
-    types = capi.SIGNATURES[name][1]
-    args = [aligned if v == P else nnz if v == NNZ else v for v in LAUNCHERS_WITH_NNZ[name]]
-    assert len(args) + 2 == len(types), name
-    for value, ctype in zip(LAUNCHERS_WITH_NNZ[name], types):      # the table follows the binding: pointers, the 64-bit nnz, floats
-        assert (value == P) == (ctype is ctypes.c_void_p) and (value == NNZ) == (ctype is ctypes.c_int64), (name, value, ctype)
-        assert isinstance(value, float) == (ctype is ctypes.c_float), (name, value, ctype)
-    rc = ctypes.c_int(-1)
-    getattr(capi.lib(), name)(*args, None, rc)
-    return rc.value
-
-
-def test_every_launcher_with_nnz_refuses_two_to_the_31_on_the_host():
-    from capi_header import prototypes
-
-    with_nnz = {name for name, (_, params) in prototypes().items()       # every launcher the header declares with an `int64_t nnz`
-                if name.startswith("voltrix_launch_") and (ctypes.c_int64, "nnz") in params}
-    assert with_nnz == set(LAUNCHERS_WITH_NNZ)               # a new launcher that takes nnz belongs in the table
-    for name in LAUNCHERS_WITH_NNZ:
-        assert _launch_on_the_host(name, 2 ** 31) == 1, name     # VOLTRIX_ERR_BAD_SHAPE, before any HIP call

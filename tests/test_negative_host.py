@@ -2,10 +2,9 @@
 (tests/negative_oracle.py) reproduces the known answers written out here, in the kernel header and in DESIGN.md, draws from a counter
 domain of its own, samples the non-neighbours uniformly and never a neighbour; a stand-alone host program runs the header's own
 ``negative_pick`` / ``entry_row`` -- the code the kernels run -- and agrees with it, sorted and unsorted; the two entry points are
-declared, bound and exported; their argument checks answer on the host before any HIP call; the Python layer raises before it looks at
+declared, bound and exported; their argument checks are rows of tests/core_abi_cases.py; the Python layer raises before it looks at
 a tensor; both kernels, in both ``SORTED`` instantiations, compile for gfx950 without scratch, spilled registers or LDS.  No GPU
 compute is called here (tests/test_gpu_negative.py compares the kernels with the same oracle)."""
-import ctypes
 import os
 import re
 import shutil
@@ -17,11 +16,11 @@ import pytest
 from conftest import REPO
 
 import negative_oracle as oracle
+from kernel_resources import resource_usage
 from voltrix import capi
 
 HEADER = os.path.join(REPO, "include", "voltrix_capi.h")
 INCLUDE = os.path.join(REPO, "voltrix-spmm_amd", "voltrix", "include")
-OK, BAD = 0, 1
 NAMES = ("voltrix_launch_negative_sample", "voltrix_launch_edge_endpoints")
 SRC = [0, 0, 5, 99]
 
@@ -251,67 +250,6 @@ def test_header_declares_and_binding_lists_the_entry_points():
         assert not hasattr(getattr(capi, wrapper), "timer_label"), wrapper
 
 
-def _ptrs(names, null, offset):
-    # host buffers: every call below is refused (or has nothing to do) before a pointer is dereferenced or a kernel launched
-    bufs = {k: np.zeros(4096 + 16, np.uint8) for k in names}
-    base = {k: b.ctypes.data + (-b.ctypes.data) % 16 for k, b in bufs.items()}
-    ptrs = {k: None if k in null else ctypes.c_void_p(base[k] + (offset[1] if offset and offset[0] == k else 0)) for k in names}
-    return bufs, ptrs
-
-
-NEGATIVE = ("indptr", "indices", "src", "neg")
-ENDPOINTS = ("indptr", "indices", "entries", "rows", "cols")
-
-
-def _negative(num_rows=4, num_cols=9, num_entries=6, num_src=3, k=5, max_tries=16, exclude_self=0, assume_sorted=1, seed=2 ** 63 + 1,
-              offset=2 ** 40, null=(), at=None):
-    bufs, p = _ptrs(NEGATIVE, null, at)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_negative_sample(p["indptr"], p["indices"], num_rows, num_cols, num_entries, p["src"], num_src, k, max_tries,
-                                              exclude_self, assume_sorted, seed, offset, p["neg"], None, ctypes.byref(rc))
-    return rc.value
-
-
-def _endpoints(num_rows=4, num_entries=6, num_ids=3, null=(), at=None):
-    bufs, p = _ptrs(ENDPOINTS, null, at)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_edge_endpoints(p["indptr"], p["indices"], num_rows, num_entries, p["entries"], num_ids, p["rows"],
-                                             p["cols"], None, ctypes.byref(rc))
-    return rc.value
-
-
-def test_negative_sample_argument_validation_on_the_host():
-    for name in NEGATIVE:
-        assert _negative(null=(name,)) == BAD, name                                       # a null pointer
-        assert _negative(at=(name, 2)) == BAD, name                                       # 4 bytes wanted, off by 2
-    for size in ("num_rows", "num_cols", "num_entries", "num_src"):
-        assert _negative(**{size: -1}) == BAD, size
-    for size in ("num_rows", "num_cols", "num_entries"):
-        assert _negative(**{size: -1}, num_src=0) == BAD, size                            # sizes are checked before "nothing to do"
-    assert _negative(num_entries=2 ** 31) == BAD
-    for k in (0, -1, 1025, 2 ** 20):
-        assert _negative(k=k) == BAD and _negative(k=k, num_src=0) == BAD, k
-    for tries in (0, -1, 257, 2 ** 20):
-        assert _negative(max_tries=tries) == BAD and _negative(max_tries=tries, num_src=0) == BAD, tries
-    for flag in (2, -1):
-        assert _negative(exclude_self=flag) == BAD and _negative(assume_sorted=flag) == BAD
-    assert _negative(num_src=2 ** 21, k=1024) == BAD and _negative(num_src=2 ** 31 - 1, k=2) == BAD          # S k above INT_MAX
-    for sorted_flag in (0, 1):
-        assert _negative(num_src=0, assume_sorted=sorted_flag) == OK and _negative(num_src=0, null=NEGATIVE, assume_sorted=sorted_flag) == OK
-    assert _negative(num_src=0, k=1024, max_tries=256) == OK
-
-
-def test_edge_endpoints_argument_validation_on_the_host():
-    for name in ENDPOINTS:
-        assert _endpoints(null=(name,)) == BAD, name
-        assert _endpoints(at=(name, 2)) == BAD, name
-    for size in ("num_rows", "num_entries", "num_ids"):
-        assert _endpoints(**{size: -1}) == BAD, size
-    assert _endpoints(num_rows=-1, num_ids=0) == BAD and _endpoints(num_entries=2 ** 31) == BAD
-    assert _endpoints(num_entries=2 ** 31, num_ids=0) == BAD
-    assert _endpoints(num_ids=0) == OK and _endpoints(num_ids=0, null=ENDPOINTS) == OK
-
-
 def test_python_layer_rejects_bad_arguments_before_any_tensor_is_looked_at():
     import torch
     import voltrix
@@ -356,29 +294,9 @@ void* the_endpoints() { return reinterpret_cast<void*>(&voltrix::edge_endpoints_
 '''
 
 
-def resource_usage(workdir):
-    """{kernel: (scratch bytes per lane, spilled SGPRs, spilled VGPRs, LDS bytes per block)} of every new kernel, and the report's
-    remark lines (what profiles/negative_sample/resource_usage.txt holds)."""
-    src = os.path.join(str(workdir), "negative.hip")
-    with open(src, "w") as f:
-        f.write(SOURCE)
-    run = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", INCLUDE,
-                          "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(str(workdir), "negative.o")],
-                         capture_output=True, text=True, timeout=900)
-    assert run.returncode == 0, run.stderr[-3000:]
-    usage = {}
-    for block in run.stderr.split("remark: Function Name: ")[1:]:
-        name = block.split(" ")[0].strip()
-        if "negative_sample_kernel" in name or "edge_endpoints_kernel" in name:
-            grab = lambda key: int(re.search(key + r": (\d+)", block).group(1))  # noqa: E731
-            usage[name] = (grab(r"ScratchSize \[bytes/lane\]"), grab("SGPRs Spill"), grab("VGPRs Spill"), grab(r"LDS Size \[bytes/block\]"))
-    report = [line[line.index("voltrix/negative_sample_kernels.hpp"):] for line in run.stderr.splitlines()
-              if "remark:" in line and "voltrix/negative_sample_kernels.hpp" in line]
-    return usage, "\n".join(report) + "\n"
-
-
 def test_every_kernel_compiles_without_scratch_spills_or_lds(tmp_path):
-    usage, _ = resource_usage(tmp_path)
+    # the report's remark lines are what profiles/negative_sample/resource_usage.txt holds
+    usage, _ = resource_usage(SOURCE, tmp_path, "negative", ("negative_sample_kernel", "edge_endpoints_kernel"))
     # the binary search, the scan and the endpoints: nothing per lane but registers
     assert len(usage) == 3 and len([n for n in usage if "negative_sample_kernel" in n]) == 2, sorted(usage)
     assert all(v == (0, 0, 0, 0) for v in usage.values()), usage

@@ -1,10 +1,9 @@
 """CPU: the neighbour sampling rule and its plumbing.  The numpy restatement (tests/sample_oracle.py) reproduces the
 known answers and draws uniformly; a stand-alone host program runs the header's own ``sample_row`` -- the code the kernel runs, here
 the instantiation of a launch without an exclusion list (tests/test_exclude_host.py runs the other, with and without a list) -- and
-agrees with it line by line; the four entry points are declared, bound and exported; their argument checks answer on the host before
-any launch; the Python layer raises before it looks at a tensor; every kernel compiles for gfx950 without scratch and without spilled
-registers.  No GPU compute is called here (tests/test_gpu_sample.py compares the kernels with the same oracle)."""
-import ctypes
+agrees with it line by line; the four entry points are declared, bound and exported; their argument checks are rows of
+tests/core_abi_cases.py; the Python layer raises before it looks at a tensor; every kernel compiles for gfx950 without scratch and
+without spilled registers.  No GPU compute is called here (tests/test_gpu_sample.py compares the kernels with the same oracle)."""
 import itertools
 import os
 import re
@@ -17,11 +16,11 @@ import pytest
 from conftest import REPO
 
 import sample_oracle as oracle
+from kernel_resources import resource_usage
 from voltrix import capi
 
 HEADER = os.path.join(REPO, "include", "voltrix_capi.h")
 INCLUDE = os.path.join(REPO, "voltrix-spmm_amd", "voltrix", "include")
-OK, BAD = 0, 1
 NAMES = ("voltrix_launch_sample_neighbors", "voltrix_launch_block_mark", "voltrix_launch_block_mark_seeds",
          "voltrix_launch_block_relabel")
 
@@ -175,82 +174,6 @@ def test_header_declares_and_binding_lists_the_entry_points():
         assert not hasattr(getattr(capi, wrapper), "timer_label"), wrapper
 
 
-def _ptrs(names, null, offset):
-    # host buffers: every call below is refused (or has nothing to do) before a pointer is dereferenced or a kernel launched
-    bufs = {k: np.zeros(4096 + 16, np.uint8) for k in names}
-    base = {k: b.ctypes.data + (-b.ctypes.data) % 16 for k, b in bufs.items()}
-    ptrs = {k: None if k in null else ctypes.c_void_p(base[k] + (offset[1] if offset and offset[0] == k else 0)) for k in names}
-    return bufs, ptrs
-
-
-SAMPLE = ("indptr", "indices", "seeds", "s_indptr", "s_indices", "s_entries")
-
-
-def _sample(num_rows=4, num_seeds=3, num_sampled=6, fanout=2, replace=0, seed=2 ** 63 + 1, offset=2 ** 40, null=(), at=None):
-    bufs, p = _ptrs(SAMPLE, null, at)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_sample_neighbors(p["indptr"], p["indices"], num_rows, p["seeds"], num_seeds, p["s_indptr"], num_sampled,
-                                               fanout, replace, seed, offset, p["s_indices"], p["s_entries"], None, ctypes.byref(rc))
-    return rc.value
-
-
-def test_sample_neighbors_argument_validation_on_the_host():
-    for name in SAMPLE:
-        assert _sample(null=(name,)) == BAD, name                                          # a null pointer
-        assert _sample(at=(name, 2)) == BAD, name                                          # 4 bytes wanted, off by 2
-    for fanout in (0, 65, -2, 2 ** 31 - 1):
-        assert _sample(fanout=fanout) == BAD, fanout
-        assert _sample(fanout=fanout, num_seeds=0) == BAD, fanout                          # checked before "nothing to do"
-    for replace in (-1, 2):
-        assert _sample(replace=replace) == BAD, replace
-    assert _sample(num_rows=-1) == BAD and _sample(num_seeds=-1) == BAD and _sample(num_sampled=-1) == BAD
-    assert _sample(num_sampled=2 ** 31) == BAD                                             # entry counts are limited to INT_MAX
-    assert _sample(num_seeds=0) == OK and _sample(num_seeds=0, null=SAMPLE) == OK          # S = 0: nothing to do, no launch
-    assert _sample(num_seeds=0, fanout=-1) == OK and _sample(num_seeds=0, fanout=64, replace=1) == OK
-    assert _sample(num_sampled=0, null=("indices", "s_indices", "s_entries")) == OK        # nothing sampled: nothing to write
-    assert _sample(num_sampled=0, null=("seeds",)) == BAD
-
-
-def _mark(num_sampled=6, num_cols=9, null=(), at=None):
-    bufs, p = _ptrs(("cols", "table"), null, at)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_block_mark(p["cols"], num_sampled, num_cols, p["table"], None, ctypes.byref(rc))
-    return rc.value
-
-
-def _mark_seeds(num_seeds=3, num_cols=9, null=(), at=None):
-    bufs, p = _ptrs(("seeds", "table"), null, at)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_block_mark_seeds(p["seeds"], num_seeds, num_cols, p["table"], None, ctypes.byref(rc))
-    return rc.value
-
-
-RELABEL = ("cols", "seeds", "table", "rank", "local", "src_ids")
-
-
-def _relabel(num_sampled=6, num_seeds=3, num_cols=9, num_src=5, null=(), at=None):
-    bufs, p = _ptrs(RELABEL, null, at)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_block_relabel(p["cols"], num_sampled, p["seeds"], num_seeds, p["table"], p["rank"], num_cols, num_src,
-                                            p["local"], p["src_ids"], None, ctypes.byref(rc))
-    return rc.value
-
-
-def test_block_entry_points_argument_validation_on_the_host():
-    for call, names, count in ((_mark, ("cols", "table"), "num_sampled"), (_mark_seeds, ("seeds", "table"), "num_seeds")):
-        for name in names:
-            assert call(null=(name,)) == BAD and call(at=(name, 2)) == BAD, name
-        assert call(**{count: -1}) == BAD and call(num_cols=-1) == BAD
-        assert call(**{count: -1}, num_cols=0) == BAD                                       # sizes are checked before "nothing to do"
-        assert call(**{count: 0}) == OK and call(**{count: 0}, null=names) == OK and call(num_cols=0, null=names) == OK
-    assert _mark(num_sampled=2 ** 31) == BAD
-    for name in RELABEL:
-        assert _relabel(null=(name,)) == BAD and _relabel(at=(name, 2)) == BAD, name
-    assert _relabel(num_sampled=-1) == BAD and _relabel(num_seeds=-1) == BAD and _relabel(num_cols=-1) == BAD
-    assert _relabel(num_sampled=2 ** 31) == BAD and _relabel(num_src=2) == BAD               # fewer sources than seeds
-    assert _relabel(num_sampled=0, num_seeds=0, num_src=0) == OK and _relabel(num_sampled=0, num_seeds=0, num_src=0, null=RELABEL) == OK
-
-
 def test_python_layer_rejects_bad_arguments_before_any_tensor_is_looked_at():
     import voltrix
 
@@ -286,19 +209,8 @@ void* the_relabel() { return reinterpret_cast<void*>(&voltrix::block_relabel_ker
 
 
 def test_every_kernel_compiles_without_scratch_or_spills(tmp_path):
-    src = tmp_path / "sample.hip"
-    src.write_text(SOURCE)
-    run = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", INCLUDE,
-                          "-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o", str(tmp_path / "sample.o")],
-                         capture_output=True, text=True, timeout=900)
-    assert run.returncode == 0, run.stderr[-3000:]
     keys = ("sample_neighbors_kernel", "block_mark_kernel", "block_mark_seeds_kernel", "block_relabel_kernel")
-    usage = {}
-    for block in run.stderr.split("remark: Function Name: ")[1:]:
-        name = block.split(" ")[0].strip()
-        if any(key in name for key in keys):
-            grab = lambda key: int(re.search(key + r": (\d+)", block).group(1))  # noqa: E731
-            usage[name] = (grab(r"ScratchSize \[bytes/lane\]"), grab("SGPRs Spill"), grab("VGPRs Spill"), grab(r"LDS Size \[bytes/block\]"))
+    usage, _ = resource_usage(SOURCE, tmp_path, "sample", keys)
     # with and without replacement, each without and with an exclusion list, and the three relabelling kernels.  The static LDS is 0
     # everywhere (a promoted per-lane array would show here); the dynamic LDS of the kernels without replacement is the launch's,
     # 256 k 4 bytes

@@ -1,11 +1,10 @@
 """CPU: the induced-subgraph contract, the walk rule and their plumbing.  The numpy restatement
 (tests/subgraph_oracle.py) reproduces the known answers of the walk rule, walks uniformly and restricts a hand-written CSR to the
 arrays written out here; a stand-alone host program runs the header's own ``walk_one`` / ``walk_step`` -- the code the kernel runs --
-and agrees with it; the three entry points are declared, bound and exported; their argument checks answer on the host before any HIP
-call; the Python layer raises before it looks at a tensor; every kernel, in every lane-group width, compiles for gfx950 without
-scratch and without spilled registers.  No GPU compute is called here (tests/test_gpu_subgraph.py compares the kernels with the same
+and agrees with it; the three entry points are declared, bound and exported; their argument checks are rows of
+tests/core_abi_cases.py; the Python layer raises before it looks at a tensor; every kernel, in every lane-group width, compiles for
+gfx950 without scratch and without spilled registers.  No GPU compute is called here (tests/test_gpu_subgraph.py compares the kernels with the same
 oracle)."""
-import ctypes
 import os
 import re
 import shutil
@@ -17,11 +16,11 @@ import pytest
 from conftest import REPO
 
 import subgraph_oracle as oracle
+from kernel_resources import resource_usage
 from voltrix import capi
 
 HEADER = os.path.join(REPO, "include", "voltrix_capi.h")
 INCLUDE = os.path.join(REPO, "voltrix-spmm_amd", "voltrix", "include")
-OK, BAD = 0, 1
 NAMES = ("voltrix_launch_subgraph_count", "voltrix_launch_subgraph_fill", "voltrix_launch_random_walk")
 GROUPS = (4, 8, 16, 32, 64)
 
@@ -261,75 +260,6 @@ def test_header_declares_and_binding_lists_the_entry_points():
     assert [voltrix.subgraph.group_for(nnz, 10) for nnz in (0, 40, 41, 80, 160, 320, 321, 10 ** 6)] == [4, 4, 8, 8, 16, 32, 64, 64]
 
 
-def _ptrs(names, null, offset):
-    # host buffers: every call below is refused (or has nothing to do) before a pointer is dereferenced or a kernel launched
-    bufs = {k: np.zeros(4096 + 16, np.uint8) for k in names}
-    base = {k: b.ctypes.data + (-b.ctypes.data) % 16 for k, b in bufs.items()}
-    ptrs = {k: None if k in null else ctypes.c_void_p(base[k] + (offset[1] if offset and offset[0] == k else 0)) for k in names}
-    return bufs, ptrs
-
-
-COUNT = ("indptr", "indices", "rows", "table", "counts")
-FILL = ("indptr", "indices", "rows", "table", "s_indptr", "s_local", "s_entries")
-WALK = ("indptr", "indices", "starts", "nodes", "entries")
-
-
-def _count(num_rows=4, num_sub_rows=3, num_cols=9, group=8, null=(), at=None):
-    bufs, p = _ptrs(COUNT, null, at)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_subgraph_count(p["indptr"], p["indices"], num_rows, p["rows"], num_sub_rows, p["table"], num_cols, group,
-                                             p["counts"], None, ctypes.byref(rc))
-    return rc.value
-
-
-def _fill(num_rows=4, num_sub_rows=3, num_cols=9, group=8, num_selected=6, null=(), at=None):
-    bufs, p = _ptrs(FILL, null, at)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_subgraph_fill(p["indptr"], p["indices"], num_rows, p["rows"], num_sub_rows, p["table"], num_cols, group,
-                                            p["s_indptr"], num_selected, p["s_local"], p["s_entries"], None, ctypes.byref(rc))
-    return rc.value
-
-
-def _walk(num_rows=4, num_walkers=3, length=5, seed=2 ** 63 + 1, offset=2 ** 40, step_major=0, null=(), at=None):
-    bufs, p = _ptrs(WALK, null, at)
-    rc = ctypes.c_int(-1)
-    capi.lib().voltrix_launch_random_walk(p["indptr"], p["indices"], num_rows, p["starts"], num_walkers, length, seed, offset,
-                                          p["nodes"], p["entries"], step_major, None, ctypes.byref(rc))
-    return rc.value
-
-
-def test_subgraph_entry_points_argument_validation_on_the_host():
-    for call, names in ((_count, COUNT), (_fill, FILL)):
-        for name in names:
-            assert call(null=(name,)) == BAD, name                                         # a null pointer
-            assert call(at=(name, 2)) == BAD, name                                         # 4 bytes wanted, off by 2
-        for size in ("num_rows", "num_sub_rows", "num_cols"):
-            assert call(**{size: -1}) == BAD, size
-        assert call(num_rows=-1, num_sub_rows=0) == BAD                                    # sizes are checked before "nothing to do"
-        for group in (0, 1, 2, 3, 5, 12, 24, 48, 63, 65, 128, -4, -64):
-            assert call(group=group) == BAD, group
-            assert call(group=group, num_sub_rows=0) == BAD, group
-        for group in GROUPS:
-            assert call(group=group, num_sub_rows=0) == OK and call(group=group, num_sub_rows=0, null=names) == OK
-    assert _fill(num_selected=-1) == BAD and _fill(num_selected=2 ** 31) == BAD            # entry counts are limited to INT_MAX
-    assert _fill(num_selected=2 ** 31, num_sub_rows=0) == BAD
-    assert _fill(num_selected=0, null=("s_local", "s_entries")) == OK                      # nothing kept: nothing to write
-    assert _fill(num_selected=0, null=("s_indptr",)) == BAD
-
-
-def test_random_walk_argument_validation_on_the_host():
-    for name in WALK:
-        assert _walk(null=(name,)) == BAD, name
-        assert _walk(at=(name, 2)) == BAD, name
-    assert _walk(num_rows=-1) == BAD and _walk(num_walkers=-1) == BAD and _walk(length=-1) == BAD
-    assert _walk(length=2 ** 20 + 1) == BAD and _walk(length=2 ** 20 + 1, num_walkers=0) == BAD
-    assert _walk(length=2 ** 20, num_walkers=2048) == BAD                                  # W (length + 1) above INT_MAX
-    assert _walk(num_walkers=2 ** 30, length=1) == BAD
-    assert _walk(step_major=2) == BAD and _walk(step_major=-1) == BAD
-    assert _walk(num_walkers=0) == OK and _walk(num_walkers=0, null=WALK) == OK and _walk(num_walkers=0, length=2 ** 20) == OK
-    assert _walk(num_walkers=0, step_major=1) == OK
-
-
 def test_python_layer_rejects_bad_arguments_before_any_tensor_is_looked_at():
     import torch
     import voltrix
@@ -366,29 +296,9 @@ void* the_walk() { return reinterpret_cast<void*>(&voltrix::random_walk_kernel);
 '''
 
 
-def resource_usage(workdir):
-    """{kernel: (scratch bytes per lane, spilled SGPRs, spilled VGPRs, LDS bytes per block)} of every new kernel, and the report's
-    remark lines (what profiles/subgraph/resource_usage.txt holds)."""
-    src = os.path.join(str(workdir), "subgraph.hip")
-    with open(src, "w") as f:
-        f.write(SOURCE)
-    run = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", INCLUDE,
-                          "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(str(workdir), "subgraph.o")],
-                         capture_output=True, text=True, timeout=900)
-    assert run.returncode == 0, run.stderr[-3000:]
-    usage = {}
-    for block in run.stderr.split("remark: Function Name: ")[1:]:
-        name = block.split(" ")[0].strip()
-        if "subgraph_kernel" in name or "random_walk_kernel" in name:
-            grab = lambda key: int(re.search(key + r": (\d+)", block).group(1))  # noqa: E731
-            usage[name] = (grab(r"ScratchSize \[bytes/lane\]"), grab("SGPRs Spill"), grab("VGPRs Spill"), grab(r"LDS Size \[bytes/block\]"))
-    report = [line[line.index("voltrix/induced_subgraph_kernels.hpp"):] for line in run.stderr.splitlines()
-              if "remark:" in line and "voltrix/induced_subgraph_kernels.hpp" in line]
-    return usage, "\n".join(report) + "\n"
-
-
 def test_every_kernel_compiles_without_scratch_or_spills(tmp_path):
-    usage, _ = resource_usage(tmp_path)
+    # the report's remark lines are what profiles/subgraph/resource_usage.txt holds
+    usage, _ = resource_usage(SOURCE, tmp_path, "subgraph", ("subgraph_kernel", "random_walk_kernel"))
     # count and fill in five widths, and the walk.  No LDS anywhere: the compaction goes through the ballot
     assert len(usage) == 11 and len([n for n in usage if "subgraph_kernel" in n]) == 10, sorted(usage)
     assert all(v == (0, 0, 0, 0) for v in usage.values()), usage

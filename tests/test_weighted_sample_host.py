@@ -1,10 +1,9 @@
 """CPU: the weighted neighbour sampling rule and its plumbing.  The numpy restatement
 (tests/weighted_sample_oracle.py) reproduces committed answers and hand-computed tables and draws with the probabilities of successive
 sampling; a stand-alone host program runs the header's own ``weighted_sample_row`` -- the code the kernel runs -- on every row of the
-GPU tests' graph and agrees with the oracle position by position; the C symbol is declared, bound and refuses bad arguments on the host
-before any HIP call; the Python layer raises before it looks at a tensor; both kernels compile for gfx950 without scratch and without
+GPU tests' graph and agrees with the oracle position by position; the C symbol is declared and bound, and its argument checks are a row of
+tests/core_abi_cases.py; the Python layer raises before it looks at a tensor; both kernels compile for gfx950 without scratch and without
 spilled registers.  No GPU compute is called here (tests/test_gpu_weighted_sample.py compares the kernels with the same oracle)."""
-import ctypes
 import itertools
 import os
 import re
@@ -17,10 +16,10 @@ import pytest
 from conftest import REPO
 
 import weighted_sample_oracle as oracle
+from kernel_resources import resource_usage
 from voltrix import capi
 
 INCLUDE = os.path.join(REPO, "voltrix-spmm_amd", "voltrix", "include")
-OK, BAD = 0, 1
 NAME = "voltrix_sample_neighbors_weighted"
 ONE = 1 << 30
 
@@ -208,42 +207,10 @@ def test_header_declares_and_binding_lists_the_symbol():
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "voltrix_capi.h")).read(), flags=re.S)
     assert re.search(rf"\b{NAME}\s*\(", text)
     assert NAME in capi.SYMBOLS and NAME in capi.SIGNATURES and hasattr(capi.lib(), NAME)
-    assert not NAME.startswith("voltrix_launch_")            # it joins the launchers' contract table when that is next opened
+    assert not NAME.startswith("voltrix_launch_")            # in the launchers' contract table by its signature, not by its name
     assert capi.lib().voltrix_abi_version() == 2
     assert callable(voltrix.sampling_weights) and voltrix.SamplingWeights is voltrix.sampling.SamplingWeights
     assert not hasattr(capi.sample_neighbors_weighted, "timer_label")
-
-
-ARGS = ("indptr", "indices", "cum", "seeds", "s_indptr", "s_indices", "s_entries")
-
-
-def _call(num_rows=4, num_seeds=3, num_sampled=6, fanout=2, replace=0, seed=2 ** 63 + 1, offset=2 ** 40, null=(), at=None):
-    # host buffers: every call below is refused (or has nothing to do) before a pointer is dereferenced or a kernel launched
-    bufs = {k: np.zeros(4096 + 16, np.uint8) for k in ARGS}
-    base = {k: b.ctypes.data + (-b.ctypes.data) % 16 for k, b in bufs.items()}
-    p = {k: None if k in null else ctypes.c_void_p(base[k] + (at[1] if at and at[0] == k else 0)) for k in ARGS}
-    rc = ctypes.c_int(-1)
-    getattr(capi.lib(), NAME)(p["indptr"], p["indices"], p["cum"], num_rows, p["seeds"], num_seeds, p["s_indptr"], num_sampled, fanout,
-                              replace, seed, offset, p["s_indices"], p["s_entries"], None, ctypes.byref(rc))
-    return rc.value
-
-
-def test_argument_validation_on_the_host():
-    for name in ARGS:
-        assert _call(null=(name,)) == BAD, name                                            # a null pointer
-        assert _call(at=(name, 2)) == BAD, name                                            # off by 2
-    assert _call(at=("cum", 4)) == BAD                                                     # cum is int64: 8 bytes wanted, off by 4
-    for fanout in (0, 65, -2, 2 ** 31 - 1):
-        assert _call(fanout=fanout) == BAD, fanout
-        assert _call(fanout=fanout, num_seeds=0) == BAD, fanout                            # checked before "nothing to do"
-    for replace in (-1, 2):
-        assert _call(replace=replace) == BAD, replace
-    assert _call(num_rows=-1) == BAD and _call(num_seeds=-1) == BAD and _call(num_sampled=-1) == BAD
-    assert _call(num_sampled=2 ** 31) == BAD                                               # entry counts are limited to INT_MAX
-    assert _call(num_seeds=0) == OK and _call(num_seeds=0, null=ARGS) == OK                # S = 0: nothing to do, no launch
-    assert _call(num_seeds=0, fanout=-1) == OK and _call(num_seeds=0, fanout=64, replace=1) == OK
-    assert _call(num_sampled=0, null=("indices", "cum", "s_indices", "s_entries")) == OK   # nothing sampled: nothing to write
-    assert _call(num_sampled=0, null=("seeds",)) == BAD
 
 
 def test_python_layer_rejects_prob_misuse_before_any_tensor_is_looked_at():
@@ -273,18 +240,7 @@ template __global__ void voltrix::sample_neighbors_weighted_kernel<true>(const v
 
 
 def test_both_kernels_compile_without_scratch_or_spills(tmp_path):
-    src = tmp_path / "weighted.hip"
-    src.write_text(SOURCE)
-    run = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", INCLUDE,
-                          "-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o", str(tmp_path / "weighted.o")],
-                         capture_output=True, text=True, timeout=900)
-    assert run.returncode == 0, run.stderr[-3000:]
-    usage = {}
-    for block in run.stderr.split("remark: Function Name: ")[1:]:
-        name = block.split(" ")[0].strip()
-        if "sample_neighbors_weighted_kernel" in name:
-            grab = lambda key: int(re.search(key + r": (\d+)", block).group(1))  # noqa: E731
-            usage[name] = (grab(r"ScratchSize \[bytes/lane\]"), grab("SGPRs Spill"), grab("VGPRs Spill"), grab(r"LDS Size \[bytes/block\]"))
+    usage, _ = resource_usage(SOURCE, tmp_path, "weighted", ("sample_neighbors_weighted_kernel",))
     # with and without replacement.  The static LDS is 0 (a promoted per-lane array would show here); the dynamic LDS is the launch's,
     # 256 k 4 bytes without replacement only (weighted_sample_lds_bytes, printed by the host program above)
     assert len(usage) == 2, sorted(usage)
