@@ -792,6 +792,46 @@ void voltrix_launch_spmm_csr_reduce(void* indptr, void* indices, int num_rows, i
 void voltrix_launch_spmm_csr_reduce_backward(void* t_indptr, void* t_indices, void* t_order, int num_cols, int64_t num_entries, int embedding_dim,
                                              void* grad_out, void* arg, void* output, void* stream, int* return_code);
 
+/* Aggregation with a feature VECTOR per edge on a DEVICE CSR (spmm_edge_kernels.hpp): op 0 mul, 1 add, 2 add_relu, 3 copy, 4 gate.
+ *   output[r, f] = sum over the entries e of row r of m(input[indices[e], f], efeat[id_e, f]),  id_e = order ? order[e] : e
+ *   m(x, w) = x * w (mul) | x + w (add) | max(x + w, 0) (add_relu) | w (copy: input is not read) |
+ *             (self[r, f] + w) > 0 ? x : 0 (gate: the gradient of add_relu for the gathered operand, run on the transposed CSR with
+ *             input = grad_out, self = the forward's gathered operand, order = t_order)
+ * num_entries = the pattern's entry count nnz; order = device int32[nnz] or NULL; input = device [*, embedding_dim] of input_dtype;
+ * efeat = device [nnz, embedding_dim] of efeat_dtype; self = device [num_rows, embedding_dim] of efeat_dtype (gate only, else NULL);
+ * output = device float[num_rows, embedding_dim], every element written, a row without entries 0.  dtypes: 0 fp32 / 1 fp16 / 2
+ * bfloat16, read as they are; the pairs (input_dtype, efeat_dtype) are (T, T) and (fp32, fp16 | bf16); gate takes input_dtype fp32
+ * only; copy ignores input_dtype.  fp32 additions in CSR order: |output - ref| <= (k + 1) 2^-23 sum |terms| for the k terms of an
+ * element.  max(x + w, 0) is a compare and a select: a NaN or inf propagates as the arithmetic does (max(NaN + w, 0) is NaN).  The gate
+ * is one fp32 addition of the exactly converted operands, so its sign is that of the exact sum; it is closed at 0 and a closed gate
+ * passes nothing.  One launch, a row per lane group (a hub row serialises its wave, as in voltrix_launch_spmm_csr_heads), 16 bytes of
+ * efeat per lane and entry, no LDS, no workspace, no float atomics, no host synchronisation, the same bits on every call; element
+ * offsets are 64-bit (nnz * embedding_dim may pass 2^31).
+ * RETURNS the status code (no return_code slot).  VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: negative
+ * sizes, num_entries > INT_MAX, an unknown op or dtype, a pair that is not instantiated, embedding_dim not a multiple of 16 bytes of
+ * efeat (8 for 16-bit, 4 for fp32), a null indptr / indices / efeat / output, a null input unless op is copy, a null self with gate, a
+ * misaligned pointer; VOLTRIX_OK without a launch for num_rows == 0 or embedding_dim == 0.  On a pattern without entries output is
+ * zero-filled and indices, input, efeat and order are not read (they must still be valid pointers).  Nothing is checked on the device.
+ * Alignment: indptr, indices, order 4 bytes; input, efeat, self, output 16 bytes.  No reference counterpart. */
+int voltrix_spmm_edge_csr(void* indptr, void* indices, void* order, int num_rows, int64_t num_entries, int embedding_dim,
+                          void* input, int input_dtype, void* efeat, int efeat_dtype, void* self, int op,
+                          void* output, void* stream);
+
+/* The gradient of voltrix_spmm_edge_csr for efeat, row-parallel on the same CSR: op 0 mul, 1 add, 2 add_relu, 3 copy.
+ *   output[e, f] = grad_out[row_e, f] * feat[indices[e], f] (mul) | grad_out[row_e, f] (add, copy) |
+ *                  (feat[indices[e], f] + efeat[e, f]) > 0 ? grad_out[row_e, f] : 0 (add_relu)
+ * grad_out = device float[num_rows, embedding_dim]; feat = device [*, embedding_dim] and efeat = device [nnz, embedding_dim], both of
+ * dtype (0 fp32 / 1 fp16 / 2 bfloat16); output = device float[nnz, embedding_dim], every element written.  feat is read by mul and
+ * add_relu, efeat by add_relu alone; what an op does not read may be NULL.  mul rounds once (|output - ref| <= 2^-23 |ref|), the others
+ * are exact.  One launch, a row per lane group (a hub row serialises its wave), 16-byte stores, no atomics, the same bits on every call,
+ * 64-bit element offsets.
+ * RETURNS the status code.  VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: negative sizes, num_entries > INT_MAX, an unknown
+ * op (gate included) or dtype, embedding_dim not a multiple of 16 bytes of dtype, a null indptr / grad_out / output, a null operand the
+ * op reads (indices and feat: mul, add_relu; efeat: add_relu), a misaligned pointer; VOLTRIX_OK without a launch for num_rows == 0,
+ * embedding_dim == 0 or num_entries == 0.  Nothing is checked on the device.  Alignment: indptr, indices 4 bytes; the others 16. */
+int voltrix_spmm_edge_grad_efeat_csr(void* indptr, void* indices, int num_rows, int64_t num_entries, int embedding_dim,
+                                     void* grad_out, void* feat, void* efeat, int dtype, int op, void* output, void* stream);
+
 /* Neighbour sampling on a device int32 CSR and the relabelling of a sampled block (voltrix/neighbor_sample_kernels.hpp): what produces
  * the rectangular [num_dst, num_src] patterns the CSR operators above take (GraphSAGE-style mini-batches).  No reference counterpart.
  * THE SAMPLING RULE.  For a seed row r (its global row id), fan-out k = fanout, degree d = indptr[r + 1] - indptr[r]:

@@ -488,6 +488,49 @@ class SpMMReduce(_PatternOp):
         return _SpMMReduceFunction.apply(feat, self)
 
 
+class _SpMMEdgeFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, efeat, op, kind):
+        from .spmm_edge import spmm_edge
+
+        ctx.op, ctx.kind = op, kind
+        ctx.feat_dtype, ctx.efeat_dtype = None if feat is None else feat.dtype, efeat.dtype
+        if kind in ("mul", "add_relu"):         # add and copy: the gradients are functions of grad_out alone
+            ctx.save_for_backward(feat, efeat)
+        return spmm_edge(op.indptr, op.indices, feat, efeat, op.num_rows, kind)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .spmm_edge import grad_efeat, grad_feat
+
+        op, kind = ctx.op, ctx.kind
+        feat, efeat = ctx.saved_tensors if ctx.saved_tensors else (None, None)
+        d_feat = d_efeat = None
+        if kind != "copy" and ctx.needs_input_grad[0]:
+            d_feat = grad_feat(op.t_indptr, op.t_indices, op.t_order, grad_out, feat, efeat, kind, op.num_cols).to(ctx.feat_dtype)
+        if ctx.needs_input_grad[1]:
+            d_efeat = grad_efeat(op.indptr, op.indices, grad_out, feat, efeat, kind).to(ctx.efeat_dtype)
+        return d_feat, d_efeat, None, None
+
+
+class SpMMEdge(_PatternOp):
+    """``out[r] = sum over the entries e of row r of m(feat[col_e], efeat[e])`` per element on a CSR pattern [num_rows, num_cols]
+    (``num_cols`` defaults to ``num_rows``), differentiable in both operands: ``SpMMEdge(indptr, indices, n)(feat, efeat, op="mul")`` with
+    ``op`` one of ``"mul"``, ``"add"``, ``"add_relu"`` (GINE's message ``relu(x_j + e_ij)``) and ``"copy"`` (``feat=None``) -- the
+    aggregation of GINE, NNConv / MPNN and CGConv layers (``voltrix.spmm_edge``).  ``feat`` [num_cols, ...], ``efeat`` [nnz, ...] in
+    CSR entry order with the same trailing dimensions.  Built once per pattern like the attention operators, or ``SpMMEdge(pattern)`` on
+    a ``CsrPattern`` shared with them.  Only the gradients ``needs_input_grad`` asks for are computed: ``efeat``'s by one row-parallel
+    launch, ``feat``'s by a gather on the transposed CSR.  mul and add_relu save both operands, add and copy nothing.  No index op, no
+    float atomics, the same bits on every call; ``out`` is float32 and the gradients come back in the operands' dtypes."""
+
+    def __call__(self, feat, efeat: torch.Tensor, op: str = "mul") -> torch.Tensor:
+        from .spmm_edge import check_operands
+
+        check_operands("SpMMEdge", op, feat, efeat, self.num_edges)
+        assert feat is None or feat.shape[0] == self.num_cols, (tuple(feat.shape), self.num_cols)
+        return _SpMMEdgeFunction.apply(feat, efeat, self, op)
+
+
 class SpMM:
     """``C = A @ B`` with a gradient for ``B``.  ``A``: binary CSR [num_rows, num_cols] (``num_cols`` defaults to
     ``num_rows``), or, with ``values`` (round 6), the weighted matrix ``csr(values)``.  Builds two reference-format handles on the current device (A and A^T); both go through

@@ -106,6 +106,8 @@ SIGNATURES = {
     "voltrix_launch_attn_aggregate_dropout_grad_feat_csr": (None, [_P, _P, _P, _I, _L, _I, _I, _P, _I, _P, _P, _P, _F, _P, _P, _F, _P, _RC_P]),
     "voltrix_launch_spmm_csr_reduce": (None, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _RC_P]),
     "voltrix_launch_spmm_csr_reduce_backward": (None, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _RC_P]),
+    "voltrix_spmm_edge_csr": (_I, [_P, _P, _P, _I, _L, _I, _P, _I, _P, _I, _P, _I, _P, _P]),
+    "voltrix_spmm_edge_grad_efeat_csr": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _I, _I, _P, _P]),
     "voltrix_launch_sample_neighbors": (None, [_P, _P, _I, _P, _I, _P, _L, _I, _I, _U64, _U64, _P, _P, _P, _RC_P]),
     "voltrix_launch_block_mark": (None, [_P, _L, _I, _P, _P, _RC_P]),
     "voltrix_launch_block_mark_seeds": (None, [_P, _I, _I, _P, _P, _RC_P]),
@@ -939,6 +941,52 @@ def launch_spmm_csr_reduce_backward(t_indptr, t_indices, t_order, num_cols: int,
     assert output.dtype == torch.float32 and output.is_contiguous() and output.shape == (num_cols, grad_out.shape[1])
     _checked("voltrix_launch_spmm_csr_reduce_backward", t_indptr.data_ptr(), t_indices.data_ptr(), t_order.data_ptr(), num_cols, nnz,
              grad_out.shape[1], grad_out.data_ptr(), arg.data_ptr(), output.data_ptr(), stream)
+
+
+# ---- aggregation with a feature vector per edge (csrc/capi_spmm_edge.hip).  The two entry points return their status code; the wrappers
+# ---- are not bracketed by KernelTimer
+
+EDGE_OPS = {"mul": 0, "add": 1, "add_relu": 2, "copy": 3, "gate": 4}   # `op` of voltrix_spmm_edge_csr; grad_efeat takes the first four
+
+
+def launch_spmm_edge(indptr, indices, order, num_rows: int, feat, efeat, self_rows, op: str, output, stream, num_entries=None) -> None:
+    """``output[r] = sum_{e in row r} m(feat[indices[e]], efeat[order[e] if order is given else e])`` (voltrix/spmm_edge_kernels.hpp):
+    device int32 CSR, ``order`` int32 [nnz] or None, fp32 / fp16 / bf16 ``efeat`` [nnz, F] whose rows are a multiple of 16 bytes, ``feat``
+    [*, F] of the same type or fp32 (None with ``"copy"``), ``self_rows`` [num_rows, F] of ``efeat``'s type with ``"gate"`` (else None),
+    fp32 ``output`` [num_rows, F]; ``num_entries``: ``indices.numel()`` unless given (a pattern without entries, whose ``indices`` and
+    ``efeat`` are stand-ins); see include/voltrix_capi.h."""
+    import torch
+
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    num_entries = indices.numel() if num_entries is None else num_entries
+    assert order is None or (order.dtype == torch.int32 and order.is_contiguous() and order.numel() == num_entries)
+    assert efeat.dim() == 2 and efeat.is_contiguous() and output.is_contiguous() and output.dtype == torch.float32
+    assert output.shape == (num_rows, efeat.shape[1])
+    assert feat is None or (feat.dim() == 2 and feat.is_contiguous() and feat.shape[1] == efeat.shape[1])
+    assert self_rows is None or (self_rows.is_contiguous() and self_rows.shape == output.shape and self_rows.dtype == efeat.dtype)
+    check(lib().voltrix_spmm_edge_csr(indptr.data_ptr(), indices.data_ptr(), _opt(order), num_rows, num_entries, efeat.shape[1],
+                                      _opt(feat), 0 if feat is None else _dtype_code(feat.dtype), efeat.data_ptr(),
+                                      _dtype_code(efeat.dtype), _opt(self_rows), EDGE_OPS[op], output.data_ptr(), stream),
+          "voltrix_spmm_edge_csr")
+
+
+def launch_spmm_edge_grad_efeat(indptr, indices, num_rows: int, grad_out, feat, efeat, dtype, op: str, output, stream) -> None:
+    """``output[e] = d m(feat[indices[e]], efeat[e]) / d efeat * grad_out[row_e]``: fp32 ``grad_out`` [num_rows, F], ``feat`` [*, F] and
+    ``efeat`` [nnz, F] of ``dtype`` (None where the op does not read them: ``feat`` for add / copy, ``efeat`` for all but add_relu), fp32
+    ``output`` [nnz, F]; see include/voltrix_capi.h."""
+    import torch
+
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    assert grad_out.dim() == 2 and grad_out.dtype == torch.float32 and grad_out.is_contiguous() and grad_out.shape[0] == num_rows
+    assert output.dtype == torch.float32 and output.is_contiguous() and output.shape == (indices.numel(), grad_out.shape[1])
+    for t in (feat, efeat):
+        assert t is None or (t.dim() == 2 and t.is_contiguous() and t.dtype == dtype and t.shape[1] == grad_out.shape[1])
+    check(lib().voltrix_spmm_edge_grad_efeat_csr(indptr.data_ptr(), indices.data_ptr(), num_rows, indices.numel(), grad_out.shape[1],
+                                                 grad_out.data_ptr(), _opt(feat), _opt(efeat), _dtype_code(dtype), EDGE_OPS[op],
+                                                 output.data_ptr(), stream),
+          "voltrix_spmm_edge_grad_efeat_csr")
 
 
 SAMPLE_ALL, SAMPLE_MAX_FANOUT = -1, 64      # `fanout` of voltrix_launch_sample_neighbors: every entry of every row; the largest fan-out
