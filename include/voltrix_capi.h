@@ -832,6 +832,59 @@ int voltrix_spmm_edge_csr(void* indptr, void* indices, void* order, int num_rows
 int voltrix_spmm_edge_grad_efeat_csr(void* indptr, void* indices, int num_rows, int64_t num_entries, int embedding_dim,
                                      void* grad_out, void* feat, void* efeat, int dtype, int op, void* output, void* stream);
 
+/* Relational (R-GCN) aggregation over TYPED edges on a DEVICE CSR, with basis decomposition (spmm_rel_kernels.hpp):
+ *   output[i, b, f] = sum over the entries e of row i of c(e, b) * input[indices[e], f],   c(e, b) = w_e * coef[etype[e], b]
+ * num_entries = the pattern's entry count nnz; etype = device int32[nnz] in CSR entry order, 0 <= etype < num_types; weight = device
+ * float[nnz] or NULL (w_e = 1: c(e, b) is coef itself); input = device [*, embedding_dim] of dtype (0 fp32 / 1 fp16 / 2 bfloat16, read
+ * as stored); coef = device float[num_types, B_pad] with B_pad = num_bases rounded up to a multiple of 4 (rows of whole 16-byte pieces;
+ * the padding is read and ignored); output = device float[num_rows, num_bases, embedding_dim], every element written, a row without
+ * entries 0.  LIMITS: 1 <= num_types <= 65 536, 0 <= num_bases <= 1 024.  fp32 throughout, sums in CSR order per row: |output - ref|
+ * <= (k + 2) 2^-23 sum |terms| for the k entries of a row (c(e, b) rounds once, a term once more).  NaN and inf propagate as the
+ * arithmetic does.  One launch: a row per lane group (a hub row serialises its wave, as in voltrix_launch_spmm_csr_heads), 16 bytes of
+ * the gathered row per lane and entry, tiles of 8 bases (4 where num_bases <= 4) in registers and over grid.z beyond -- the gathered
+ * row is read again per tile --, coef by plain loads, no LDS, no workspace, no float atomics, no host synchronisation, the same bits on
+ * every call; element offsets are 64-bit (num_rows * num_bases * embedding_dim may pass 2^31).
+ * RETURNS the status code (no return_code slot).  VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: negative
+ * sizes, num_entries > INT_MAX, num_types or num_bases outside the limits, an unknown dtype, embedding_dim not a multiple of 16 bytes
+ * of dtype (8 for 16-bit, 4 for fp32); then VOLTRIX_OK without a launch for num_rows == 0, embedding_dim == 0 or num_bases == 0; then
+ * VOLTRIX_ERR_BAD_SHAPE for a null indptr / indices / etype / input / coef / output or a misaligned pointer.  On a pattern without
+ * entries output is zero-filled and indices, etype, weight, input and coef are not read (they must still be valid pointers).  Nothing
+ * is checked on the device.  Alignment: indptr, indices, etype, weight 4 bytes; input, coef, output 16 bytes.  No reference counterpart. */
+int voltrix_spmm_rel_csr(void* indptr, void* indices, void* etype, void* weight, int num_rows, int64_t num_entries, int embedding_dim,
+                         int num_types, int num_bases, void* input, int dtype, void* coef, void* output, void* stream);
+
+/* The gradient of voltrix_spmm_rel_csr for its gathered operand, on the TRANSPOSED CSR (t_indptr has num_cols + 1 elements):
+ *   output[c, f] = sum over the entries e of row c of the transpose, over b, of c(id_e, b) * grad_out[t_indices[e], b, f]
+ *   id_e = order ? order[e] : e,   c(id, b) = w_id * coef[etype[id], b]
+ * order = device int32[nnz] or NULL: the entry of the CSR that entry e of the transpose is (t_order); etype, weight (or NULL) and coef
+ * as in voltrix_spmm_rel_csr, indexed by CSR entry; grad_out = device float[*, num_bases, embedding_dim]; output = device
+ * float[num_cols, embedding_dim], every element written, a column without entries 0.  A gather: fp32 additions in a fixed order (the
+ * transposed CSR's entries in batches of 4; inside a batch tiles of 4 bases, inside a tile entry by entry and basis by basis):
+ * |output - ref| <= (k num_bases + 2) 2^-23 sum |terms| for the k entries of a column.  One launch, a column per lane group and 4
+ * features per lane, no workspace, no float atomics, the same bits on every call, 64-bit element offsets.
+ * RETURNS the status code.  VOLTRIX_ERR_BAD_SHAPE as for voltrix_spmm_rel_csr with embedding_dim a multiple of 4 and grad_out in the
+ * place of input; VOLTRIX_OK without a launch for num_cols == 0, embedding_dim == 0 or num_bases == 0 (the caller zero-fills where
+ * num_bases == 0).  Alignment: t_indptr, t_indices, order, etype, weight 4 bytes; grad_out, coef, output 16 bytes. */
+int voltrix_spmm_rel_contract_csr(void* t_indptr, void* t_indices, void* order, void* etype, void* weight, int num_cols,
+                                  int64_t num_entries, int embedding_dim, int num_types, int num_bases, void* grad_out, void* coef,
+                                  void* output, void* stream);
+
+/* The dots behind the gradient of voltrix_spmm_rel_csr for coef, row-parallel on the same CSR:
+ *   output[e, b] = w_e * <grad_out[row_e, b, :], feat[indices[e], :]>     (b < num_bases;  0 for num_bases <= b < B_pad)
+ * grad_out = device float[num_rows, num_bases, embedding_dim]; feat = device [*, embedding_dim] of dtype; weight = device float[nnz] or
+ * NULL; output = device float[num_entries, B_pad], every element written.  The gradient is the sum of output's rows per type:
+ * voltrix_launch_spmm_csr_rows on a table of the entries sorted by type (in chunks, then per type; voltrix/spmm_rel.py).  A dot of F
+ * terms in fp32: |output - ref| <= (F + 1) 2^-23 |w_e| sum_f |g x|.  One launch, a row per lane group, embedding_dim beyond one slab
+ * of 64 pieces walked inside the kernel, a butterfly of shuffles per dot, 16-byte stores, no atomics, the same bits on every call,
+ * 64-bit element offsets.
+ * RETURNS the status code.  VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: negative sizes, num_entries > INT_MAX, num_bases
+ * > 1 024, an unknown dtype, embedding_dim not a multiple of 16 bytes of dtype; then VOLTRIX_OK without a launch for num_rows == 0,
+ * embedding_dim == 0, num_bases == 0 or num_entries == 0 (the caller zero-fills where embedding_dim == 0); then VOLTRIX_ERR_BAD_SHAPE
+ * for a null indptr / indices / grad_out / feat / output or a misaligned pointer.  Alignment: indptr, indices, weight 4 bytes; grad_out,
+ * feat, output 16 bytes. */
+int voltrix_spmm_rel_dots_csr(void* indptr, void* indices, void* weight, int num_rows, int64_t num_entries, int embedding_dim,
+                              int num_bases, void* grad_out, void* feat, int dtype, void* output, void* stream);
+
 /* Neighbour sampling on a device int32 CSR and the relabelling of a sampled block (voltrix/neighbor_sample_kernels.hpp): what produces
  * the rectangular [num_dst, num_src] patterns the CSR operators above take (GraphSAGE-style mini-batches).  No reference counterpart.
  * THE SAMPLING RULE.  For a seed row r (its global row id), fan-out k = fanout, degree d = indptr[r + 1] - indptr[r]:

@@ -531,6 +531,66 @@ class SpMMEdge(_PatternOp):
         return _SpMMEdgeFunction.apply(feat, efeat, self, op)
 
 
+class _SpMMRelFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, coef, weight, op):
+        from .spmm_rel import spmm_rel
+
+        ctx.op, ctx.weight = op, weight
+        ctx.save_for_backward(feat, coef)           # coef: None for the identity; weight is a constant of the graph, not saved here
+        return spmm_rel(op.indptr, op.indices, op.etype, feat, op.num_types if coef is None else coef, op.num_rows, weight)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .spmm_rel import grad_coef, grad_feat
+
+        op = ctx.op
+        feat, coef = ctx.saved_tensors
+        d_feat = d_coef = None
+        if ctx.needs_input_grad[0]:
+            d_feat = grad_feat(op.t_indptr, op.t_indices, op.t_order, op.etype, grad_out, op.num_types if coef is None else coef,
+                               op.num_cols, ctx.weight).to(feat.dtype)
+        if coef is not None and ctx.needs_input_grad[1]:
+            d_coef = grad_coef(op.indptr, op.indices, op.etype, op.type_index, grad_out, feat, ctx.weight).to(coef.dtype)
+        return d_feat, d_coef, None, None
+
+
+class SpMMRel(_PatternOp):
+    """``out[i, b] = sum over the entries e of row i of weight[e] * coef[etype[e], b] * feat[col_e]`` on a CSR pattern [num_rows,
+    num_cols] whose entries carry a type: R-GCN's aggregation with basis decomposition (``voltrix.spmm_rel``), differentiable in
+    ``feat`` [num_cols, F] and ``coef`` [num_types, B]: ``SpMMRel(indptr, indices, n, etype=etype, num_types=R)(feat, coef, weight)`` ->
+    float32 [num_rows, B, F]; ``coef=None`` is the identity ([num_rows, R, F], no gradient for it).  ``etype``: int32 [nnz] in CSR
+    entry order (``etype[block.entries]`` with ``SpMMRel(block.pattern, ...)``).  ``weight``: fp32 [nnz] or None, the degree normaliser
+    (``voltrix.spmm_rel.type_norm``); it gets no gradient: a ``weight`` that requires grad is a ``ValueError``.  Built once per pattern
+    like the attention operators, or on a ``CsrPattern`` shared with them; its ``TypeIndex`` (which refuses a type outside
+    ``[0, num_types)``) is built once, in the constructor.  Only the gradients ``needs_input_grad`` asks for are computed: ``feat``'s by
+    a gather on the transposed CSR, ``coef``'s by one row-parallel launch and two fixed-order row sums.  ``feat`` and ``coef`` alone are
+    saved.  No index op, no float atomics, the same bits on every call; the gradients come back in the operands' dtypes."""
+
+    def __init__(self, indptr, indices: torch.Tensor = None, num_rows: int = None, num_cols: int = None, transposed=None, *,
+                 etype: torch.Tensor, num_types: int):
+        from .spmm_rel import TypeIndex
+
+        super().__init__(indptr, indices, num_rows, num_cols, transposed)
+        if etype.dim() != 1 or etype.numel() != self.num_edges:
+            raise ValueError(f"SpMMRel: etype must be [nnz] = [{self.num_edges}], got {tuple(etype.shape)}")
+        self.num_types = int(num_types)
+        self.etype = etype.to(torch.int32).contiguous().cuda()
+        self.type_index = TypeIndex(self.etype, self.num_types)
+
+    def __call__(self, feat: torch.Tensor, coef: torch.Tensor = None, weight: torch.Tensor = None) -> torch.Tensor:
+        from .spmm_rel import _check
+
+        if weight is not None and weight.requires_grad:
+            raise ValueError("SpMMRel: weight is the degree normaliser and gets no gradient; a learnt scalar per edge is "
+                             "voltrix.spmm_heads / attn_aggregate")
+        _check("SpMMRel", self.pattern.indices, self.etype, coef, weight, feat=feat)
+        if coef is not None and coef.shape[0] != self.num_types:
+            raise ValueError(f"SpMMRel: coef {tuple(coef.shape)} has not {self.num_types} rows")
+        assert feat.shape[0] == self.num_cols, (tuple(feat.shape), self.num_cols)
+        return _SpMMRelFunction.apply(feat, coef, weight, self)
+
+
 class SpMM:
     """``C = A @ B`` with a gradient for ``B``.  ``A``: binary CSR [num_rows, num_cols] (``num_cols`` defaults to
     ``num_rows``), or, with ``values`` (round 6), the weighted matrix ``csr(values)``.  Builds two reference-format handles on the current device (A and A^T); both go through

@@ -108,6 +108,9 @@ SIGNATURES = {
     "voltrix_launch_spmm_csr_reduce_backward": (None, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _RC_P]),
     "voltrix_spmm_edge_csr": (_I, [_P, _P, _P, _I, _L, _I, _P, _I, _P, _I, _P, _I, _P, _P]),
     "voltrix_spmm_edge_grad_efeat_csr": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "voltrix_spmm_rel_csr": (_I, [_P, _P, _P, _P, _I, _L, _I, _I, _I, _P, _I, _P, _P, _P]),
+    "voltrix_spmm_rel_contract_csr": (_I, [_P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _P, _P, _P, _P]),
+    "voltrix_spmm_rel_dots_csr": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _P]),
     "voltrix_launch_sample_neighbors": (None, [_P, _P, _I, _P, _I, _P, _L, _I, _I, _U64, _U64, _P, _P, _P, _RC_P]),
     "voltrix_launch_block_mark": (None, [_P, _L, _I, _P, _P, _RC_P]),
     "voltrix_launch_block_mark_seeds": (None, [_P, _I, _I, _P, _P, _RC_P]),
@@ -987,6 +990,77 @@ def launch_spmm_edge_grad_efeat(indptr, indices, num_rows: int, grad_out, feat, 
                                                  grad_out.data_ptr(), _opt(feat), _opt(efeat), _dtype_code(dtype), EDGE_OPS[op],
                                                  output.data_ptr(), stream),
           "voltrix_spmm_edge_grad_efeat_csr")
+
+
+# ---- relational aggregation over typed edges (csrc/capi_spmm_rel.hip).  The three entry points return their status code; the wrappers
+# ---- are not bracketed by KernelTimer
+
+REL_BASIS_TILE, REL_MAX_TYPES, REL_MAX_BASES = 8, 65536, 1024    # kRelBasisTile, kRelMaxTypes, kRelMaxBases of spmm_rel_kernels.hpp
+
+
+def _rel_tables(etype, weight, coef, num_entries, num_bases):
+    import torch
+
+    assert etype.dtype == torch.int32 and etype.is_contiguous() and etype.numel() == num_entries
+    assert weight is None or (weight.dtype == torch.float32 and weight.is_contiguous() and weight.numel() == num_entries)
+    assert coef.dim() == 2 and coef.dtype == torch.float32 and coef.is_contiguous() and coef.shape[1] == (num_bases + 3) // 4 * 4
+
+
+def launch_spmm_rel(indptr, indices, etype, weight, num_rows: int, feat, coef, num_bases: int, output, stream, num_entries=None) -> None:
+    """``output[i, b] = sum_{e in row i} weight[e] * coef[etype[e], b] * feat[indices[e]]`` (voltrix/spmm_rel_kernels.hpp): device int32
+    CSR and ``etype`` [nnz], fp32 ``weight`` [nnz] or None, fp32 / fp16 / bf16 ``feat`` [*, F] whose rows are a multiple of 16 bytes, fp32
+    ``coef`` [R, B_pad] (``num_bases`` rounded up to 4), fp32 ``output`` [num_rows, num_bases, F]; ``num_entries``: ``indices.numel()``
+    unless given (a pattern without entries, whose ``indices`` and ``etype`` are stand-ins); see include/voltrix_capi.h."""
+    import torch
+
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    num_entries = indices.numel() if num_entries is None else num_entries
+    if num_entries:
+        _rel_tables(etype, weight, coef, num_entries, num_bases)
+    assert feat.dim() == 2 and feat.is_contiguous() and output.is_contiguous() and output.dtype == torch.float32
+    assert output.shape == (num_rows, num_bases, feat.shape[1])
+    check(lib().voltrix_spmm_rel_csr(indptr.data_ptr(), indices.data_ptr(), etype.data_ptr(), _opt(weight), num_rows, num_entries,
+                                     feat.shape[1], coef.shape[0], num_bases, feat.data_ptr(), _dtype_code(feat.dtype), coef.data_ptr(),
+                                     output.data_ptr(), stream),
+          "voltrix_spmm_rel_csr")
+
+
+def launch_spmm_rel_contract(t_indptr, t_indices, order, etype, weight, num_cols: int, grad_out, coef, output, stream) -> None:
+    """``output[c] = sum_{e in row c of the transposed CSR} sum_b weight[id] * coef[etype[id], b] * grad_out[t_indices[e], b]`` with
+    ``id = order[e]`` (``order`` None: ``e``): fp32 ``grad_out`` [*, B, F] with F a multiple of 4, fp32 ``output`` [num_cols, F]; see
+    include/voltrix_capi.h."""
+    import torch
+
+    assert t_indptr.dtype == torch.int32 and t_indices.dtype == torch.int32 and t_indptr.numel() == num_cols + 1
+    assert t_indptr.is_contiguous() and t_indices.is_contiguous()
+    nnz = t_indices.numel()
+    assert order is None or (order.dtype == torch.int32 and order.is_contiguous() and order.numel() == nnz)
+    assert grad_out.dim() == 3 and grad_out.dtype == torch.float32 and grad_out.is_contiguous()
+    _rel_tables(etype, weight, coef, nnz, grad_out.shape[1])
+    assert output.dtype == torch.float32 and output.is_contiguous() and output.shape == (num_cols, grad_out.shape[2])
+    check(lib().voltrix_spmm_rel_contract_csr(t_indptr.data_ptr(), t_indices.data_ptr(), _opt(order), etype.data_ptr(), _opt(weight),
+                                              num_cols, nnz, grad_out.shape[2], coef.shape[0], grad_out.shape[1], grad_out.data_ptr(),
+                                              coef.data_ptr(), output.data_ptr(), stream),
+          "voltrix_spmm_rel_contract_csr")
+
+
+def launch_spmm_rel_dots(indptr, indices, weight, num_rows: int, grad_out, feat, output, stream) -> None:
+    """``output[e, b] = weight[e] * <grad_out[row_e, b], feat[indices[e]]>``: fp32 ``grad_out`` [num_rows, B, F], ``feat`` [*, F] whose
+    rows are a multiple of 16 bytes, fp32 ``output`` [nnz, B_pad], the padding written as 0; see include/voltrix_capi.h."""
+    import torch
+
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    nnz = indices.numel()
+    assert weight is None or (weight.dtype == torch.float32 and weight.is_contiguous() and weight.numel() == nnz)
+    assert grad_out.dim() == 3 and grad_out.dtype == torch.float32 and grad_out.is_contiguous() and grad_out.shape[0] == num_rows
+    assert feat.dim() == 2 and feat.is_contiguous() and feat.shape[1] == grad_out.shape[2]
+    num_bases = grad_out.shape[1]
+    assert output.dtype == torch.float32 and output.is_contiguous() and output.shape == (nnz, (num_bases + 3) // 4 * 4)
+    check(lib().voltrix_spmm_rel_dots_csr(indptr.data_ptr(), indices.data_ptr(), _opt(weight), num_rows, nnz, feat.shape[1], num_bases,
+                                          grad_out.data_ptr(), feat.data_ptr(), _dtype_code(feat.dtype), output.data_ptr(), stream),
+          "voltrix_spmm_rel_dots_csr")
 
 
 SAMPLE_ALL, SAMPLE_MAX_FANOUT = -1, 64      # `fanout` of voltrix_launch_sample_neighbors: every entry of every row; the largest fan-out
