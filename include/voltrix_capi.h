@@ -885,6 +885,43 @@ int voltrix_spmm_rel_contract_csr(void* t_indptr, void* t_indices, void* order, 
 int voltrix_spmm_rel_dots_csr(void* indptr, void* indices, void* weight, int num_rows, int64_t num_entries, int embedding_dim,
                               int num_bases, void* grad_out, void* feat, int dtype, void* output, void* stream);
 
+/* FP8 feature rows (OCP e4m3fn = torch.float8_e4m3fn: bias 7, subnormals m 2^-9, largest finite 448, 0x7f / 0xff NaN, no infinities;
+ * NOT the MI300 e4m3fnuz encoding), spmm_fp8_kernels.hpp.  The quantiser, row-major, one launch that reads input once:
+ *   output[i, f] = rne_e4m3(clamp(fp32(input[i, f]) * inv_scale[f], -448, 448))   for f < embedding_dim;  0x00 for the padding up to F16
+ * F16 = embedding_dim rounded up to 16.  input = device [num_rows, embedding_dim] of dtype (0 fp32 / 1 fp16 / 2 bfloat16, read as
+ * stored) whose rows are input_ld ELEMENTS apart (input_ld >= embedding_dim: a column slice of a wider matrix goes in as it is; rows on
+ * 16-byte boundaries are read 16 bytes at a time, others element by element); inv_scale = device float[F16]; output = device
+ * uint8[num_rows, F16] whose rows are output_ld BYTES apart (>= F16, a multiple of 16).  One fp32 multiply, then the clamp, then one
+ * rounding to nearest even with e4m3 subnormals: torch's (x.float() * inv_scale).clamp(-448, 448).to(torch.float8_e4m3fn) bit for
+ * bit.  +-inf saturates to +-448, a NaN gives an e4m3 NaN code, -0 keeps its sign.  A grid-stride loop over the rows, 64-bit offsets,
+ * no LDS, no atomics, no host synchronisation.
+ * RETURNS the status code (no return_code slot).  VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: negative
+ * sizes, an unknown dtype, input_ld < embedding_dim, output_ld < F16 or not a multiple of 16; then VOLTRIX_OK without a launch for
+ * num_rows == 0 or embedding_dim == 0; then VOLTRIX_ERR_BAD_SHAPE for a null or misaligned pointer.  Alignment: input, inv_scale,
+ * output 16 bytes.  No reference counterpart. */
+int voltrix_quantize_fp8_rows(void* input, int dtype, int num_rows, int embedding_dim, int64_t input_ld, void* inv_scale, void* output,
+                              int64_t output_ld, void* stream);
+
+/* Aggregation of FP8 feature rows on a DEVICE CSR:
+ *   output[i, f] = scale[f] * sum over the entries e of row i of v_e * dec(input[indices[e], f])        v_e = values ? values[e] : 1
+ * input = device uint8[*, embedding_dim16] of e4m3fn codes (embedding_dim16 a multiple of 16; padding columns hold 0x00); scale =
+ * device float[embedding_dim16], the dequantisation multiplier per COLUMN (a per-row scale would be a second gathered line per entry);
+ * values = device float[nnz] in CSR order or NULL; output = device [num_rows, embedding_dim16] of out_dtype (0 fp32 / 1 fp16 / 2
+ * bfloat16; a 16-bit output is the fp32 result rounded to nearest even), every element written, a row without entries 0; num_entries =
+ * the pattern's entry count nnz; xcd_ranges as in voltrix_launch_spmm_csr_rows.  Decoded values are exact in fp32; the sum is fp32 in
+ * CSR entry order (with values: one fused multiply-add per element) and starts from -0, so a lone -0 keeps its sign; then one multiply
+ * by scale[f]: |output - ref| <= (k + 2) 2^-23 |scale[f]| sum_e |v_e dec_e| for the k entries of a row; integer-valued codes and
+ * values with power-of-two scales give equality.  NaN propagates as the arithmetic does.  One launch, a row per lane group (a hub row
+ * serialises its wave), 16 bytes = 16 features of the gathered row per lane and entry, no LDS, no workspace, no atomics, no host
+ * synchronisation, the same bits on every call; element offsets are 64-bit (rows * embedding_dim16 may pass 2^31).
+ * RETURNS the status code.  VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: negative sizes, num_entries > INT_MAX,
+ * embedding_dim16 not a multiple of 16, an unknown out_dtype; then VOLTRIX_OK without a launch for num_rows == 0 or embedding_dim16
+ * == 0; then VOLTRIX_ERR_BAD_SHAPE for a null indptr / indices / input / scale / output or a misaligned pointer.  On a pattern without
+ * entries indices, values and input are not read (they must still be valid pointers).  Nothing is checked on the device.  Alignment:
+ * indptr, indices, values 4 bytes; input, scale, output 16 bytes.  No reference counterpart. */
+int voltrix_spmm_fp8_csr(void* indptr, void* indices, void* values, int num_rows, int embedding_dim16, void* input, void* scale,
+                         void* output, int out_dtype, int xcd_ranges, int64_t num_entries, void* stream);
+
 /* Neighbour sampling on a device int32 CSR and the relabelling of a sampled block (voltrix/neighbor_sample_kernels.hpp): what produces
  * the rectangular [num_dst, num_src] patterns the CSR operators above take (GraphSAGE-style mini-batches).  No reference counterpart.
  * THE SAMPLING RULE.  For a seed row r (its global row id), fan-out k = fanout, degree d = indptr[r + 1] - indptr[r]:

@@ -591,6 +591,60 @@ class SpMMRel(_PatternOp):
         return _SpMMRelFunction.apply(feat, coef, weight, self)
 
 
+class _SpMMFp8Function(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, values, op, scale, out_dtype):
+        from .fp8 import quantize_fp8, spmm_fp8
+
+        ctx.op, ctx.values, ctx.in_dtype = op, values, feat.dtype       # values: a constant of the graph; feat is saved nowhere
+        return spmm_fp8(op.indptr, op.indices, quantize_fp8(feat, scale), op.num_rows, values, out_dtype)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import capi
+        from .jit_kernels.spmm import _raw_stream
+        from .utils import padded_last_dim, piece_width
+
+        op = ctx.op
+        dim = grad_out.shape[1]
+        width = piece_width(max(dim, 1), torch.float32)
+        out = torch.empty((op.num_cols, width), dtype=torch.float32, device=grad_out.device)
+        if op.num_edges == 0 or dim == 0:
+            out.zero_()
+        elif op.num_cols > 0:
+            values = None if ctx.values is None else ctx.values.float()[op.t_order].contiguous()
+            capi.launch_spmm_csr_rows(op.t_indptr, op.t_indices, op.num_cols, padded_last_dim(grad_out.float(), width), out,
+                                      _raw_stream(out.device), 1, values)
+        return out[:, :dim].to(ctx.in_dtype), None, None, None, None
+
+
+class SpMMFp8(_PatternOp):
+    """``out[r] = sum over the entries e of row r of values[e] * q(feat)[col_e]`` on a CSR pattern [num_rows, num_cols], where ``q`` is
+    the FP8 (e4m3fn) quantisation of ``voltrix.quantize_fp8``: ``SpMMFp8(indptr, indices, n)(feat, values=None, scale="column")`` ->
+    ``out_dtype`` (float32) [num_rows, F] -- aggregation at half the gathered bytes of a 16-bit row (``voltrix.spmm_fp8``; its docstring
+    has the error bounds).  Built once per pattern like the attention operators, or ``SpMMFp8(pattern)`` on a ``CsrPattern`` shared
+    with them (``block.pattern`` of a sampled block).  The forward quantises ``feat`` and aggregates; ``feat`` is saved nowhere.  The
+    backward is STRAIGHT-THROUGH: ``d_feat = csr(values)^T grad_out``, the exact fp32 CSR row-gather sum on the pattern's transpose
+    (``values[t_order]`` where values are given), as if the quantiser were the identity; it comes back in ``feat``'s dtype.  ``values``
+    (fp32 [nnz], e.g. a degree normaliser) gets no gradient: one that requires grad is a ``ValueError``.  An ``Fp8Rows`` in place of
+    ``feat`` is the inference case: nothing is quantised again and no gradient flows."""
+
+    def __call__(self, feat, values: torch.Tensor = None, scale="column", out_dtype=torch.float32) -> torch.Tensor:
+        from .fp8 import Fp8Rows, _check_quantize, spmm_fp8
+
+        if values is not None and values.requires_grad:
+            raise ValueError("SpMMFp8: values get no gradient; learnt edge values are voltrix.autograd.SpMM(values=) / SpMMHeads")
+        if isinstance(feat, Fp8Rows):
+            return spmm_fp8(self.indptr, self.indices, feat, self.num_rows, values, out_dtype)
+        _check_quantize("SpMMFp8", feat, scale)
+        if values is not None and values.numel() != self.num_edges:
+            raise ValueError(f"SpMMFp8: values must be [nnz] = [{self.num_edges}], got {tuple(values.shape)}")
+        if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError(f"SpMMFp8: out_dtype must be torch.float32, float16 or bfloat16, got {out_dtype}")
+        assert feat.shape[0] == self.num_cols, (tuple(feat.shape), self.num_cols)
+        return _SpMMFp8Function.apply(feat, values, self, scale, out_dtype)
+
+
 class SpMM:
     """``C = A @ B`` with a gradient for ``B``.  ``A``: binary CSR [num_rows, num_cols] (``num_cols`` defaults to
     ``num_rows``), or, with ``values`` (round 6), the weighted matrix ``csr(values)``.  Builds two reference-format handles on the current device (A and A^T); both go through

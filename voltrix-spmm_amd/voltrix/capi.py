@@ -111,6 +111,8 @@ SIGNATURES = {
     "voltrix_spmm_rel_csr": (_I, [_P, _P, _P, _P, _I, _L, _I, _I, _I, _P, _I, _P, _P, _P]),
     "voltrix_spmm_rel_contract_csr": (_I, [_P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _P, _P, _P, _P]),
     "voltrix_spmm_rel_dots_csr": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _P]),
+    "voltrix_quantize_fp8_rows": (_I, [_P, _I, _I, _I, _L, _P, _P, _L, _P]),
+    "voltrix_spmm_fp8_csr": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _L, _P]),
     "voltrix_launch_sample_neighbors": (None, [_P, _P, _I, _P, _I, _P, _L, _I, _I, _U64, _U64, _P, _P, _P, _RC_P]),
     "voltrix_launch_block_mark": (None, [_P, _L, _I, _P, _P, _RC_P]),
     "voltrix_launch_block_mark_seeds": (None, [_P, _I, _I, _P, _P, _RC_P]),
@@ -1063,7 +1065,47 @@ def launch_spmm_rel_dots(indptr, indices, weight, num_rows: int, grad_out, feat,
           "voltrix_spmm_rel_dots_csr")
 
 
-SAMPLE_ALL, SAMPLE_MAX_FANOUT = -1, 64      # `fanout` of voltrix_launch_sample_neighbors: every entry of every row; the largest fan-out
+# ---- FP8 (e4m3fn) feature rows: the quantiser and the aggregation (csrc/capi_spmm_fp8.hip).  The two entry points return their status
+# ---- code; the wrappers are not bracketed by KernelTimer
+
+
+def launch_quantize_fp8_rows(feat, inv_scale, output, stream) -> None:
+    """``output[i, f] = e4m3(clamp(feat[i, f] * inv_scale[f], -448, 448))`` (voltrix/spmm_fp8_kernels.hpp): fp32 / fp16 / bf16 ``feat``
+    [n, F] with unit column stride and any row stride >= F, fp32 ``inv_scale`` [F16], ``output`` [n, F16] of ``torch.float8_e4m3fn``
+    or uint8, F16 = F rounded up to 16, the padding written as 0x00; see include/voltrix_capi.h."""
+    import torch
+
+    assert feat.dim() == 2 and (feat.shape[1] <= 1 or feat.stride(1) == 1) and (feat.shape[0] <= 1 or feat.stride(0) >= feat.shape[1])
+    width = (feat.shape[1] + 15) // 16 * 16
+    assert inv_scale.dtype == torch.float32 and inv_scale.is_contiguous() and inv_scale.numel() == width
+    assert output.element_size() == 1 and output.is_contiguous() and output.shape == (feat.shape[0], width)
+    check(lib().voltrix_quantize_fp8_rows(feat.data_ptr(), _dtype_code(feat.dtype), feat.shape[0], feat.shape[1],
+                                          feat.stride(0) if feat.shape[0] > 1 else max(feat.shape[1], 1), inv_scale.data_ptr(),
+                                          output.data_ptr(), width, stream),
+          "voltrix_quantize_fp8_rows")
+
+
+def launch_spmm_fp8(indptr, indices, values, num_rows: int, data, scale, output, stream, xcd_ranges: int = 1, num_entries=None) -> None:
+    """``output[i] = scale * sum_{e in row i} values[e] * dec(data[indices[e]])`` (voltrix/spmm_fp8_kernels.hpp): device int32 CSR, fp32
+    ``values`` [nnz] or None, ``data`` [*, F16] of e4m3fn codes with F16 a multiple of 16, fp32 ``scale`` [F16], fp32 / fp16 / bf16
+    ``output`` [num_rows, F16]; ``num_entries``: ``indices.numel()`` unless given (a pattern without entries, whose ``indices`` is a
+    stand-in); see include/voltrix_capi.h."""
+    import torch
+
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    num_entries = indices.numel() if num_entries is None else num_entries
+    assert values is None or (values.dtype == torch.float32 and values.is_contiguous() and values.numel() == num_entries)
+    assert data.dim() == 2 and data.element_size() == 1 and data.is_contiguous() and data.shape[1] % 16 == 0
+    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == data.shape[1]
+    assert output.is_contiguous() and output.shape == (num_rows, data.shape[1])
+    check(lib().voltrix_spmm_fp8_csr(indptr.data_ptr(), indices.data_ptr(), _opt(values), num_rows, data.shape[1], data.data_ptr(),
+                                     scale.data_ptr(), output.data_ptr(), _dtype_code(output.dtype), int(xcd_ranges), num_entries,
+                                     stream),
+          "voltrix_spmm_fp8_csr")
+
+
+SAMPLE_ALL, SAMPLE_MAX_FANOUT = -1, 64     # `fanout` of voltrix_launch_sample_neighbors: every entry of every row; the largest fan-out
 
 
 def launch_sample_neighbors(indptr, indices, num_rows: int, seeds, s_indptr, num_sampled: int, fanout: int, replace: bool, seed: int,
