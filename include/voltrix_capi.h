@@ -922,6 +922,54 @@ int voltrix_quantize_fp8_rows(void* input, int dtype, int num_rows, int embeddin
 int voltrix_spmm_fp8_csr(void* indptr, void* indices, void* values, int num_rows, int embedding_dim16, void* input, void* scale,
                          void* output, int out_dtype, int xcd_ranges, int64_t num_entries, void* stream);
 
+/* Several aggregates of every row's neighbours from ONE gather of a DEVICE CSR (spmm_multi_kernels.hpp): per row r with d entries
+ * (duplicates count twice) and per element f, over x_e = input[indices[e], f] in CSR order:
+ *   sum   fp32 additions from 0 (the bits of voltrix_launch_spmm_csr_rows)       mean  sum / d (the bits of voltrix_launch_spmm_csr_reduce)
+ *   max, min   strict selection: the first entry wins ties, the first NaN wins and stays (the bits of voltrix_launch_spmm_csr_reduce);
+ *              argmax / argmin = the CSR ENTRY id of the winner
+ *   var   max(S2 / d - (S1 / d)^2, 0) from moments SHIFTED by the row's first entry: y_e = x_e - x_first, S1 = sum y_e, S2 = sum y_e^2;
+ *         |var - ref| <= (d + 4) 2^-23 (2 / d) sum_e (x_e - x_first)^2; one entry gives 0 exactly; a NaN or +-inf entry gives NaN
+ *   std   sqrt(var + eps)
+ * output = device float[num_rows, num_slots, embedding_dim]; slot_sum .. slot_std = the slot of each aggregate in a row of output, -1
+ * for one that is not stored; the stored ones fill the slots 0 .. num_slots - 1, each exactly once.  argmax / argmin = device
+ * int32[num_rows, embedding_dim] or NULL; one that is given needs its max / min stored.  input = device [*, embedding_dim] of dtype
+ * (0 fp32 / 1 fp16 / 2 bfloat16), read as it is; num_entries = the pattern's entry count nnz.  Every element of output and of the
+ * args is written; a row without entries gives 0 in every aggregate (std too) and -1 in the args.  An aggregate's bits do not depend
+ * on which others are stored.  One launch, a row per lane group (a hub row serialises its wave, as in voltrix_launch_spmm_csr_heads),
+ * 16 bytes of the gathered row per lane and entry, no LDS, no workspace, no atomics, no host synchronisation, the same bits on every
+ * call; element offsets are 64-bit (num_rows * num_slots * embedding_dim may pass 2^31).
+ * RETURNS the status code.  VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: negative sizes, num_entries > INT_MAX, an unknown
+ * dtype, num_slots outside 1 .. 6, a slot outside -1 .. num_slots - 1, two aggregates in one slot, a slot nobody fills, argmax / argmin
+ * without max / min, eps not finite or <= 0 when std is stored, embedding_dim not a multiple of 16 bytes (8 for 16-bit, 4 for fp32);
+ * then VOLTRIX_OK without a launch for num_rows == 0 or embedding_dim == 0; then VOLTRIX_ERR_BAD_SHAPE for a null indptr / indices /
+ * input / output or a misaligned pointer.  On a pattern without entries indices and input are not read (they must still be valid
+ * pointers).  Nothing is checked on the device.  Alignment: indptr, indices 4 bytes; input, output, argmax, argmin 16 bytes.  No
+ * reference counterpart. */
+int voltrix_spmm_multi_csr(void* indptr, void* indices, int num_rows, int64_t num_entries, int embedding_dim, void* input, int dtype,
+                           int slot_sum, int slot_mean, int slot_max, int slot_min, int slot_var, int slot_std, int num_slots,
+                           float eps, void* output, void* argmax, void* argmin, void* stream);
+
+/* The joint backward of voltrix_spmm_multi_csr for its input, a gather on the TRANSPOSED CSR (t_indptr / t_indices; t_order[e] = the
+ * entry of the CSR that entry e of the transpose is):
+ *   output[c, f] = sum over the entries e of column c, r = t_indices[e], id = t_order[e], of
+ *                  u[r, f] + w[r, f] (x[c, f] - mean[r, f]) + [argmax[r, f] == id] g_max[r, f] + [argmin[r, f] == id] g_min[r, f]
+ * in the transposed CSR's order, the terms of an entry in this order, the centred term one fused multiply-add.  The caller forms
+ * u = g_sum + g_mean / d and w = 2 g_var / d + g_std / (d std).  All operands are device float (the args int32) [*, embedding_dim];
+ * x = the forward's input as fp32 [num_cols, embedding_dim], read once per column; mean has rows of mean_ld floats (a slot of the
+ * forward's output).  u may be NULL; w, x and mean are NULL together; g_max with argmax and g_min with argmin are NULL in pairs; at
+ * least one group is given.  A g_max / g_min row is loaded only where a component matched.  output = device float[num_cols,
+ * embedding_dim], every row written, columns without entries zeros.  One launch, a column per lane group (a hub column serialises its
+ * wave), 4 features per lane, no atomics, the same bits on every call; element offsets are 64-bit.
+ * RETURNS the status code.  VOLTRIX_ERR_BAD_SHAPE, on the host and before any launch: negative sizes, num_entries > INT_MAX,
+ * embedding_dim not a multiple of 4, a group given in part or none at all, mean_ld < embedding_dim or not a multiple of 4 (with w);
+ * then VOLTRIX_OK without a launch for num_cols == 0 or embedding_dim == 0; then VOLTRIX_ERR_BAD_SHAPE for a null t_indptr / output,
+ * a misaligned pointer, or with num_entries > 0 a null t_indices, or a null t_order beside g_max / g_min.  Nothing is checked on the
+ * device; the args are only compared, never used as an index.  Alignment: t_indptr, t_indices, t_order 4 bytes; the rest 16 bytes.
+ * No reference counterpart. */
+int voltrix_spmm_multi_backward_csr(void* t_indptr, void* t_indices, void* t_order, int num_cols, int64_t num_entries, int embedding_dim,
+                                    void* x, void* u, void* w, void* mean, int64_t mean_ld, void* g_max, void* argmax, void* g_min,
+                                    void* argmin, void* output, void* stream);
+
 /* Neighbour sampling on a device int32 CSR and the relabelling of a sampled block (voltrix/neighbor_sample_kernels.hpp): what produces
  * the rectangular [num_dst, num_src] patterns the CSR operators above take (GraphSAGE-style mini-batches).  No reference counterpart.
  * THE SAMPLING RULE.  For a seed row r (its global row id), fan-out k = fanout, degree d = indptr[r + 1] - indptr[r]:

@@ -24,6 +24,7 @@ from .spmm_reduce import spmm_reduce
 from .spmm_edge import spmm_edge
 from .spmm_rel import spmm_rel
 from .fp8 import Fp8Rows, dequantize_fp8, quantize_fp8, spmm_fp8
+from .spmm_multi import spmm_multi
 from .dropout import apply_dropout_mask, dropout_mask
 from .sampling import Block, SamplingWeights, compact_block, sample_blocks, sample_neighbors, sampling_weights
 from .subgraph import Subgraph, induced_subgraph, random_walk, sample_subgraph_rw, subgraph_csr

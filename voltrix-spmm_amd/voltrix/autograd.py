@@ -488,6 +488,75 @@ class SpMMReduce(_PatternOp):
         return _SpMMReduceFunction.apply(feat, self)
 
 
+class _SpMMMultiFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, op):
+        from .spmm_multi import spmm_multi
+
+        ctx.op, ctx.in_dtype = op, feat.dtype
+        out, state = spmm_multi(op.indptr, op.indices, feat, op.num_rows, op.aggrs, op.eps, return_state=True)
+        # only what the requested aggregates need: the winners' entry ids for max / min; feat, mean and std for var / std; nothing
+        # for sum / mean alone
+        ctx.save_for_backward(*[t for t in (state.argmax, state.argmin, state.mean, state.std, feat if op.moments else None)
+                                if t is not None])
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .spmm_multi import spmm_multi_backward
+        from .spmm_reduce import row_degrees
+
+        op = ctx.op
+        saved = list(ctx.saved_tensors)
+        argmax = saved.pop(0) if "max" in op.aggrs else None
+        argmin = saved.pop(0) if "min" in op.aggrs else None
+        mean = saved.pop(0) if op.moments else None
+        std = saved.pop(0) if "std" in op.aggrs else None
+        feat = saved.pop(0) if op.moments else None
+        g = {name: grad_out[:, i].float() for i, name in enumerate(op.aggrs)}
+        shape = (op.num_rows,) + (1,) * (grad_out.dim() - 2)
+        deg = row_degrees(op.indptr).view(shape)
+        u = w = None                      # u = g_sum + g_mean / d,  w = 2 g_var / d + g_std / (d std)
+        if "mean" in g:
+            u = g["mean"] / deg
+        if "sum" in g:
+            u = g["sum"] if u is None else u + g["sum"]
+        if "var" in g:
+            w = 2.0 * g["var"] / deg
+        if "std" in g:
+            by_std = g["std"] / (deg * std)
+            w = by_std if w is None else w + by_std
+        grad = spmm_multi_backward(op.t_indptr, op.t_indices, op.t_order, op.num_cols, feat=feat, u=u, w=w, mean=mean,
+                                   g_max=g.get("max"), argmax=argmax, g_min=g.get("min"), argmin=argmin)
+        return grad.to(ctx.in_dtype), None
+
+
+class SpMMMulti(_PatternOp):
+    """``out[r, a] = aggrs[a] over the entries e of row r of feat[col_e]`` per element on a CSR pattern [num_rows, num_cols] (``num_cols``
+    defaults to ``num_rows``), differentiable in ``feat`` [num_cols, ...]: ``SpMMMulti(indptr, indices, n, aggrs=("mean", "max", "min",
+    "std"), eps=1e-5)(feat)`` -> float32 ``[n, len(aggrs), ...]`` -- the aggregators of a PNA layer from one gather
+    (``voltrix.spmm_multi``), or ``SpMMMulti(pattern, aggrs=...)`` on a ``CsrPattern`` shared with the other operators.  The backward is
+    one gather on the transposed CSR.  Saved is only what the requested aggregates need: the winners' entry ids for max / min (int32,
+    never ``feat``); ``feat``, ``mean`` and ``std`` for var / std; nothing for sum / mean alone.  The gradient of max / min goes to the
+    one winner of an element (the first in CSR order on a tie).  The gradient of var / std is ``w (x - mean)`` per entry with ``w = 2
+    g_var / d + g_std / (d std)``: a non-finite feature in a row makes it NaN for that row's columns (``std`` is NaN there).  A row
+    without entries passes nothing back.  No index op, no float atomics, the same bits on every call; ``out`` is float32 and the
+    gradient comes back in ``feat``'s dtype."""
+
+    def __init__(self, indptr, indices: torch.Tensor = None, num_rows: int = None, num_cols: int = None, transposed=None,
+                 aggrs=("mean", "max", "min", "std"), eps: float = 1e-5):
+        from .spmm_multi import check_aggrs
+
+        self.aggrs = check_aggrs("SpMMMulti", aggrs, eps)
+        self.eps = float(eps)
+        self.moments = "var" in self.aggrs or "std" in self.aggrs
+        super().__init__(indptr, indices, num_rows, num_cols, transposed)
+
+    def __call__(self, feat: torch.Tensor) -> torch.Tensor:
+        assert feat.dim() >= 2 and feat.shape[0] == self.num_cols, (tuple(feat.shape), self.num_cols)
+        return _SpMMMultiFunction.apply(feat, self)
+
+
 class _SpMMEdgeFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, efeat, op, kind):

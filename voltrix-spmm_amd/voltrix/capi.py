@@ -113,6 +113,8 @@ SIGNATURES = {
     "voltrix_spmm_rel_dots_csr": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _I, _P, _P]),
     "voltrix_quantize_fp8_rows": (_I, [_P, _I, _I, _I, _L, _P, _P, _L, _P]),
     "voltrix_spmm_fp8_csr": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _L, _P]),
+    "voltrix_spmm_multi_csr": (_I, [_P, _P, _I, _L, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
+    "voltrix_spmm_multi_backward_csr": (_I, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
     "voltrix_launch_sample_neighbors": (None, [_P, _P, _I, _P, _I, _P, _L, _I, _I, _U64, _U64, _P, _P, _P, _RC_P]),
     "voltrix_launch_block_mark": (None, [_P, _L, _I, _P, _P, _RC_P]),
     "voltrix_launch_block_mark_seeds": (None, [_P, _I, _I, _P, _P, _RC_P]),
@@ -1103,6 +1105,62 @@ def launch_spmm_fp8(indptr, indices, values, num_rows: int, data, scale, output,
                                      scale.data_ptr(), output.data_ptr(), _dtype_code(output.dtype), int(xcd_ranges), num_entries,
                                      stream),
           "voltrix_spmm_fp8_csr")
+
+
+# ---- several aggregates from one gather (csrc/capi_spmm_multi.hip).  The two entry points return their status code; the wrappers are
+# ---- not bracketed by KernelTimer
+
+MULTI_AGGREGATES = ("sum", "mean", "max", "min", "var", "std")   # the order of the slot parameters of voltrix_spmm_multi_csr
+
+
+def launch_spmm_multi(indptr, indices, num_rows: int, feat, slots, eps: float, output, argmax, argmin, stream, num_entries=None) -> None:
+    """``output[r, slots[name]] = name over the entries of row r of feat[indices[e]]`` for every ``name`` of ``slots`` (a dict from
+    ``MULTI_AGGREGATES`` to the slots ``0 .. A - 1``; voltrix/spmm_multi_kernels.hpp): device int32 CSR, fp32 / fp16 / bf16 ``feat``
+    [*, F] whose rows are a multiple of 16 bytes, fp32 ``output`` [num_rows, A, F], ``argmax`` / ``argmin`` int32 [num_rows, F] or
+    None; ``num_entries``: ``indices.numel()`` unless given (a pattern without entries, whose ``indices`` is a stand-in); see
+    include/voltrix_capi.h."""
+    import torch
+
+    assert indptr.dtype == torch.int32 and indices.dtype == torch.int32 and indptr.numel() == num_rows + 1
+    assert indptr.is_contiguous() and indices.is_contiguous()
+    assert feat.dim() == 2 and feat.is_contiguous() and output.is_contiguous() and output.dtype == torch.float32
+    assert output.shape == (num_rows, len(slots), feat.shape[1])
+    for arg in (argmax, argmin):
+        assert arg is None or (arg.dtype == torch.int32 and arg.is_contiguous() and arg.shape == (num_rows, feat.shape[1]))
+    num_entries = indices.numel() if num_entries is None else num_entries
+    check(lib().voltrix_spmm_multi_csr(indptr.data_ptr(), indices.data_ptr(), num_rows, num_entries, feat.shape[1], feat.data_ptr(),
+                                       _dtype_code(feat.dtype), *[slots.get(name, -1) for name in MULTI_AGGREGATES], len(slots),
+                                       float(eps), output.data_ptr(), _opt(argmax), _opt(argmin), stream),
+          "voltrix_spmm_multi_csr")
+
+
+def launch_spmm_multi_backward(t_indptr, t_indices, t_order, num_cols: int, x, u, w, mean, g_max, argmax, g_min, argmin, output,
+                               stream) -> None:
+    """``output[c] = sum_{e in row c of the transposed CSR} u[r] + w[r] (x[c] - mean[r]) + [argmax[r] == t_order[e]] g_max[r] +
+    [argmin[r] == t_order[e]] g_min[r]`` with ``r = t_indices[e]``: fp32 operands (int32 args) [*, F] with F a multiple of 4, each
+    group -- ``u``; ``w`` with ``x`` and ``mean``; ``g_max`` with ``argmax``; ``g_min`` with ``argmin`` -- given or None; ``mean`` may
+    be a column slice of a wider array (rows of ``mean.stride(0)`` floats); fp32 ``output`` [num_cols, F]; see include/voltrix_capi.h."""
+    import torch
+
+    assert t_indptr.dtype == torch.int32 and t_indices.dtype == torch.int32 and t_indptr.numel() == num_cols + 1
+    assert t_indptr.is_contiguous() and t_indices.is_contiguous()
+    nnz = t_indices.numel()
+    assert t_order.dtype == torch.int32 and t_order.is_contiguous() and t_order.numel() == nnz
+    assert output.dtype == torch.float32 and output.is_contiguous() and output.dim() == 2 and output.shape[0] == num_cols
+    dim = output.shape[1]
+    for t in (x, u, w, g_max, g_min):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == dim)
+    for t in (argmax, argmin):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == dim)
+    assert x is None or x.shape[0] == num_cols
+    mean_ld = 0
+    if mean is not None:
+        assert mean.dtype == torch.float32 and mean.dim() == 2 and mean.shape[1] == dim and (mean.stride(1) == 1 or dim == 1)
+        mean_ld = mean.stride(0) if mean.shape[0] > 1 else dim
+    check(lib().voltrix_spmm_multi_backward_csr(t_indptr.data_ptr(), t_indices.data_ptr(), t_order.data_ptr(), num_cols, nnz, dim,
+                                                _opt(x), _opt(u), _opt(w), _opt(mean), mean_ld, _opt(g_max), _opt(argmax), _opt(g_min),
+                                                _opt(argmin), output.data_ptr(), stream),
+          "voltrix_spmm_multi_backward_csr")
 
 
 SAMPLE_ALL, SAMPLE_MAX_FANOUT = -1, 64     # `fanout` of voltrix_launch_sample_neighbors: every entry of every row; the largest fan-out
