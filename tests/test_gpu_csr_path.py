@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
-@pytest.mark.parametrize("width", [8, 32, 72, 128, 200, 512, 1024])
+@pytest.mark.parametrize("width", [8, 32, 72, 128, 200, 512, 520, 1024])   # 520: a last slab of 2 (fp32) and of 1 (16-bit) pieces
 def test_csr_kernel_matches_the_oracle(cuda_device, csr_fixture, dtype, width):
     g = csr_fixture
     n = int(g["num_nodes"])

@@ -386,7 +386,7 @@ def _check_aggregate(indptr, indices, v, feat, num_rows, out, single_head_bits=T
 def test_aggregation_heads_shapes_and_types(cuda_device, name):
     indptr, indices, n, m = _graph(name)
     nnz = indices.numel()
-    for heads, dim in SHAPES:
+    for heads, dim in SHAPES + [(1, 8)]:      # (1, 8): a row of one 16-byte piece for the 16-bit types
         for dtype in TYPES:
             feat = _randn((m, heads, dim), dtype, 7 * heads + dim)
             v = _randn((nnz, heads), torch.float32, 7 * heads + dim + 1)

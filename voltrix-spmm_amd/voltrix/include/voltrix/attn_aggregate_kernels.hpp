@@ -11,8 +11,8 @@
 // m[row_e, h] and l[row_e, h], so it is recomputed where it is used and never stored; and sum_e alpha_e <dC_r, feat_e> = <dC_r, out_r>,
 // so the softmax backward's row reduction is the dense product delta (torch, [n, H, D]) instead of a segmented scan over the edges.
 //
-// Forward (attn_aggregate_csr_kernel).  spmm_csr_heads_kernel<T, 4>'s shape: a group of min(64, next_pow2(H D / V)) lanes owns one
-// row, grid.y walks slabs of 64 pieces, a lane owns 16 bytes of every gathered row and the head piece / (D / V).  Two passes per row.
+// Forward (attn_aggregate_csr_kernel).  spmm_csr_heads_kernel<T, 4>'s shape: the lane's place of csr_row_gather.hpp over rows of H D
+// elements, a lane owns the head piece / (D / V).  Two passes per row.
 // Pass 1: the row maximum of the lane's head -- a maximum is exact in any order, so when a head is a power of two of pieces (<= 64)
 // its lanes split the row's entries and combine with an xor tree; any other head width has every lane read all of them.  Pass 2:
 // w_e = exp(|scale| (sigma s_e - m)), acc = fma(w_e, feat, acc) and l += w_e in CSR edge order, batches of 4 edges with a clamped
@@ -120,16 +120,10 @@ template <typename T, int UNROLL, bool DROP = false>
 static __global__ __launch_bounds__(256) void attn_aggregate_csr_kernel(const AttnAggregateArgs<T> a) {
 #pragma clang fp contract(off)
   constexpr int V = 16 / (int)sizeof(T);
-  const int L = a.lanes_per_row;
-  const int rows_per_group = 256 / L;
-  // XCD x owns the row groups [x * groups_per_xcd, (x + 1) * groups_per_xcd)
-  const long long group = (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd;
-  const long long row = group * rows_per_group + (int)threadIdx.x / L;
-  if (row >= a.num_rows) return;
-  const int lane = (int)threadIdx.x & (L - 1);
-  const int piece = (int)blockIdx.y * 64 + lane;                       // this lane's 16 bytes of every gathered row
-  const long long col0 = (long long)piece * V;
-  if (col0 >= a.F) return;                                             // whole heads leave: a head's lanes stay together below
+  const CsrLanePlace p = csr_lane_place<V>(a.lanes_per_row, a.groups_per_xcd, a.num_rows, a.F);
+  if (!p.work) return;                                                 // whole heads leave: a head's lanes stay together below
+  const long long row = p.row, col0 = p.col0;
+  const int piece = p.piece;
   const long long H = a.heads;
   const int head = piece / a.head_pieces;
   const float* const sc = a.scores + head;                             // this lane's head: s[e, head] = sc[e H]
@@ -278,7 +272,7 @@ inline int launch_attn_aggregate_csr_impl(const int* indptr, const int* indices,
   const RowGroupGrid g = row_group_grid(num_rows, pieces);
   if (!g.ok) return kErrBadShape;
   const int max_lanes = head_pieces <= 64 && (head_pieces & (head_pieces - 1)) == 0 ? head_pieces : 1;
-  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
+  const dim3 grid = row_group_dim3(g);
   auto go = [&](auto tag) {
     using T = decltype(tag);
     const AttnAggregateArgs<T> a{indptr, indices, static_cast<const T*>(input), output, scores, m, l, num_rows, heads, head_pieces,
@@ -545,15 +539,10 @@ template <typename T, int UNROLL, bool DROP = false>
 static __global__ __launch_bounds__(256) void attn_aggregate_grad_feat_kernel(const AttnAggregateGradFeatArgs<T> a) {
 #pragma clang fp contract(off)
   constexpr int V = 16 / (int)sizeof(T);
-  const int L = a.lanes_per_row;
-  const int rows_per_group = 256 / L;
-  const long long group = (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd;
-  const long long row = group * rows_per_group + (int)threadIdx.x / L;
-  if (row >= a.num_rows) return;
-  const int lane = (int)threadIdx.x & (L - 1);
-  const int piece = (int)blockIdx.y * 64 + lane;
-  const long long col0 = (long long)piece * V;
-  if (col0 >= a.F) return;
+  const CsrLanePlace p = csr_lane_place<V>(a.lanes_per_row, a.groups_per_xcd, a.num_rows, a.F);
+  if (!p.work) return;
+  const long long row = p.row, col0 = p.col0;
+  const int piece = p.piece;
   const long long H = a.heads;
   const int head = piece / a.head_pieces;
   const float* const sc = a.scores + head;
@@ -669,9 +658,7 @@ static __global__ __launch_bounds__(256) void attn_aggregate_grad_feat_kernel(co
         }
       }
   }
-  float4_t* out = reinterpret_cast<float4_t*>(a.output + row * F + col0);
-#pragma unroll
-  for (int i = 0; i < V / 4; ++i) out[i] = float4_t{acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]};
+  csr_store_piece(a.output + row * F + col0, acc);
 }
 
 // d_feat[c, h, :] = sum_{e in row c of the transposed CSR} alpha[order[e], h] grad_out[t_indices[e], h, :], alpha recomputed from
@@ -695,7 +682,7 @@ inline int launch_attn_aggregate_grad_feat_csr_impl(const int* t_indptr, const i
   const int pieces = heads * head_pieces;
   const RowGroupGrid g = row_group_grid(num_rows, pieces);
   if (!g.ok) return kErrBadShape;
-  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
+  const dim3 grid = row_group_dim3(g);
   auto go = [&](auto tag) {
     using T = decltype(tag);
     const AttnAggregateGradFeatArgs<T> a{t_indptr, t_indices, order, static_cast<const T*>(grad_out), out, scores, m, l, num_rows,

@@ -18,10 +18,9 @@
 // pieces) walks the pieces.  Slabs of whole heads go through grid.y; XCD x = blockIdx.x % 8 owns a contiguous eighth of the chunks.  The
 // xor butterfly stops at Lh and lane 0 of every head stores: the H floats of an edge leave in one store instruction.
 //
-// Row sum (gatv2_rowsum_csr_kernel), one family for both sides.  spmm_csr_heads_kernel's shape: a group of
-// min(64, next_pow2(H D / V)) lanes owns one row, grid.y walks slabs of 64 pieces, batches of 4 edges in flight with the tail batch
-// clamped.  The lane holds its piece of p[r] as floats, reads the one float g[., head] of its head and slope g once per edge, and adds
-// z > 0 ? g : slope g in CSR edge order.  Every row of G is written (empty rows: +0); no workspace.
+// Row sum (gatv2_rowsum_csr_kernel), one family for both sides.  The row-gather skeleton of csr_row_gather.hpp over rows of H D
+// elements, UNROLL = 4.  The lane holds its piece of p[r] as floats, reads the one float g[., head] of its head and slope g once per
+// edge, and adds z > 0 ? g : slope g in CSR edge order.  Every row of G is written (empty rows: +0); no workspace.
 //
 // Known limit.  A row per lane group keeps the weakness of spmm_csr_rows_kernel / spmm_csr_heads_kernel on hub rows: a hub row (or,
 // for G_r, a hub column) serialises its wave.  Splitting hub rows with a fixed-order combine is the follow-up for this kernel and
@@ -43,6 +42,7 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "voltrix/csr_row_gather.hpp"
 #include "voltrix/sddmm_kernels.hpp"
 
 namespace voltrix {
@@ -258,52 +258,37 @@ template <typename T, int UNROLL>
 static __global__ __launch_bounds__(256) void gatv2_rowsum_csr_kernel(const Gatv2RowsumArgs<T> a) {
 #pragma clang fp contract(off)   // every term is g or the one rounded product slope g: no product fused into the sum
   constexpr int V = 16 / (int)sizeof(T);
-  const int L = a.lanes_per_row;
-  const int rows_per_group = 256 / L;
-  // XCD x owns the row groups [x * groups_per_xcd, (x + 1) * groups_per_xcd)
-  const long long group = (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd;
-  const long long row = group * rows_per_group + (int)threadIdx.x / L;
-  if (row >= a.num_rows) return;
-  const int lane = (int)threadIdx.x & (L - 1);
-  const int piece = (int)blockIdx.y * 64 + lane;                       // this lane's 16 bytes of p[row] and of every gathered row
-  const long long col0 = (long long)piece * V;
-  if (col0 >= a.F) return;
+  const CsrLanePlace p = csr_lane_place<V>(a.lanes_per_row, a.groups_per_xcd, a.num_rows, a.F);
+  if (!p.work) return;
   const long long H = a.heads;
   const long long F = a.F;
-  const float* const gh = a.g + piece / a.head_pieces;                 // this lane's head: g[e, head] = gh[e H]
+  const float* const gh = a.g + p.piece / a.head_pieces;               // this lane's head: g[e, head] = gh[e H]
   const float slope = a.slope;
   float acc[V], pv[V];
 #pragma unroll
   for (int i = 0; i < V; ++i) acc[i] = 0.0f;
-  sddmm_to_float<T, 1>({*reinterpret_cast<const uint4_t*>(a.p + row * F + col0)}, pv);
-  int e = a.indptr[row];
-  const int end = a.indptr[row + 1];
-  const T* const base = a.q + col0;
-  // a batch of UNROLL edges from e, every load issued before the first is consumed; the tail batch clamps its ids and skips the rest
-  auto batch = [&](auto tail) {
-    uint4_t raw[UNROLL];
-    float gv[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int ee = !decltype(tail)::value || u < end - e ? e + u : end - 1;
-      raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
-      gv[u] = gh[(long long)(a.order != nullptr ? a.order[ee] : ee) * H];
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-      if (!decltype(tail)::value || u < end - e) {
-        float qv[V];
-        sddmm_to_float<T, 1>({raw[u]}, qv);
-        const float gs = slope * gv[u];                                // one rounded product per edge
-#pragma unroll
-        for (int i = 0; i < V; ++i) acc[i] += (pv[i] + qv[i] > 0.0f) ? gv[u] : gs;
-      }
+  sddmm_to_float<T, 1>({*reinterpret_cast<const uint4_t*>(a.p + p.row * F + p.col0)}, pv);
+  const T* const base = a.q + p.col0;
+  struct Slot {
+    uint4_t raw;
+    float gv;
   };
-  for (; end - e >= UNROLL; e += UNROLL) batch(std::false_type{});
-  if (e < end) batch(std::true_type{});
-  float4_t* out = reinterpret_cast<float4_t*>(a.out + row * F + col0);
+  csr_for_each_batch<UNROLL, Slot>(
+      a.indptr[p.row], a.indptr[p.row + 1],
+      [&](Slot& s, const int ee) {
+        s.raw = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
+        s.gv = gh[(long long)(a.order != nullptr ? a.order[ee] : ee) * H];
+      },
+      [&](const Slot& s, int, const bool live) {
+        if (live) {
+          float qv[V];
+          sddmm_to_float<T, 1>({s.raw}, qv);
+          const float gs = slope * s.gv;                               // one rounded product per edge
 #pragma unroll
-  for (int i = 0; i < V / 4; ++i) out[i] = float4_t{acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]};
+          for (int i = 0; i < V; ++i) acc[i] += (pv[i] + qv[i] > 0.0f) ? s.gv : gs;
+        }
+      });
+  csr_store_piece(a.out + p.row * F + p.col0, acc);
 }
 
 // dtype: 0 fp32, 1 fp16, 2 bfloat16 (p and q).  order: null, or int32 [nnz].  Every row of out[num_rows, heads, head_dim] is written
@@ -326,7 +311,7 @@ inline int launch_gatv2_rowsum_csr(const int* indptr, const int* indices, const 
   const int pieces = heads * head_pieces;                // 16-byte pieces per row
   const RowGroupGrid grid_of = row_group_grid(num_rows, pieces);
   if (!grid_of.ok) return kErrBadShape;
-  const dim3 grid((unsigned)(grid_of.per_xcd * kNumXcd), (unsigned)grid_of.slabs);
+  const dim3 grid = row_group_dim3(grid_of);
   auto go = [&](auto tag) {
     using T = decltype(tag);
     const Gatv2RowsumArgs<T> args{indptr, indices, order, static_cast<const T*>(p), static_cast<const T*>(q), g, out, num_rows, heads,

@@ -1,6 +1,7 @@
 // Voltrix-SpMM for MI355X (gfx950) -- what the launch_* host functions of the CSR / attention kernels share: the operand checks and the
-// two launch geometries, and the dispatch over the operand's type.  Host code only: plain C++17, no HIP, nothing for the device.  The callers build their own dim3 and kernel
-// arguments from the integers returned here (tests/test_launch_geometry.py restates both formulas).
+// two launch geometries, and the dispatch over the operand's type.  Host code only: plain C++17, no HIP, nothing for the device.  The
+// callers build their kernel arguments and their dim3 from the integers returned here -- the row-group grid through
+// csr_row_gather.hpp's row_group_dim3, beside the device code that inverts it (tests/test_launch_geometry.py restates both formulas).
 #pragma once
 
 #include <cstdint>

@@ -6,11 +6,10 @@
 // its own at F = D: H reads of indptr / indices, H gathers of a D-wide slice, and -- on the block-format path -- the head's values
 // scattered into the value planes of A and A^T first.  Here nothing is installed: the values are read where they are used.
 //
-// Shape.  spmm_csr_rows_kernel<T, 4, true> where a lane multiplies by the value of ITS head: a group of L = min(64, next_pow2(H D / V))
-// lanes owns one row, grid.y walks slabs of 64 pieces, a lane owns 16 bytes of every gathered row and its head is piece / (D / V).  One
-// indices read and one gathered row per edge serve all heads; the H values of an edge are 4 H consecutive bytes, read by every lane as
-// the one float of its head (the lanes of a head share the address, the group shares the one or two 32-byte sectors).  Batches of 4
-// edges in flight, the tail batch clamped, as in the single-head kernel.
+// Shape.  The row-gather skeleton of csr_row_gather.hpp (V = 16 bytes of the operand, UNROLL = 4) over rows of H D elements, where a
+// lane multiplies by the value of ITS head, piece / (D / V).  One indices read and one gathered row per edge serve all heads; the H
+// values of an edge are 4 H consecutive bytes, read by every lane as the one float of its head (the lanes of a head share the address,
+// the group shares the one or two 32-byte sectors).
 //
 // Numerics.  fp32 products, one fused multiply-add per element, summed in CSR edge order: out[:, h] has the BITS of
 // spmm_csr_rows_kernel<T, 4, true> on the contiguous slices v[:, h], feat[:, h].  |out - ref| <= deg_r 2^-23 sum_e |v[e, h]| |feat[col_e, h, d]|.
@@ -48,54 +47,29 @@ struct CsrHeadsArgs {
 template <typename T, int UNROLL>
 static __global__ __launch_bounds__(256) void spmm_csr_heads_kernel(const CsrHeadsArgs<T> a) {
   constexpr int V = 16 / (int)sizeof(T);
-  const int L = a.lanes_per_row;
-  const int rows_per_group = 256 / L;
-  // XCD x owns the row groups [x * groups_per_xcd, (x + 1) * groups_per_xcd)
-  const long long group = (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd;
-  const long long row = group * rows_per_group + (int)threadIdx.x / L;
-  if (row >= a.num_rows) return;
-  const int lane = (int)threadIdx.x & (L - 1);
-  const int piece = (int)blockIdx.y * 64 + lane;                       // this lane's 16 bytes of every gathered row
-  const long long col0 = (long long)piece * V;
-  if (col0 >= a.F) return;
+  const CsrLanePlace p = csr_lane_place<V>(a.lanes_per_row, a.groups_per_xcd, a.num_rows, a.F);
+  if (!p.work) return;
   const long long H = a.heads;
-  const float* const vals = a.values + piece / a.head_pieces;          // this lane's head: v[e, head] = vals[e H]
+  const float* const vals = a.values + p.piece / a.head_pieces;        // this lane's head: v[e, head] = vals[e H]
   float acc[V];
 #pragma unroll
   for (int i = 0; i < V; ++i) acc[i] = 0.0f;
-  int e = a.indptr[row];
-  const int end = a.indptr[row + 1];
-  const T* const base = a.input + col0;
+  const T* const base = a.input + p.col0;
   const long long F = a.F;
-  // full batches of UNROLL edges, then one more batch for the tail with clamped ids (spmm_csr_rows_kernel: every load issued before the
-  // first is consumed)
-  for (; end - e >= UNROLL; e += UNROLL) {
-    uint4_t raw[UNROLL];
-    float v[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[e + u] * F);
-      v[u] = vals[(long long)(e + u) * H];
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) csr_accumulate_scaled<T>(acc, raw[u], v[u]);
-  }
-  if (e < end) {
-    uint4_t raw[UNROLL];
-    float v[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int ee = u < end - e ? e + u : end - 1;
-      raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
-      v[u] = vals[(long long)ee * H];
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-      if (u < end - e) csr_accumulate_scaled<T>(acc, raw[u], v[u]);
-  }
-  float4_t* out = reinterpret_cast<float4_t*>(a.output + row * F + col0);
-#pragma unroll
-  for (int i = 0; i < V / 4; ++i) out[i] = float4_t{acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]};
+  struct Slot {
+    uint4_t raw;
+    float v;
+  };
+  csr_for_each_batch<UNROLL, Slot>(
+      a.indptr[p.row], a.indptr[p.row + 1],
+      [&](Slot& s, const int ee) {
+        s.raw = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
+        s.v = vals[(long long)ee * H];
+      },
+      [&](const Slot& s, int, const bool live) {
+        if (live) csr_accumulate_scaled<T>(acc, s.raw, s.v);
+      });
+  csr_store_piece(a.output + p.row * F + p.col0, acc);
 }
 
 // dtype: 0 fp32, 1 fp16, 2 bfloat16.  head_dim % (16 / sizeof(T)) == 0 (a head is a whole number of 16-byte pieces).  Every row of
@@ -112,7 +86,7 @@ inline int launch_spmm_csr_heads(const int* indptr, const int* indices, const fl
   const int pieces = heads * head_pieces;                // 16-byte pieces per row
   const RowGroupGrid g = row_group_grid(num_rows, pieces);
   if (!g.ok) return kErrBadShape;
-  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
+  const dim3 grid = row_group_dim3(g);
   auto go = [&](auto tag) {
     using T = decltype(tag);
     const CsrHeadsArgs<T> a{indptr, indices, static_cast<const T*>(input), output, values, num_rows, heads, head_pieces,

@@ -10,12 +10,9 @@
 // the exact tiles and 0.172 for rocSPARSE's best algorithm; F = 512 0.449 / 0.650 / 0.661; com-amazon-like 0.145 / 0.180 / 0.191.
 // voltrix.spmm times it ONCE per (handle, width, dtype) against the block-format path and keeps the faster (spmm/spmm.py).
 //
-// Shape.  A group of L = min(64, next_pow2(slab_columns / V)) lanes owns one row (V = 16 bytes of the operand: 4 fp32, 8 fp16 / bf16);
-// a 256-thread workgroup owns 256 / L consecutive rows; grid.y walks column slabs of 64 V columns (fp32: 256, 16-bit: 512).  Per edge a
-// lane loads its 16 bytes of row B[col] (batches of UNROLL = 4 edges in flight, the last batch masked), accumulates in fp32 in CSR order, and stores 16-byte pieces of C.
-// Workgroup -> rows: XCD x = blockIdx.x % 8 owns a contiguous eighth of the row groups (xcd_ranges = 1: neighbouring rows, which
-// reference neighbouring rows of B on band / community graphs, share an L2; equal or better than the round-robin order on every graph
-// measured: amazon0505-like x 128 fp32 0.297 -> 0.256 ms, ppi-like x 512 0.166 -> 0.111), or workgroup b = row group b (0).  A binary: products are exact; the sum is fp32 in edge order:
+// Shape.  The row-gather skeleton of csr_row_gather.hpp with V = 16 bytes of the operand (4 fp32, 8 fp16 / bf16) and UNROLL = 4:
+// per entry a lane loads its 16 bytes of row B[col], accumulates in fp32 in CSR order, and stores 16-byte pieces of C.  xcd_ranges = 0
+// asks for the round-robin order of workgroups.  A binary: products are exact; the sum is fp32 in edge order:
 // |C - ref| <= deg * 2^-23 * (A |B|).
 //
 // Bound: the CUs' line-request rate / HBM, like the window kernel on these graphs.  Rows of very different length
@@ -27,8 +24,7 @@
 #include <cstdint>
 #include <type_traits>
 
-#include "voltrix/launch_geometry.hpp"
-#include "voltrix/spmm_kernels.hpp"
+#include "voltrix/csr_row_gather.hpp"
 
 namespace voltrix {
 
@@ -46,102 +42,33 @@ struct CsrArgs {
   int xcd_ranges;       // 1: XCD x owns a contiguous eighth of the row groups; 0: consecutive groups go round the XCDs
 };
 
-template <typename T>
-__device__ __forceinline__ void csr_accumulate(float (&acc)[16 / sizeof(T)], const uint4_t raw) {
-  if constexpr (std::is_same<T, float>::value) {
-    const float4_t v = __builtin_bit_cast(float4_t, raw);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] += v[i];
-  } else if constexpr (std::is_same<T, _Float16>::value) {
-    const half8_t v = __builtin_bit_cast(half8_t, raw);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] += (float)v[i];
-  } else {   // bfloat16 as bits: a 16-bit shift is the conversion
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      acc[2 * i] += __builtin_bit_cast(float, raw[i] << 16);
-      acc[2 * i + 1] += __builtin_bit_cast(float, raw[i] & 0xffff0000u);
-    }
-  }
-}
-
-// acc += v * row piece (WEIGHTED kernels: one fused multiply-add per element, a single fp32 rounding)
-template <typename T>
-__device__ __forceinline__ void csr_accumulate_scaled(float (&acc)[16 / sizeof(T)], const uint4_t raw, const float v) {
-  if constexpr (std::is_same<T, float>::value) {
-    const float4_t x = __builtin_bit_cast(float4_t, raw);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf(v, x[i], acc[i]);
-  } else if constexpr (std::is_same<T, _Float16>::value) {
-    const half8_t x = __builtin_bit_cast(half8_t, raw);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] = __builtin_fmaf(v, (float)x[i], acc[i]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      acc[2 * i] = __builtin_fmaf(v, __builtin_bit_cast(float, raw[i] << 16), acc[2 * i]);
-      acc[2 * i + 1] = __builtin_fmaf(v, __builtin_bit_cast(float, raw[i] & 0xffff0000u), acc[2 * i + 1]);
-    }
-  }
-}
-
 template <typename T, int UNROLL, bool WEIGHTED = false>
 static __global__ __launch_bounds__(256) void spmm_csr_rows_kernel(const CsrArgs<T> a) {
   constexpr int V = 16 / (int)sizeof(T);
-  const int L = a.lanes_per_row;
-  const int rows_per_group = 256 / L;
-  // xcd_ranges: XCD x owns the row groups [x * groups_per_xcd, (x + 1) * groups_per_xcd); else workgroup b = row group b
-  const long long group = a.xcd_ranges ? (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd
-                                       : (long long)blockIdx.x;
-  const long long row = group * rows_per_group + (int)threadIdx.x / L;
-  if (row >= a.num_rows) return;
-  const int lane = (int)threadIdx.x & (L - 1);
-  const long long col0 = ((long long)blockIdx.y * 64 + lane) * V;     // this lane's 16 bytes of every gathered row
-  if (col0 >= a.F) return;
+  const CsrLanePlace p = csr_lane_place<V>(a.lanes_per_row, a.groups_per_xcd, a.num_rows, a.F, a.xcd_ranges != 0);
+  if (!p.work) return;
   float acc[V];
 #pragma unroll
   for (int i = 0; i < V; ++i) acc[i] = 0.0f;
-  int e = a.indptr[row];
-  const int end = a.indptr[row + 1];
-  const T* const base = a.input + col0;
+  const T* const base = a.input + p.col0;
   const long long F = a.F;
-  // full batches of UNROLL edges, then ONE more batch for the tail with clamped ids (every load of it is issued, unconditionally, before
-  // the first is consumed; the slots past the row's end are skipped when adding): at mean degree 5 a row is one or two batches with all
-  // their loads in flight -- a scalar tail loop ran most rows of these graphs one load at a time; a tail whose LOADS were predicated
-  // serialised them (ppi-like x 128: 0.150 ms against 0.091; profiles/r06/experiment_csr_mapping.log)
-  for (; end - e >= UNROLL; e += UNROLL) {
-    uint4_t raw[UNROLL];
-    float v[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[e + u] * F);
-      if constexpr (WEIGHTED) v[u] = a.values[e + u];
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      if constexpr (WEIGHTED) csr_accumulate_scaled<T>(acc, raw[u], v[u]);
-      else csr_accumulate<T>(acc, raw[u]);
-    }
-  }
-  if (e < end) {
-    uint4_t raw[UNROLL];
-    float v[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int ee = u < end - e ? e + u : end - 1;
-      raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
-      if constexpr (WEIGHTED) v[u] = a.values[ee];
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-      if (u < end - e) {
-        if constexpr (WEIGHTED) csr_accumulate_scaled<T>(acc, raw[u], v[u]);
-        else csr_accumulate<T>(acc, raw[u]);
-      }
-  }
-  float4_t* out = reinterpret_cast<float4_t*>(a.output + row * F + col0);
-#pragma unroll
-  for (int i = 0; i < V / 4; ++i) out[i] = float4_t{acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]};
+  struct Slot {
+    uint4_t raw;
+    float v;   // WEIGHTED
+  };
+  csr_for_each_batch<UNROLL, Slot>(
+      a.indptr[p.row], a.indptr[p.row + 1],
+      [&](Slot& s, const int ee) {
+        s.raw = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
+        if constexpr (WEIGHTED) s.v = a.values[ee];
+      },
+      [&](const Slot& s, int, const bool live) {
+        if (live) {
+          if constexpr (WEIGHTED) csr_accumulate_scaled<T>(acc, s.raw, s.v);
+          else csr_accumulate<T>(acc, s.raw);
+        }
+      });
+  csr_store_piece(a.output + p.row * F + p.col0, acc);
 }
 
 // dtype: 0 fp32, 1 fp16, 2 bfloat16.  embedding_dim % (16 / sizeof(T)) == 0 (16-byte row pieces).  Every row of `output` is written.

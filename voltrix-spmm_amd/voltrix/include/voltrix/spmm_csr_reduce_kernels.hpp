@@ -7,10 +7,8 @@
 // attn_aggregate_kernels.hpp).  Max-pool GraphSAGE, PNA's towers, GIN-max and edge convolutions select.  The composite -- feat[cols]
 // ([nnz, F] materialised) + scatter_reduce -- moves the gathered rows three times and has an index_add backward with float atomics.
 //
-// Forward shape.  spmm_csr_heads_kernel's: a group of L = min(64, next_pow2(F / V)) lanes owns one row, grid.y walks slabs of 64 pieces,
-// a lane owns 16 bytes of every gathered row (V = 4 fp32, 8 fp16 / bf16), XCD x owns a contiguous range of row groups, batches of
-// UNROLL = 4 edges are issued before the first is consumed, the tail batch reads clamped ids and its surplus slots are skipped (a
-// clamped entry never takes part in the selection).  No workspace.
+// Forward shape.  The row-gather skeleton of csr_row_gather.hpp (V = 16 bytes of the operand, UNROLL = 4); a surplus slot of the tail
+// batch never takes part in the selection.  No workspace.
 //
 // Selection (max; min mirrors it).  Per element `best` (float) and `arg` (int32) start at (-inf, indptr[row]); entry e with value v is
 // taken when v > best || (v != v && best == best).  Strict, so the first entry in CSR order wins ties (+0 and -0 tie); the first NaN
@@ -61,26 +59,6 @@ struct CsrReduceArgs {
   int groups_per_xcd;   // ceil(row groups / 8): sizes the grid; a row group = 256 / lanes_per_row rows
 };
 
-// the 16 bytes of a lane as fp32 (exact for every T)
-template <typename T>
-__device__ __forceinline__ void csr_piece_as_float(float (&v)[16 / sizeof(T)], const uint4_t raw) {
-  if constexpr (std::is_same<T, float>::value) {
-    const float4_t x = __builtin_bit_cast(float4_t, raw);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = x[i];
-  } else if constexpr (std::is_same<T, _Float16>::value) {
-    const half8_t x = __builtin_bit_cast(half8_t, raw);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)x[i];
-  } else {   // bfloat16 as bits: a 16-bit shift is the conversion
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __builtin_bit_cast(float, raw[i] << 16);
-      v[2 * i + 1] = __builtin_bit_cast(float, raw[i] & 0xffff0000u);
-    }
-  }
-}
-
 // entry `e`'s piece against the running winner: strict, first wins ties, the first NaN wins and stays.  `live` = false: a surplus slot
 // of the tail batch, never taken (part of the predicate, so the tail has no branch around its selects)
 template <typename T, int OP, bool WITH_ARG>
@@ -103,18 +81,10 @@ template <typename T, int OP, bool WITH_ARG, int UNROLL = 4>
 static __global__ __launch_bounds__(256) void spmm_csr_reduce_kernel(const CsrReduceArgs<T> a) {
   static_assert(OP == kReduceMax || OP == kReduceMin || (OP == kReduceMean && !WITH_ARG), "mean has no arg");
   constexpr int V = 16 / (int)sizeof(T);
-  const int L = a.lanes_per_row;
-  const int rows_per_group = 256 / L;
-  // XCD x owns the row groups [x * groups_per_xcd, (x + 1) * groups_per_xcd)
-  const long long group = (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd;
-  const long long row = group * rows_per_group + (int)threadIdx.x / L;
-  if (row >= a.num_rows) return;
-  const int lane = (int)threadIdx.x & (L - 1);
-  const long long col0 = ((long long)blockIdx.y * 64 + lane) * V;     // this lane's 16 bytes of every gathered row
-  if (col0 >= a.F) return;
-  int e = a.indptr[row];
-  const int begin = e;
-  const int end = a.indptr[row + 1];
+  const CsrLanePlace p = csr_lane_place<V>(a.lanes_per_row, a.groups_per_xcd, a.num_rows, a.F);
+  if (!p.work) return;
+  const int begin = a.indptr[p.row];
+  const int end = a.indptr[p.row + 1];
   float acc[V];   // the sum (mean) or the winner (max / min)
   int arg[WITH_ARG ? V : 1];
 #pragma unroll
@@ -123,36 +93,20 @@ static __global__ __launch_bounds__(256) void spmm_csr_reduce_kernel(const CsrRe
 #pragma unroll
     for (int i = 0; i < V; ++i) arg[i] = begin;
   }
-  const T* const base = a.input + col0;
+  const T* const base = a.input + p.col0;
   const long long F = a.F;
-  // full batches of UNROLL edges, then one more batch for the tail with clamped ids (spmm_csr_rows_kernel: every load issued before the
-  // first is consumed); a clamped slot is never selected from
-  for (; end - e >= UNROLL; e += UNROLL) {
-    uint4_t raw[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[e + u] * F);
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      if constexpr (OP == kReduceMean) csr_accumulate<T>(acc, raw[u]);
-      else csr_select<T, OP, WITH_ARG>(acc, arg, raw[u], e + u);
-    }
-  }
-  if (e < end) {
-    uint4_t raw[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int ee = u < end - e ? e + u : end - 1;
-      raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F);
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      if constexpr (OP == kReduceMean) {
-        if (u < end - e) csr_accumulate<T>(acc, raw[u]);
-      } else {
-        csr_select<T, OP, WITH_ARG>(acc, arg, raw[u], e + u, u < end - e);
-      }
-    }
-  }
+  struct Slot {
+    uint4_t raw;
+  };
+  csr_for_each_batch<UNROLL, Slot>(
+      begin, end, [&](Slot& s, const int ee) { s.raw = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F); },
+      [&](const Slot& s, const int entry, const bool live) {
+        if constexpr (OP == kReduceMean) {
+          if (live) csr_accumulate<T>(acc, s.raw);
+        } else {
+          csr_select<T, OP, WITH_ARG>(acc, arg, s.raw, entry, live);
+        }
+      });
   const int deg = end - begin;
   if constexpr (OP == kReduceMean) {
     const float count = (float)(deg > 0 ? deg : 1);
@@ -165,14 +119,8 @@ static __global__ __launch_bounds__(256) void spmm_csr_reduce_kernel(const CsrRe
       if constexpr (WITH_ARG) arg[i] = -1;
     }
   }
-  float4_t* out = reinterpret_cast<float4_t*>(a.output + row * F + col0);
-#pragma unroll
-  for (int i = 0; i < V / 4; ++i) out[i] = float4_t{acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]};
-  if constexpr (WITH_ARG) {
-    int4_t* out_arg = reinterpret_cast<int4_t*>(a.arg + row * F + col0);
-#pragma unroll
-    for (int i = 0; i < V / 4; ++i) out_arg[i] = int4_t{arg[4 * i], arg[4 * i + 1], arg[4 * i + 2], arg[4 * i + 3]};
-  }
+  csr_store_piece(a.output + p.row * F + p.col0, acc);
+  if constexpr (WITH_ARG) csr_store_piece(a.arg + p.row * F + p.col0, arg);
 }
 
 // dtype: 0 fp32, 1 fp16, 2 bfloat16; op: 0 max, 1 min, 2 mean.  embedding_dim % (16 / sizeof(T)) == 0 (16-byte row pieces).  Every
@@ -189,7 +137,7 @@ inline int launch_spmm_csr_reduce(const int* indptr, const int* indices, int num
   if (bad_ptr(indptr, 3) || bad_ptr(indices, 3) || bad_ptr(input, 15) || bad_ptr(output, 15) || misaligned(arg, 15)) return kErrBadShape;
   const RowGroupGrid g = row_group_grid(num_rows, embedding_dim / v);
   if (!g.ok) return kErrBadShape;
-  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
+  const dim3 grid = row_group_dim3(g);
   auto go = [&](auto tag) {
     using T = decltype(tag);
     const CsrReduceArgs<T> a{indptr, indices, static_cast<const T*>(input), output, arg, num_rows, embedding_dim, g.lanes, (int)g.per_xcd};
@@ -224,57 +172,32 @@ struct CsrReduceBackwardArgs {
 
 template <int UNROLL = 4>
 static __global__ __launch_bounds__(256) void spmm_csr_reduce_backward_kernel(const CsrReduceBackwardArgs a) {
-  const int L = a.lanes_per_row;
-  const int rows_per_group = 256 / L;
-  const long long group = (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd;
-  const long long col = group * rows_per_group + (int)threadIdx.x / L;
-  if (col >= a.num_cols) return;
-  const int lane = (int)threadIdx.x & (L - 1);
-  const long long f0 = ((long long)blockIdx.y * 64 + lane) * 4;       // this lane's 4 features
-  if (f0 >= a.F) return;
+  const CsrLanePlace p = csr_lane_place<4>(a.lanes_per_row, a.groups_per_xcd, a.num_cols, a.F);   // row: the column c; a lane: 4 features
+  if (!p.work) return;
   float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  int e = a.t_indptr[col];
-  const int end = a.t_indptr[col + 1];
   const long long F = a.F;
-  // the winners of a batch of entries are loaded before the first is compared (the tail: clamped ids, surplus slots skipped); the
-  // gradient's row only where a component matched
-  auto consume = [&](const int4_t won, const int id, const long long offset) {
-    if (won[0] == id || won[1] == id || won[2] == id || won[3] == id) {
-      const float4_t g = *reinterpret_cast<const float4_t*>(a.grad_out + offset);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (won[i] == id) acc[i] += g[i];
-    }
+  // the winners of a batch of entries are loaded before the first is compared; the gradient's row only where a component matched
+  struct Slot {
+    int4_t won;
+    int id;
+    long long offset;
   };
-  for (; end - e >= UNROLL; e += UNROLL) {
-    int4_t won[UNROLL];
-    int id[UNROLL];
-    long long offset[UNROLL];
+  csr_for_each_batch<UNROLL, Slot>(
+      a.t_indptr[p.row], a.t_indptr[p.row + 1],
+      [&](Slot& s, const int ee) {
+        s.offset = (long long)a.t_indices[ee] * F + p.col0;
+        s.id = a.t_order[ee];
+        s.won = *reinterpret_cast<const int4_t*>(a.arg + s.offset);
+      },
+      [&](const Slot& s, int, const bool live) {
+        if (live && (s.won[0] == s.id || s.won[1] == s.id || s.won[2] == s.id || s.won[3] == s.id)) {
+          const float4_t g = *reinterpret_cast<const float4_t*>(a.grad_out + s.offset);
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      offset[u] = (long long)a.t_indices[e + u] * F + f0;
-      id[u] = a.t_order[e + u];
-      won[u] = *reinterpret_cast<const int4_t*>(a.arg + offset[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) consume(won[u], id[u], offset[u]);
-  }
-  if (e < end) {
-    int4_t won[UNROLL];
-    int id[UNROLL];
-    long long offset[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int ee = u < end - e ? e + u : end - 1;
-      offset[u] = (long long)a.t_indices[ee] * F + f0;
-      id[u] = a.t_order[ee];
-      won[u] = *reinterpret_cast<const int4_t*>(a.arg + offset[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-      if (u < end - e) consume(won[u], id[u], offset[u]);
-  }
-  *reinterpret_cast<float4_t*>(a.output + col * F + f0) = float4_t{acc[0], acc[1], acc[2], acc[3]};
+          for (int i = 0; i < 4; ++i)
+            if (s.won[i] == s.id) acc[i] += g[i];
+        }
+      });
+  csr_store_piece(a.output + p.row * F + p.col0, acc);
 }
 
 // embedding_dim % 4 == 0.  Every row of `output` is written (columns without entries: zeros); with nnz == 0 nothing but t_indptr is
@@ -288,7 +211,7 @@ inline int launch_spmm_csr_reduce_backward(const int* t_indptr, const int* t_ind
   if (nnz > 0 && (bad_ptr(t_indices, 3) || bad_ptr(t_order, 3) || bad_ptr(grad_out, 15) || bad_ptr(arg, 15))) return kErrBadShape;
   const RowGroupGrid g = row_group_grid(num_cols, embedding_dim / 4);
   if (!g.ok) return kErrBadShape;
-  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
+  const dim3 grid = row_group_dim3(g);
   const CsrReduceBackwardArgs a{t_indptr, t_indices, t_order, grad_out, arg, output, num_cols, embedding_dim, g.lanes, (int)g.per_xcd};
   hipLaunchKernelGGL((spmm_csr_reduce_backward_kernel<4>), grid, dim3(256), 0, stream, a);
   return hipGetLastError() == hipSuccess ? kOk : kErrLaunch;

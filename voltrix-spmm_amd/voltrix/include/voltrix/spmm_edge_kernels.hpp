@@ -9,13 +9,12 @@
 // composite -- feat[cols] ([nnz, F] materialised), an elementwise op, index_add_ -- moves the gathered rows three times, needs int64
 // row ids per entry, and its float atomics give other bits on every run.
 //
-// Forward shape.  spmm_csr_reduce_kernel's: a group of L = min(64, next_pow2(F / V)) lanes owns one row, grid.y walks slabs of 64
-// pieces, XCD x owns a contiguous range of row groups, batches of UNROLL = 4 entries are issued before the first is consumed, the tail
-// batch reads clamped ids and its surplus slots are skipped.  A lane owns V = 16 / sizeof(TE) consecutive features: one 16-byte load of
-// efeat[id], the matching V elements of input[col] (16 bytes; 32 where TI is fp32 and TE is 16-bit) and V / 4 float4 stores.  fp32
-// additions in CSR order: |out - ref| <= (k + 1) 2^-23 sum |terms| for the k terms of an element (each term one rounding, k - 1
-// additions; holds with and without contraction of the product into the sum).  No LDS, no workspace, no atomics: the same bits on every
-// call.  Every element of `output` is written; a row without entries gives 0.
+// Forward shape.  The row-gather skeleton of csr_row_gather.hpp with UNROLL = 4 (the forward kernel takes the lane's place from it and
+// writes the batch loop out, for one instantiation's registers: see the kernel).  A lane owns V = 16 / sizeof(TE) consecutive
+// features: one 16-byte load of efeat[id], the matching V elements of input[col] (16 bytes; 32 where TI is fp32 and TE is 16-bit) and
+// V / 4 float4 stores.  fp32 additions in CSR order: |out - ref| <= (k + 1) 2^-23 sum |terms| for the k terms of an element (each term
+// one rounding, k - 1 additions; holds with and without contraction of the product into the sum).  No LDS, no workspace, no atomics:
+// the same bits on every call.  Every element of `output` is written; a row without entries gives 0.
 //
 // One kernel for both directions.  `order` (nullable, int32 [nnz]): entry e of the CSR at hand reads efeat[order[e]]; NULL means
 // efeat[e].  The forward passes NULL, the backward on the transposed CSR passes t_order (the branch is wave-uniform).  `self` (op gate
@@ -99,15 +98,9 @@ static __global__ __launch_bounds__(256) void spmm_edge_kernel(const SpmmEdgeArg
   static_assert(OP >= kEdgeMul && OP <= kEdgeGate, "op");
   constexpr int V = 16 / (int)sizeof(TE);
   constexpr int NR = OP == kEdgeCopy ? 1 : V * (int)sizeof(TI) / 16;     // 16-byte registers of input[col] per entry
-  const int L = a.lanes_per_row;
-  const int rows_per_group = 256 / L;
-  // XCD x owns the row groups [x * groups_per_xcd, (x + 1) * groups_per_xcd)
-  const long long group = (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd;
-  const long long row = group * rows_per_group + (int)threadIdx.x / L;
-  if (row >= a.num_rows) return;
-  const int lane = (int)threadIdx.x & (L - 1);
-  const long long col0 = ((long long)blockIdx.y * 64 + lane) * V;     // this lane's V features
-  if (col0 >= a.F) return;
+  const CsrLanePlace p = csr_lane_place<V>(a.lanes_per_row, a.groups_per_xcd, a.num_rows, a.F);   // a lane: V features
+  if (!p.work) return;
+  const long long row = p.row, col0 = p.col0;
   const long long F = a.F;
   int e = a.indptr[row];
   const int end = a.indptr[row + 1];
@@ -147,12 +140,13 @@ static __global__ __launch_bounds__(256) void spmm_edge_kernel(const SpmmEdgeArg
     const long long id = ordered ? a.order[ee] : ee;
     wraw = edge_stream_load(ebase + id * F);
     if constexpr (OP != kEdgeCopy) {
-      const TI* const p = a.input + col0 + (long long)a.indices[ee] * F;
+      const TI* const x = a.input + col0 + (long long)a.indices[ee] * F;
 #pragma unroll
-      for (int j = 0; j < NR; ++j) xraw[j] = reinterpret_cast<const uint4_t*>(p)[j];
+      for (int j = 0; j < NR; ++j) xraw[j] = reinterpret_cast<const uint4_t*>(x)[j];
     }
   };
-  // full batches of UNROLL entries, then one more batch for the tail with clamped ids: every load issued before the first is consumed
+  // csr_for_each_batch's loop and csr_store_piece's store, written out: the (bf16, bf16, add_relu) instantiation sits at 80 VGPRs, the
+  // most that keep 6 waves per SIMD, and either helper costs it two more and a wave (profiles/csr_row_gather/README.md)
   for (; end - e >= UNROLL; e += UNROLL) {
     uint4_t xraw[UNROLL][NR], wraw[UNROLL];
 #pragma unroll
@@ -202,7 +196,7 @@ inline int launch_spmm_edge(const int* indptr, const int* indices, const int* or
   if ((op == kEdgeGate && self == nullptr) || (op != kEdgeCopy && input == nullptr)) return kErrBadShape;
   const RowGroupGrid g = row_group_grid(num_rows, embedding_dim / v);
   if (!g.ok) return kErrBadShape;
-  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
+  const dim3 grid = row_group_dim3(g);
   auto go = [&](auto itag, auto etag) {
     using TI = decltype(itag);
     using TE = decltype(etag);
@@ -249,14 +243,9 @@ template <typename T, int OP, int UNROLL = 4>
 static __global__ __launch_bounds__(256) void spmm_edge_grad_efeat_kernel(const SpmmEdgeGradArgs<T> a) {
   static_assert(OP == kEdgeMul || OP == kEdgeAdd || OP == kEdgeAddRelu, "copy is add");
   constexpr int V = 16 / (int)sizeof(T);
-  const int L = a.lanes_per_row;
-  const int rows_per_group = 256 / L;
-  const long long group = (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd;
-  const long long row = group * rows_per_group + (int)threadIdx.x / L;
-  if (row >= a.num_rows) return;
-  const int lane = (int)threadIdx.x & (L - 1);
-  const long long col0 = ((long long)blockIdx.y * 64 + lane) * V;
-  if (col0 >= a.F) return;
+  const CsrLanePlace p = csr_lane_place<V>(a.lanes_per_row, a.groups_per_xcd, a.num_rows, a.F);
+  if (!p.work) return;
+  const long long row = p.row, col0 = p.col0;
   const long long F = a.F;
   int e = a.indptr[row];
   const int end = a.indptr[row + 1];
@@ -268,47 +257,34 @@ static __global__ __launch_bounds__(256) void spmm_edge_grad_efeat_kernel(const 
 #pragma unroll
     for (int j = 0; j < 4; ++j) g[4 * i + j] = piece[j];
   }
-  auto store = [&](const int ee, const float (&r)[V]) {
-    float4_t* out = reinterpret_cast<float4_t*>(a.output + (long long)ee * F + col0);
-#pragma unroll
-    for (int i = 0; i < V / 4; ++i) out[i] = float4_t{r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]};
-  };
+  float* const out = a.output + col0;
   if constexpr (OP == kEdgeAdd) {
-    for (; e < end; ++e) store(e, g);
+    for (; e < end; ++e) csr_store_piece(out + (long long)e * F, g);
   } else {
-    auto consume = [&](const int ee, const uint4_t xraw, const uint4_t wraw) {
-      float x[V], r[V];
-      csr_piece_as_float<T>(x, xraw);
-      if constexpr (OP == kEdgeMul) {
-#pragma unroll
-        for (int i = 0; i < V; ++i) r[i] = g[i] * x[i];
-      } else {
-        float w[V];
-        csr_piece_as_float<T>(w, wraw);
-#pragma unroll
-        for (int i = 0; i < V; ++i) r[i] = x[i] + w[i] > 0.0f ? g[i] : 0.0f;
-      }
-      store(ee, r);
+    struct Slot {
+      uint4_t xraw, wraw;   // wraw: add_relu
     };
-    auto issue = [&](uint4_t& xraw, uint4_t& wraw, const int ee) {
-      xraw = *reinterpret_cast<const uint4_t*>(a.feat + (long long)a.indices[ee] * F + col0);
-      if constexpr (OP == kEdgeAddRelu) wraw = edge_stream_load(a.efeat + (long long)ee * F + col0);
-    };
-    for (; end - e >= UNROLL; e += UNROLL) {
-      uint4_t xraw[UNROLL], wraw[UNROLL] = {};
+    csr_for_each_batch<UNROLL, Slot>(
+        e, end,
+        [&](Slot& s, const int ee) {
+          s.xraw = *reinterpret_cast<const uint4_t*>(a.feat + (long long)a.indices[ee] * F + col0);
+          if constexpr (OP == kEdgeAddRelu) s.wraw = edge_stream_load(a.efeat + (long long)ee * F + col0);
+        },
+        [&](const Slot& s, const int entry, const bool live) {
+          if (!live) return;
+          float x[V], r[V];
+          csr_piece_as_float<T>(x, s.xraw);
+          if constexpr (OP == kEdgeMul) {
 #pragma unroll
-      for (int u = 0; u < UNROLL; ++u) issue(xraw[u], wraw[u], e + u);
+            for (int i = 0; i < V; ++i) r[i] = g[i] * x[i];
+          } else {
+            float w[V];
+            csr_piece_as_float<T>(w, s.wraw);
 #pragma unroll
-      for (int u = 0; u < UNROLL; ++u) consume(e + u, xraw[u], wraw[u]);
-    }
-    if (e < end) {
-      uint4_t xraw[UNROLL], wraw[UNROLL] = {};
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) issue(xraw[u], wraw[u], u < end - e ? e + u : end - 1);
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u)
-        if (u < end - e) consume(e + u, xraw[u], wraw[u]);
-    }
+            for (int i = 0; i < V; ++i) r[i] = x[i] + w[i] > 0.0f ? g[i] : 0.0f;
+          }
+          csr_store_piece(out + (long long)entry * F, r);
+        });
   }
 }
 
@@ -333,7 +309,7 @@ inline int launch_spmm_edge_grad_efeat(const int* indptr, const int* indices, in
   if (op == kEdgeAddRelu && efeat == nullptr) return kErrBadShape;
   const RowGroupGrid g = row_group_grid(num_rows, embedding_dim / v);
   if (!g.ok) return kErrBadShape;
-  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
+  const dim3 grid = row_group_dim3(g);
   dispatch_feature_type(dtype, [&](auto tag) {
     using T = decltype(tag);
     const SpmmEdgeGradArgs<T> a{indptr, indices, grad_out, static_cast<const T*>(feat), static_cast<const T*>(efeat), output,

@@ -10,14 +10,13 @@
 // Why the scale is per COLUMN and not per row.  A per-row scale would be a second gathered line per entry -- the bytes fp8 saves.  A
 // per-column scale costs nothing in the loop: it leaves the sum and is applied once in the epilogue, 16 multiplies per lane.
 //
-// Aggregation, spmm_csr_rows_fp8_kernel<TO, WEIGHTED, UNROLL>: the geometry of spmm_csr_rows_kernel (spmm_csr_kernels.hpp).  A row of
-// data is F16 bytes, F16 = F rounded up to 16.  A group of L = min(64, next_pow2(F16 / 16)) lanes owns a row, a lane owns 16 features:
-// one 16-byte load per entry, 16 fp32 accumulators; grid.y walks slabs of 64 x 16 = 1024 columns; XCD x owns a contiguous eighth of
-// the row groups (xcd_ranges).  Full batches of UNROLL entries are issued before the first is consumed, then ONE tail batch with clamped
-// ids whose surplus slots are skipped when adding.  The offsets col F16 and row F16 are 64-bit.  Decode: v_cvt_pk_f32_fp8 on the low
-// and the high half of every word, eight per 16 bytes; every decoded value is exact in fp32.  The sum is fp32 in CSR entry order, with
-// values one fused multiply-add per element; it starts from -0.0, the identity of IEEE addition, so that a row's first term arrives
-// with its own sign (a row that gathers one -0 gives -0); a row without entries starts from, and gives, +0.  The epilogue loads the
+// Aggregation, spmm_csr_rows_fp8_kernel<TO, WEIGHTED, UNROLL>: the row-gather skeleton of csr_row_gather.hpp with a piece of V = 16
+// features.  A row of data is F16 bytes, F16 = F rounded up to 16: one 16-byte load per entry, 16 fp32 accumulators; grid.y walks
+// slabs of 64 x 16 = 1024 columns; xcd_ranges = 0 asks for the round-robin order of workgroups.  The offsets col F16 and row F16 are
+// 64-bit.  Decode: v_cvt_pk_f32_fp8 on the low and the high half of every word, eight per 16 bytes; every decoded value is exact in
+// fp32.  The sum is fp32 in CSR entry order, with values one fused multiply-add per element; it starts from -0.0, the identity of IEEE
+// addition, so that a row's first term arrives with its own sign (a row that gathers one -0 gives -0); a row without entries starts
+// from, and gives, +0.  The epilogue loads the
 // lane's 16 scales (four 16-byte loads), multiplies, and stores 64 bytes (fp32) or 32 bytes (fp16 / bf16: the fp32 result rounded to
 // nearest even) in 16-byte pieces.  Every element of the output [num_rows, F16] is written.  No LDS, no atomics, no workspace, the same
 // bits on every call.  |out - ref| <= (k + 2) 2^-23 |scale[f]| sum_e |v_e dec_e| for the k entries of a row against float64 on the
@@ -42,8 +41,7 @@
 #include <cstdint>
 #include <type_traits>
 
-#include "voltrix/launch_geometry.hpp"
-#include "voltrix/spmm_kernels.hpp"
+#include "voltrix/csr_row_gather.hpp"
 
 #ifndef VOLTRIX_SPMM_FP8_UNROLL
 #define VOLTRIX_SPMM_FP8_UNROLL 4         // entries in flight per lane: 4, or 8 (the experiment's other build)
@@ -104,16 +102,10 @@ __device__ __forceinline__ unsigned bf16_bits_rne(const float v) {
 
 template <typename TO, bool WEIGHTED, int UNROLL = kFp8Unroll>
 static __global__ __launch_bounds__(256) void spmm_csr_rows_fp8_kernel(const Fp8CsrArgs<TO> a) {
-  const int L = a.lanes_per_row;
-  const int rows_per_group = 256 / L;
-  const long long group = a.xcd_ranges ? (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd
-                                       : (long long)blockIdx.x;
-  const long long row = group * rows_per_group + (int)threadIdx.x / L;
-  if (row >= a.num_rows) return;
-  const int lane = (int)threadIdx.x & (L - 1);
-  const long long col0 = ((long long)blockIdx.y * 64 + lane) * 16;    // this lane's 16 bytes of every gathered row
-  if (col0 >= a.F16) return;
-  int e = a.indptr[row];
+  const CsrLanePlace p = csr_lane_place<16>(a.lanes_per_row, a.groups_per_xcd, a.num_rows, a.F16, a.xcd_ranges != 0);
+  if (!p.work) return;
+  const long long row = p.row, col0 = p.col0;
+  const int e = a.indptr[row];
   const int end = a.indptr[row + 1];
   // -0.0 is the identity of IEEE addition (x + -0 = x for every x, -0 included): the first term keeps its sign.  No entries: +0
   const float start = e < end ? -0.0f : 0.0f;
@@ -122,32 +114,19 @@ static __global__ __launch_bounds__(256) void spmm_csr_rows_fp8_kernel(const Fp8
   for (int i = 0; i < 16; ++i) acc[i] = start;
   const uint8_t* const base = a.input + col0;
   const long long F16 = a.F16;
-  // full batches of UNROLL entries, then ONE more batch for the tail with clamped ids: every load of a batch is issued, unconditionally,
-  // before the first is consumed (spmm_csr_rows_kernel has the measurements behind this shape)
-  for (; end - e >= UNROLL; e += UNROLL) {
-    uint4_t raw[UNROLL];
-    float v[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[e + u] * F16);
-      v[u] = WEIGHTED ? a.values[e + u] : 1.0f;
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) fp8_accumulate<WEIGHTED>(acc, raw[u], v[u]);
-  }
-  if (e < end) {
-    uint4_t raw[UNROLL];
-    float v[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int ee = u < end - e ? e + u : end - 1;
-      raw[u] = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F16);
-      v[u] = WEIGHTED ? a.values[ee] : 1.0f;
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-      if (u < end - e) fp8_accumulate<WEIGHTED>(acc, raw[u], v[u]);
-  }
+  struct Slot {
+    uint4_t raw;
+    float v;
+  };
+  csr_for_each_batch<UNROLL, Slot>(
+      e, end,
+      [&](Slot& s, const int ee) {
+        s.raw = *reinterpret_cast<const uint4_t*>(base + (long long)a.indices[ee] * F16);
+        s.v = WEIGHTED ? a.values[ee] : 1.0f;
+      },
+      [&](const Slot& s, int, const bool live) {
+        if (live) fp8_accumulate<WEIGHTED>(acc, s.raw, s.v);
+      });
   const float4_t* const sc = reinterpret_cast<const float4_t*>(a.scale + col0);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -157,9 +136,7 @@ static __global__ __launch_bounds__(256) void spmm_csr_rows_fp8_kernel(const Fp8
   }
   TO* const out = a.output + row * F16 + col0;
   if constexpr (std::is_same<TO, float>::value) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      reinterpret_cast<float4_t*>(out)[i] = float4_t{acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]};
+    csr_store_piece(out, acc);
   } else if constexpr (std::is_same<TO, _Float16>::value) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -201,7 +178,7 @@ inline int launch_spmm_fp8_csr(const int* indptr, const int* indices, const floa
     return kErrBadShape;
   const RowGroupGrid g = row_group_grid(num_rows, embedding_dim16 / 16);
   if (!g.ok) return kErrBadShape;
-  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
+  const dim3 grid = row_group_dim3(g);
   dispatch_feature_type(out_dtype, [&](auto tag) {
     using TO = decltype(tag);
     const Fp8CsrArgs<TO> a{indptr, indices, values, static_cast<const uint8_t*>(input), scale, static_cast<TO*>(output), num_rows,
@@ -259,21 +236,10 @@ static __global__ __launch_bounds__(256) void quantize_fp8_rows_kernel(const Fp8
       for (int i = 0; i < 16 / V; ++i) raw[i] = reinterpret_cast<const uint4_t*>(in)[i];
 #pragma unroll
       for (int i = 0; i < 16 / V; ++i) {
-        if constexpr (std::is_same<T, float>::value) {
-          const float4_t f = __builtin_bit_cast(float4_t, raw[i]);     // the whole vector: a bit_cast of one ELEMENT reads element 0
+        float part[V];
+        csr_piece_as_float<T>(part, raw[i]);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) x[4 * i + j] = f[j];
-        } else if constexpr (std::is_same<T, _Float16>::value) {
-          const half8_t h = __builtin_bit_cast(half8_t, raw[i]);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) x[8 * i + j] = (float)h[j];
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            x[8 * i + 2 * j] = __builtin_bit_cast(float, raw[i][j] << 16);
-            x[8 * i + 2 * j + 1] = __builtin_bit_cast(float, raw[i][j] & 0xffff0000u);
-          }
-        }
+        for (int j = 0; j < V; ++j) x[V * i + j] = part[j];
       }
     } else {
 #pragma unroll

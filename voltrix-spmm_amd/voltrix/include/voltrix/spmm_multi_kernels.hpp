@@ -237,7 +237,7 @@ inline int launch_spmm_multi(const int* indptr, const int* indices, int num_rows
     return kErrBadShape;
   const RowGroupGrid g = row_group_grid(num_rows, embedding_dim / v);
   if (!g.ok) return kErrBadShape;
-  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
+  const dim3 grid = row_group_dim3(g);
   const bool m2 = slots[kMultiVar] >= 0 || slots[kMultiStd] >= 0;
   const int select = argmax != nullptr || argmin != nullptr ? kMultiSelectArgs
                      : slots[kMultiMax] >= 0 || slots[kMultiMin] >= 0 ? kMultiSelectValues : kMultiSelectNone;
@@ -386,7 +386,7 @@ inline int launch_spmm_multi_backward(const int* t_indptr, const int* t_indices,
   if (num_entries > 0 && (t_indices == nullptr || ((has_max || has_min) && t_order == nullptr))) return kErrBadShape;
   const RowGroupGrid g = row_group_grid(num_cols, embedding_dim / 4);
   if (!g.ok) return kErrBadShape;
-  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
+  const dim3 grid = row_group_dim3(g);
   const SpmmMultiBackwardArgs a{t_indptr, t_indices, t_order, x, u, w, mean, g_max, argmax, g_min, argmin, output, mean_ld,
                                 num_cols, embedding_dim, g.lanes, (int)g.per_xcd};
   const int variant = (has_u ? 4 : 0) | (has_w ? 2 : 0) | (has_max || has_min ? 1 : 0);

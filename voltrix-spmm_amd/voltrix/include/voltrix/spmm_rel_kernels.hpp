@@ -17,9 +17,9 @@
 // propagate as the arithmetic does.  |out - ref| <= (k + 2) 2^-23 sum |terms| for the k entries of a row; dF: (k B + 2); dC: (m_r + F +
 // 2) for the m_r entries of type r.
 //
-// Geometry (spmm_edge_kernels.hpp, spmm_csr_heads_kernels.hpp): a group of L = min(64, next_pow2(F / V)) lanes owns one row, grid.y
-// walks slabs of 64 pieces, XCD x owns a contiguous range of row groups, batches of UNROLL = 4 entries are issued before the first is
-// consumed, the tail batch reads clamped ids and its surplus slots are skipped.  Offsets row B F, col F and e B_pad are 64-bit.
+// Geometry: the lane's place of csr_row_gather.hpp.  The loops are these kernels' own -- a single loop whose every batch clamps its
+// ids to the row's last entry, every load issued before the first is consumed, surplus slots skipped -- with UNROLL = 4.  Offsets
+// row B F, col F and e B_pad are 64-bit.
 //
 // Forward, spmm_rel_kernel<T, BT>.  A lane owns V = 16 / sizeof(T) features and BT x V fp32 accumulators for a tile of BT bases.  Per
 // entry: one 16-byte load of feat[col], one etype read (and the weight read), and BT / 4 16-byte loads of that type's row of coef.
@@ -112,15 +112,9 @@ static __global__ __launch_bounds__(256) void spmm_rel_kernel(const SpmmRelArgs<
   for (int i = (int)threadIdx.x; i < a.table_pieces; i += 256) table[i] = reinterpret_cast<const float4_t*>(a.coef)[i];
   __syncthreads();
 #endif
-  const int L = a.lanes_per_row;
-  const int rows_per_group = 256 / L;
-  // XCD x owns the row groups [x * groups_per_xcd, (x + 1) * groups_per_xcd)
-  const long long group = (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd;
-  const long long row = group * rows_per_group + (int)threadIdx.x / L;
-  if (row >= a.num_rows) return;
-  const int lane = (int)threadIdx.x & (L - 1);
-  const long long col0 = ((long long)blockIdx.y * 64 + lane) * V;     // this lane's V features
-  if (col0 >= a.F) return;
+  const CsrLanePlace p = csr_lane_place<V>(a.lanes_per_row, a.groups_per_xcd, a.num_rows, a.F);   // a lane: V features
+  if (!p.work) return;
+  const long long row = p.row, col0 = p.col0;
   const long long F = a.F;
   const int b0 = (int)blockIdx.z * BT;
   const int live = a.B - b0 < BT ? a.B - b0 : BT;                    // bases of this tile; wave-uniform
@@ -178,9 +172,7 @@ static __global__ __launch_bounds__(256) void spmm_rel_kernel(const SpmmRelArgs<
 #pragma unroll
   for (int j = 0; j < BT; ++j) {
     if (j < live) {
-      float4_t* o = reinterpret_cast<float4_t*>(out + j * F);
-#pragma unroll
-      for (int i = 0; i < V / 4; ++i) o[i] = float4_t{acc[j][4 * i], acc[j][4 * i + 1], acc[j][4 * i + 2], acc[j][4 * i + 3]};
+      csr_store_piece(out + j * F, acc[j]);
     }
   }
 }
@@ -211,7 +203,7 @@ inline int launch_spmm_rel(const int* indptr, const int* indices, const int* ety
   const int table_pieces = num_types * (rel_padded_bases(num_bases) / 4);
   if (VOLTRIX_SPMM_REL_COEF_LDS && table_pieces > kRelLdsFloats / 4) return kErrBadShape;   // the experiment's build: the table must fit
   const int tile = num_bases <= 4 ? 4 : kRelBasisTile;
-  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs, (unsigned)((num_bases + tile - 1) / tile));
+  const dim3 grid = row_group_dim3(g, (unsigned)((num_bases + tile - 1) / tile));
   dispatch_feature_type(dtype, [&](auto tag) {
     using T = decltype(tag);
     const SpmmRelArgs<T> a{indptr, indices, etype, weight, static_cast<const T*>(input), coef, output, num_rows, embedding_dim,
@@ -245,14 +237,9 @@ static __global__ __launch_bounds__(256) void spmm_rel_contract_kernel(const Spm
   static_assert(BT % 4 == 0, "whole 16-byte pieces of a row of coef");
   constexpr int V = 4;
   constexpr int NC = BT / 4;
-  const int L = a.lanes_per_row;
-  const int rows_per_group = 256 / L;
-  const long long group = (long long)(blockIdx.x % kNumXcd) * a.groups_per_xcd + blockIdx.x / kNumXcd;
-  const long long row = group * rows_per_group + (int)threadIdx.x / L;
-  if (row >= a.num_rows) return;
-  const int lane = (int)threadIdx.x & (L - 1);
-  const long long col0 = ((long long)blockIdx.y * 64 + lane) * V;
-  if (col0 >= a.F) return;
+  const CsrLanePlace p = csr_lane_place<V>(a.lanes_per_row, a.groups_per_xcd, a.num_rows, a.F);
+  if (!p.work) return;
+  const long long row = p.row, col0 = p.col0;
   const long long F = a.F;
   const long long BF = (long long)a.B * F;
   int e = a.indptr[row];
@@ -298,7 +285,7 @@ static __global__ __launch_bounds__(256) void spmm_rel_contract_kernel(const Spm
       }
     }
   }
-  *reinterpret_cast<float4_t*>(a.output + row * F + col0) = float4_t{acc[0], acc[1], acc[2], acc[3]};
+  csr_store_piece(a.output + row * F + col0, acc);
 }
 
 // The CSR at hand is the TRANSPOSE of the forward's pattern: num_rows = the forward's num_cols.  embedding_dim % 4 == 0; the limits of
@@ -315,7 +302,7 @@ inline int launch_spmm_rel_contract(const int* indptr, const int* indices, const
     return kErrBadShape;
   const RowGroupGrid g = row_group_grid(num_rows, embedding_dim / 4);
   if (!g.ok) return kErrBadShape;
-  const dim3 grid((unsigned)(g.per_xcd * kNumXcd), (unsigned)g.slabs);
+  const dim3 grid = row_group_dim3(g);
   const SpmmRelContractArgs a{indptr, indices, order, etype, weight, grad_out, coef, output, num_rows, embedding_dim,
                               num_bases, rel_padded_bases(num_bases), g.lanes, (int)g.per_xcd};
   hipLaunchKernelGGL((spmm_rel_contract_kernel<kRelContractTile>), grid, dim3(256), 0, stream, a);
