@@ -230,6 +230,8 @@ def sample_edge_batch(indptr: torch.Tensor, indices: torch.Tensor, entries: torc
         slots = torch.where(keep, ends - 1, torch.full_like(ends, total))       # the exhausted slots all go to one spare element
         p_indices = torch.empty(total + 1, dtype=torch.int32, device=dev).scatter_(0, slots, candidates.view(-1))[:total].contiguous()
     labels = torch.zeros(total, dtype=torch.float32, device=dev)
-    labels[p_indptr[:-1].long()] = 1.0                        # every row has its positive, so the row starts are distinct entries
+    # every row has its positive, so the row starts are distinct entries.  index_fill_ takes the 1 as a launch argument;
+    # ``labels[ids] = 1.0`` builds it on the host and copies it over, which is one more host synchronisation
+    labels.index_fill_(0, p_indptr[:-1].long(), 1.0)
     pairs = CsrPattern(p_indptr, p_indices, count, node_ids.numel())
     return EdgeBatch(blocks, node_ids, pairs, labels, src_local, num_exhausted)
