@@ -449,8 +449,8 @@ def test_csr_kernel_with_values_matches_the_oracle(cuda_device, dtype, width, mo
 
 def test_exact_fp32_weighted_product_and_the_measured_path(cuda_device, monkeypatch):
     """VOLTRIX_FP32_MODE=exact on a weighted handle used to be refused (16-bit planes); it now runs the CSR kernel with values.  Without
-    the flag a handle of short windows times both paths once per (width, dtype) and remembers the choice; either is within the plane
-    path's bound."""
+    the flag a handle of short windows times both paths once per (width, dtype) and remembers the choice; the result is within the bound
+    of the path that was recorded (and, as before, either within the plane path's loose one)."""
     import synth_graphs
 
     indptr, indices, _ = synth_graphs.generate("com_amazon_like", scale=0.2)
@@ -470,6 +470,13 @@ def test_exact_fp32_weighted_product_and_the_measured_path(cuda_device, monkeypa
         out = voltrix.spmm_weighted(h, operand)
         key = (64, str(operand.dtype))
         assert h.path_choice[key] in ("csr", "plane")
+        # each path against its own bound, keyed on the recorded choice (tests/test_gpu_measured_choices.py forces both)
+        if h.path_choice[key] == "csr":     # fp32 values, the rows as given, one fused multiply-add per element
+            same = _oracle(indptr.numpy(), indices.numpy(), values, operand.cpu().float(), n, n)
+            same_scale = _oracle(indptr.numpy(), indices.numpy(), values.abs(), operand.cpu().float().abs(), n, n)
+            assert ((out.cpu().double() - same).abs() <= (deg + 1) * 2.0 ** -23 * same_scale + 1e-30).all()
+        else:                               # values and B at 16 bits: test_weighted_spmm_matches_the_oracle's bound
+            assert ((out.cpu().double() - ref).abs() <= (2.0 ** -10 + (deg + 1) * 2.0 ** -23) * scale + 1e-6).all()
         assert ((out.cpu().double() - ref).abs() <= (2.0 ** -9 + deg * 2.0 ** -23) * scale + 1e-6).all()
         assert torch.equal(out, voltrix.spmm_weighted(h, operand))                      # the remembered choice: the same kernel again
     monkeypatch.setenv("VOLTRIX_CSR_PATH", "0")

@@ -55,8 +55,9 @@ def _drop(key) -> None:
         _CSR.pop(key, None)
 
 
-# ---- CSR side-car (round 6): handles of short windows keep the device CSR they were built from, for the CSR row-gather kernel
-# ---- (spmm_csr_kernels.hpp); voltrix.spmm times it once per (width, dtype) against the block-format path and keeps the faster
+# ---- CSR side-car (round 6): handles of short windows keep a copy of their own of the device CSR they were built from, for the CSR
+# ---- row-gather kernel (spmm_csr_kernels.hpp); voltrix.spmm times it once per (width, dtype) against the block-format path and keeps
+# ---- the faster -- where both read the same operand (spmm/spmm.py::_csr_choice)
 _CSR = {}
 
 

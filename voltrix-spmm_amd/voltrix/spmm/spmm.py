@@ -49,7 +49,8 @@ def csr_preprocess(indptr: torch.Tensor, indices: torch.Tensor, num_nodes: int, 
     assert indptr.numel() == num_nodes + 1
 
     if preprocess_mode()[0] != "reference":
-        return csr_preprocess_device(indptr.contiguous().cuda(), indices.contiguous().cuda(), num_nodes, num_cols)
+        # the device copies made here are nobody else's: the CSR side-car keeps them as they are
+        return csr_preprocess_device(indptr.contiguous().cuda(), indices.contiguous().cuda(), num_nodes, num_cols, _private=True)
 
     num_edges = indices.numel()
     num_row_windows = math.ceil(num_nodes / BLK_H)
@@ -86,13 +87,16 @@ def preprocess_mode():
     return mode, (path or None)
 
 
-def csr_preprocess_device(indptr: torch.Tensor, indices: torch.Tensor, num_nodes: int, num_cols: int = None):
+def csr_preprocess_device(indptr: torch.Tensor, indices: torch.Tensor, num_nodes: int, num_cols: int = None, _private: bool = False):
     """``csr_preprocess`` for a CSR that already lives on the GPU (extension: the reference takes CPU tensors only; graph
-    pipelines and the row-sharded operator build their shards on the device).  Same handle, same side-car policy.  Handles of
-    short windows keep ``indptr`` / ``indices`` THEMSELVES as their CSR side-car (no copy: 4 (nnz + N) bytes saved): do not write into
-    them while the handle is in use -- the CSR kernel would see the change, the block format would not."""
+    pipelines and the row-sharded operator build their shards on the device).  Same handle, same side-car policy.  The handle
+    OWNS what it computes from: handles of short windows keep a COPY of ``indptr`` / ``indices`` as their CSR side-car (4 (nnz + N)
+    bytes, at most 256 MiB by ``CSR_MAX_EDGES``; made only when the side-car is attached), so the caller may reuse its buffers --
+    the CSR kernel and the block format keep computing the matrix the handle was built from.  ``_private`` (internal): the two
+    tensors are the caller's own temporaries and are kept without a copy."""
     assert indptr.is_cuda and indptr.dtype == torch.int32 and indices.is_cuda and indices.dtype == torch.int32
     assert indptr.numel() == num_nodes + 1
+    given = (indptr.data_ptr(), indices.data_ptr())
     indptr, indices = indptr.contiguous(), indices.contiguous()
     path = preprocess_mode()[1]
     pointer1, hspa_packed, hind, _ = csr_fused_preprocess_kernel(indptr, indices, num_nodes, num_cols, path=path)
@@ -106,7 +110,9 @@ def csr_preprocess_device(indptr: torch.Tensor, indices: torch.Tensor, num_nodes
     # and re-packed tuples of the handle keep it, it dies with the storage
     sidecar.register(hspa_packed, two)
     if two is None:
-        _attach_csr_side_car(hspa_packed, indptr, indices, num_nodes, num_cols)
+        # ``.contiguous()`` above already made a private copy of a strided argument
+        copy = tuple(not _private and t.data_ptr() == p for t, p in zip((indptr, indices), given))
+        _attach_csr_side_car(hspa_packed, indptr, indices, num_nodes, num_cols, copy)
     return pointer1, hspa_packed, hind
 
 
@@ -119,13 +125,15 @@ CSR_MAX_EDGES = 1 << 26
 
 def csr_path_mode() -> str:
     """``VOLTRIX_CSR_PATH``: ``auto`` (default: handles of short windows keep their CSR; the first ``voltrix.spmm`` per (width, dtype)
-    times the CSR row-gather kernel against the block-format path -- three calls each, one host sync -- and keeps the faster) |
-    ``1`` (always the CSR kernel where a CSR side-car exists: tests) | ``0`` (never)."""
+    times the CSR row-gather kernel against the block-format path -- three calls each, one host sync -- and keeps the faster; only
+    where both read the same operand: not for fp32 features that the handle's class rounds to fp16, ``_csr_choice``) |
+    ``1`` (always the CSR kernel where a CSR side-car exists, fp32 rows as they are whatever the class: tests) | ``0`` (never)."""
     v = os.getenv(CSR_PATH_FLAG, "auto")
     return "off" if v in ("0", "off") else ("on" if v in ("1", "on") else "auto")
 
 
-def _attach_csr_side_car(hspa_packed, indptr, indices, num_nodes, num_cols) -> None:
+def _attach_csr_side_car(hspa_packed, indptr, indices, num_nodes, num_cols, copy=(True, True)) -> None:
+    """``copy``: whether ``indptr`` / ``indices`` are somebody else's buffers (the side-car then keeps clones of them)."""
     if csr_path_mode() == "off" or num_nodes == 0 or indices.numel() == 0 or indices.numel() > CSR_MAX_EDGES:
         return
     windows = (num_nodes + 15) // 16
@@ -139,6 +147,7 @@ def _attach_csr_side_car(hspa_packed, indptr, indices, num_nodes, num_cols) -> N
     distinct = torch.unique(key).numel()
     if int(lo) < 0 or int(hi) >= cols or distinct != indices.numel():      # ids outside the universe / duplicates: block format only
         return
+    indptr, indices = (t.clone() if c else t for t, c in zip((indptr, indices), copy))
     sidecar.register_csr(hspa_packed, sidecar.CsrSideCar(indptr, indices, num_nodes, cols))
 
 
@@ -282,16 +291,32 @@ def spmm(blk_offsets: torch.Tensor, hspa_packed: torch.Tensor, hind: torch.Tenso
     operand (their kernels have no fp32 tiles).  Every output row is written, including the
     ``num_nodes % 16`` tail the reference skips.  When ``csr_preprocess`` attached the two-level side-car to this very
     ``hspa_packed`` tensor, the 16-bit-operand product runs in that form (same result up to fp32 summation order).
+
+    CONTRACT: how B is rounded is a function of (handle, width, dtype, environment) -- never of a clock, of an entry in the tuned
+    store or of stream-capture state.  The measured choices (``_csr_choice``: CSR row-gather kernel or block format;
+    ``VOLTRIX_HYBRID=tune``: window or two-level format) only pick between candidates that read the SAME operand and differ by
+    fp32 summation order: for fp32 features the class (``fp32_mode``) is fixed first, and the CSR kernel, which sums the fp32 rows
+    as they are, competes only in class "exact".
     """
-    num_feats = feat.shape[1]
     known, two, csr = sidecar.lookup_both(hspa_packed)
-    if _CSR_DEPTH[0]:
-        csr = None
+    # class first, clock second: what fp32 rows become is decided from (handle, width, environment) BEFORE any measured choice, and
+    # a measured choice only picks between candidates of that class (they differ by fp32 summation order, never by a rounding of B)
+    klass = fp32_mode(hspa_packed, num_nodes, feat.shape[1]) if feat.dtype == torch.float32 else None
+
+    def block():
+        return _spmm_block(blk_offsets, hspa_packed, hind, num_nodes, num_edges, feat, klass, known, two)
+
     if csr is not None and csr.num_rows == num_nodes and feat.is_cuda and feat.dim() == 2:
-        if _csr_choice(csr, blk_offsets, hspa_packed, hind, num_nodes, num_edges, feat) == "csr":
+        if _csr_choice(csr, hspa_packed, feat, klass, block) == "csr":
             return _spmm_csr(csr, feat)
-    operand, out_scale, padded, exact = _operand(feat, fp32_mode(hspa_packed, num_nodes, feat.shape[1])
-                                                 if feat.dtype == torch.float32 else None)
+    return block()
+
+
+def _spmm_block(blk_offsets, hspa_packed, hind, num_nodes, num_edges, feat, klass, known, two):
+    """The block-format paths of ``spmm`` (window format, two-level side-car) for an operand of class ``klass`` ("exact" | "fp16" for
+    fp32 features, None for 16-bit ones).  ``_csr_choice`` times this very function: the CSR side-car is not looked at here."""
+    num_feats = feat.shape[1]
+    operand, out_scale, padded, exact = _operand(feat, klass)
     output = torch.empty((num_nodes, padded), dtype=torch.float32, device=feat.device)
     mode = hybrid.hybrid_mode()
     if not known and mode == "auto" and not exact:
@@ -322,8 +347,23 @@ def spmm(blk_offsets: torch.Tensor, hspa_packed: torch.Tensor, hind: torch.Tenso
     return output if padded == num_feats else output[:, :num_feats].contiguous()
 
 
-_CSR_DEPTH = [0]      # > 0 while _csr_choice times the block-format path through voltrix.spmm itself
 CSR_MIN_GAIN = 0.03   # the CSR kernel must beat the block-format path by this much to be taken
+
+
+def _time_ms(fn, warmup: int = 2, reps: int = 3, label: str = "") -> float:
+    """Milliseconds per call of ``fn()`` on the current stream: ``warmup`` calls (a candidate's own first-call tuning included), then
+    ``reps`` calls between two events; one host sync.  THE stopwatch of every measured choice of the operators (``_csr_choice``,
+    ``_choose_format``, ``weighted._weighted_path``): they reach it through this module's attribute, so one replacement scripts all
+    three.  ``label`` names the candidate (for such a script; the measurement ignores it)."""
+    for _ in range(warmup):
+        fn()
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(reps):
+        fn()
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / reps
 
 
 def _spmm_csr(csr, feat: torch.Tensor) -> torch.Tensor:
@@ -337,24 +377,26 @@ def _spmm_csr(csr, feat: torch.Tensor) -> torch.Tensor:
     return output if padded == num_feats else output[:, :num_feats].contiguous()
 
 
-def _csr_choice(csr, blk_offsets, hspa_packed, hind, num_nodes, num_edges, feat) -> str:
-    """"csr" | "block" for this (handle, width, dtype): decided once.  ``VOLTRIX_CSR_PATH=1`` forces "csr".  Otherwise the first call
-    times both paths (one warm-up -- the block path's own first-call tuning included -- then three calls each; one host sync; not
-    inside a stream capture, where the block path is taken) and the choice is remembered on the side-car and, for tagged handles,
-    persisted next to the tile choices."""
+def _csr_choice(csr, hspa_packed, feat, klass, block) -> str:
+    """"csr" | "block" for this (handle, width, dtype) and the operand class ``klass`` (``fp32_mode`` for fp32 features, None for 16-bit
+    ones); ``block()`` runs the block-format path of that class.  The CSR kernel sums the rows AS THEY ARE, so it is a candidate only
+    where the block path reads the same operand: 16-bit features, and fp32 features of class "exact".  In class "fp16" (B rounded to
+    fp16 behind one scale) it is none -- whatever a clock, a remembered or a stored choice says -- unless ``VOLTRIX_CSR_PATH=1`` pins
+    the kernel.  Among candidates the first call times both (``_time_ms``; not inside a stream capture, where the block path is taken
+    and nothing is recorded); the choice is remembered on the side-car and, for tagged handles, persisted next to the tile choices
+    under a key that carries the class."""
     mode = csr_path_mode()
     if mode == "off" or feat.dtype not in (torch.float32, torch.float16, torch.bfloat16) or feat.shape[0] < csr.num_cols:
         return "block"
     if mode == "on":
         return "csr"
-    # pinned numerics / pinned kernels stay pinned: VOLTRIX_FP32_MODE=fp16 asks for the scaled 16-bit operand (this kernel would
-    # compute the exact fp32 product), VOLTRIX_TUNE_SPACE=none / stream name the block-format kernel to run (tests, experiments)
+    # pinned kernels stay pinned: VOLTRIX_TUNE_SPACE=none / stream name the block-format kernel to run (tests, experiments)
     from ..jit_kernels.spmm import tune_space_mode
 
-    if (feat.dtype == torch.float32 and os.getenv(FP32_MODE_FLAG, "auto") == "fp16") or tune_space_mode() in ("none", "stream"):
+    if klass == "fp16" or tune_space_mode() in ("none", "stream"):
         return "block"
     key = (int(feat.shape[1]), str(feat.dtype))
-    if key in csr.choice:
+    if csr.choice.get(key) in ("csr", "block"):
         return csr.choice[key]
     if torch.cuda.is_current_stream_capturing():
         return "block"
@@ -363,28 +405,14 @@ def _csr_choice(csr, blk_offsets, hspa_packed, hind, num_nodes, num_edges, feat)
 
     tagged = isinstance(getattr(hspa_packed, "hash_tag", None), str)
     signature = ("spmm_csr_path", f"{{'device': '{torch.cuda.get_device_name(hspa_packed.device)}', 'dtype': '{key[1]}', "
-                                  f"'embedding_dim': {key[0]}, 'feature_hash': '{feature_hash(hspa_packed) if tagged else ''}'}}")
+                                  f"'embedding_dim': {key[0]}, 'feature_hash': '{feature_hash(hspa_packed) if tagged else ''}', "
+                                  f"'operand': '{klass or 'as given'}'}}")
     if tagged:
         stored = jit_tuner._load_store().get(f"{signature[0]}|{signature[1]}")
         if stored in ("csr", "block"):
             csr.choice[key] = stored
             return stored
-    times = {}
-    _CSR_DEPTH[0] += 1
-    try:
-        for name, fn in (("block", lambda: spmm(blk_offsets, hspa_packed, hind, num_nodes, num_edges, feat)),
-                         ("csr", lambda: _spmm_csr(csr, feat))):
-            fn()
-            fn()
-            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            start.record()
-            for _ in range(3):
-                fn()
-            end.record()
-            end.synchronize()
-            times[name] = start.elapsed_time(end) / 3
-    finally:
-        _CSR_DEPTH[0] -= 1
+    times = {"block": _time_ms(block, label="block"), "csr": _time_ms(lambda: _spmm_csr(csr, feat), label="csr")}
     best = "csr" if times["csr"] < (1.0 - CSR_MIN_GAIN) * times["block"] else "block"
     if os.getenv("VOLTRIX_PRINT_AUTO_TUNE") or os.getenv("VOLTRIX_JIT_DEBUG"):
         print(f"voltrix.spmm path for width {key[0]} {key[1]}: {times} -> {best}")
@@ -408,16 +436,8 @@ def _choose_format(hspa_packed, key, window, two_level) -> str:
     stored = jit_tuner._load_store().get(f"{signature[0]}|{signature[1]}")
     if stored in ("two-level", "window") and hasattr(hspa_packed, "hash_tag"):
         return stored
-    times = {}
-    for name, fn in (("window", window), ("two-level", two_level)):
-        fn()   # tile / schedule sweep of the first call
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(3):
-            fn()
-        end.record()
-        end.synchronize()
-        times[name] = start.elapsed_time(end)
+    # one warm-up each: the tile / schedule sweep of the first call
+    times = {"window": _time_ms(window, warmup=1, label="window"), "two-level": _time_ms(two_level, warmup=1, label="two-level")}
     best = min(times, key=times.get)
     if os.getenv("VOLTRIX_PRINT_AUTO_TUNE") or os.getenv("VOLTRIX_JIT_DEBUG"):
         print(f"voltrix.spmm format for width {key[0]} {key[1]}: {times} -> {best}")

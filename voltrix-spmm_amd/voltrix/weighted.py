@@ -349,9 +349,11 @@ def spmm_weighted(handle: WeightedHandle, feat: torch.Tensor, hash_tag: str = No
     Separable handles only (round 6): ``prescaled=True`` -- the caller has already multiplied row j of ``feat`` by
     ``handle.col_scale[j]`` (e.g. in the epilogue of the GEMM that produced it): no pass over B here; ``postscale=False`` -- return
     ``A (diag(c) feat)`` WITHOUT the row factors, for callers that fold ``handle.row_scale`` into what consumes C (bias, activation):
-    no pass over C here.  With both the weighted product costs exactly the binary one."""
-    from .spmm.spmm import _operand
+    no pass over C here.  With both the weighted product costs exactly the binary one.
 
+    General handles of short windows: the rounding CLASS of the result is keyed on the choice recorded in ``handle.path_choice``
+    (``_weighted_path``) -- "csr": fp32 values times the rows as given, (deg + 1) 2^-23 (|A| |B|); "plane": values and an fp32 ``feat``
+    rounded to 16 bits.  The two kernels differ by that inherently; pin ``VOLTRIX_CSR_PATH`` where it matters."""
     assert isinstance(handle, WeightedHandle)
     if hash_tag is not None and getattr(handle.hspa_packed, "hash_tag", None) is None:
         handle.hspa_packed.hash_tag = hash_tag
@@ -362,6 +364,14 @@ def spmm_weighted(handle: WeightedHandle, feat: torch.Tensor, hash_tag: str = No
             return _spmm_separable(handle, feat, prescaled, postscale)
     if not handle.separable and _weighted_path(handle, feat) == "csr":
         return _spmm_weighted_csr(handle, feat)
+    return _spmm_weighted_plane(handle, feat)
+
+
+def _spmm_weighted_plane(handle: WeightedHandle, feat: torch.Tensor) -> torch.Tensor:
+    """``csr(values) @ feat`` through the value plane (WEIGHTED tiles of the window kernel): values and an fp32 ``feat`` at 16 bits."""
+    from .spmm.spmm import _operand
+
+    num_feats = feat.shape[1]
     operand, out_scale, padded, exact = _operand(feat)
     assert not exact, ("the value planes are 16-bit: VOLTRIX_FP32_MODE=exact needs the CSR kernel with values, i.e. a general handle that "
                        "kept its CSR and values (csr_preprocess_weighted(..., separable=False), at most KEEP_CSR_MAX_EDGES edges)")
@@ -422,18 +432,10 @@ def _weighted_path(handle: WeightedHandle, feat: torch.Tensor) -> str:
         return handle.path_choice[key]
     if torch.cuda.is_current_stream_capturing():
         return "plane"
-    handle.path_choice[key] = "plane"          # what the timed calls below take
-    times = {}
-    for name, fn in (("plane", lambda: spmm_weighted(handle, feat)), ("csr", lambda: _spmm_weighted_csr(handle, feat))):
-        fn()
-        fn()
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(3):
-            fn()
-        end.record()
-        end.synchronize()
-        times[name] = start.elapsed_time(end) / 3
+    from .spmm.spmm import _time_ms             # the one stopwatch of the measured choices, looked up at call time
+
+    times = {"plane": _time_ms(lambda: _spmm_weighted_plane(handle, feat), label="plane"),
+             "csr": _time_ms(lambda: _spmm_weighted_csr(handle, feat), label="csr")}
     best = "csr" if times["csr"] < (1.0 - WEIGHTED_CSR_MIN_GAIN) * times["plane"] else "plane"
     if os.getenv("VOLTRIX_PRINT_AUTO_TUNE") or os.getenv("VOLTRIX_JIT_DEBUG"):
         print(f"voltrix.spmm_weighted path for width {key[0]} {key[1]}: {times} -> {best}")
